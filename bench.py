@@ -19,10 +19,15 @@ touches a GPU) starts the N rank processes itself and exits with their status.
   --batch B         ciphertexts per GPU (weak scaling, the default: 64 per GPU)
   --total-batch T   T ciphertexts block-partitioned over the ranks (strong scaling;
                     BASELINE configs[3] = --total-batch 512 at N = 2/4/8)
-With N > 1 the line also carries `with_host_scatter` (every rank uploads its own shard from
-page-locked host memory and downloads its results: SURVEY.md 8e's alternative) and
-`with_scatter_gather` (the input slabs sent from rank 0 over xGMI and the results returned to it),
-both with the transfers inside the timed region.
+A plain run sets up, warms up, times the K steps and prints the headline.  Everything else it can
+measure runs only with --full: the per-kernel breakdown and roofline (a profiled pass of the same K
+steps of its own), the CPU baseline, clocks and power, the copy yardstick, the NTT, whole-function and
+reference-shape legs with their check against the restated reference, and at N > 1
+`with_host_scatter` (every rank uploads its own shard from page-locked host memory and downloads its
+results: SURVEY.md 8e's alternative) and `with_scatter_gather` (the input slabs sent from rank 0 over
+xGMI and the results returned to it), both with the transfers inside the timed region.
+  --dump-outputs DIR  after the timed steps, write a fixed sample of what the last step computed
+                      (see dump_outputs) as DIR/<name>.npy; same arguments, same inputs.
 
 Prints ONE JSON line (rank 0).
 """
@@ -42,6 +47,8 @@ ALGO_BYTES_PER_HE_MUL = (7 * DIM_A + 5 * DIM_B) * (8 << LOGN)  # 228,065,280 (SU
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8.0 TB/s spec
 SG_DEADLINE_S = 150    # watchdog of the secondary scatter/gather leg (N > 1)
 SG_FAILED_STATUS = 3   # exit status of every rank when that leg stalls or fails (the line is still printed first)
+DUMP_WORDS = 1 << 19   # --dump-outputs: sampled words per output slab over all ranks (5 slabs x 2 float64 halves: 40 MiB)
+DUMP_SEED = 4242       # fixes which words are sampled
 
 # own read+write bytes of one (limb, polynomial) unit of each kernel, in limbs of n*8 bytes
 KERNEL_LIMB_PASSES = {"strided_fwd": 2, "strided_inv": 2, "tensor_mid": 7, "keyswitch_mid": 5,
@@ -54,6 +61,19 @@ def rand_slab(torch, ctx, dim, batch, gen):
     for d in range(dim):
         out[:, d, :] = torch.randint(0, ctx.p[d], (batch, ctx.n), dtype=torch.int64, device="cuda", generator=gen)
     return out.reshape(-1)
+
+
+def dump_outputs(torch, outdir, slabs, rank, world):
+    """--dump-outputs: the output slabs of the last timed step as DIR/<name>.npy (DIR/<name>_rank<r>.npy at N > 1).  A slab of
+    batch x limbs x n words is far beyond the size budget, so the same DUMP_SEED-drawn word positions are kept in every run; each word
+    (a residue below 2^60, more than float64's 53 bits) is stored exactly as a float64 pair [high 32 bits, low 32 bits], shape (S, 2)."""
+    os.makedirs(outdir, exist_ok=True)
+    per = max(1, DUMP_WORDS // world)
+    for name, t in slabs:
+        idx = np.arange(t.numel()) if t.numel() <= per else np.sort(np.random.default_rng(DUMP_SEED).choice(t.numel(), per, replace=False))
+        w = t[torch.from_numpy(idx).to(t.device)].cpu().numpy().view(np.uint64)
+        pair = np.stack([(w >> np.uint64(32)).astype(np.float64), (w & np.uint64(0xFFFFFFFF)).astype(np.float64)], axis=1)
+        np.save(os.path.join(outdir, (name if world == 1 else "%s_rank%d" % (name, rank)) + ".npy"), pair)
 
 
 def pmc_traffic(kernel, chunk):
@@ -690,17 +710,20 @@ def parse_args(argv=None):
                     "(strong scaling; BASELINE configs[3] = 512); overrides --batch")
     ap.add_argument("--chunk", type=int, default=0, help="polynomials per fused launch group (0 = library default)")
     ap.add_argument("--limb-block", type=int, default=0, help="limbs per launch group (0 = library default: all)")
-    ap.add_argument("--cpu-sample", type=int, default=16, help="ciphertexts the CPU baseline replays (0 = skip)")
-    ap.add_argument("--no-ntt", action="store_true", help="skip the secondary legs run after the timed region (NTT GB/s, MPI-level he_mul, n=2^17 key switch)")
+    ap.add_argument("--full", action="store_true", help="after the headline, also measure and check everything else: per-kernel breakdown and roofline "
+                    "(a profiled pass of its own), CPU baseline, secondary legs, and the transfer legs at N > 1")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write a fixed sample of the last timed step's output slabs as DIR/<name>.npy")
+    ap.add_argument("--cpu-sample", type=int, default=16, help="with --full: ciphertexts the CPU baseline replays (0 = skip)")
+    ap.add_argument("--no-ntt", action="store_true", help="with --full: skip the secondary legs run after the timed region (NTT GB/s, MPI-level he_mul, n=2^17 key switch)")
     ap.add_argument("--variant", default=None, help="dev: path of another build of libgpqhe_hip.so (make -C gpqhe_amd/csrc variant ...) for interleaved A/B timing")
-    ap.add_argument("--quick", action="store_true", help="of the secondary legs keep only the clock / power sample, the VALU floor and the copy yardstick (tests)")
+    ap.add_argument("--quick", action="store_true", help="with --full: of the secondary legs keep only the clock / power sample, the VALU floor and the copy yardstick (tests)")
     ap.add_argument("--lanes", choices=("auto", "1", "2"), default="auto", help="RNS-core steps: gpq_set_overlap of the context (auto = the library's default; 1 for kernel traces "
                     "and PMC passes, whose durations should be those of kernels with nothing running beside them)")
     ap.add_argument("--host-pipeline-sub", type=int, default=2, help="with_host_scatter: ciphertexts per sub-batch of the pipelined (three-stream) variant; 0 = skip it")
     ap.add_argument("--no-affinity", action="store_true", help="leave the process's CPU mask alone (default: bind to the CPUs of the GPU's NUMA node before the first HIP call)")
-    ap.add_argument("--no-check", action="store_true", help="skip the restated-reference check of the whole-function legs (about 40 s of CPU after the timed legs)")
+    ap.add_argument("--no-check", action="store_true", help="with --full: skip the restated-reference check of the whole-function legs (about 40 s of CPU after the timed legs)")
     ap.add_argument("--streams", type=int, default=1, help="2: tensor stage and key-switch stage on separate HIP streams")
-    ap.add_argument("--no-scatter-gather", action="store_true", help="N>1: skip the extra step that has the input slabs scattered from "
+    ap.add_argument("--no-scatter-gather", action="store_true", help="N>1 with --full: skip the extra step that has the input slabs scattered from "
                     "rank 0 and the outputs gathered back inside the timed region (SURVEY.md 8d config 4)")
     ap.add_argument("--backend", default="nccl", help="N>1: nccl = slab transfers over RCCL/xGMI, one rank per GPU (the control plane -- barriers, MAX of "
                     "the timing -- is gloo either way); gloo = everything over gloo, to rehearse several ranks on one GPU")
@@ -708,7 +731,12 @@ def parse_args(argv=None):
     ap.add_argument("--share-gpu", action="store_true", help="testing: with --backend nccl on a node with fewer GPUs than ranks, let ranks share "
                     "a device -- RCCL refuses that at the first transfer, which rehearses a fabric failure inside the scatter/gather leg")
     ap.add_argument("--sg-stall-rank", type=int, default=-1, help="testing: this rank never enters the scatter/gather leg (rehearses a stalled transfer)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.quick and not args.full:
+        ap.error("--quick trims the legs of --full; give both")
+    return args
 
 
 def launch_ranks(n, argv):
@@ -842,7 +870,6 @@ def main(argv=None):
     for _ in range(args.warmup):
         step()
     barrier()
-    ctx.profile(True)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
@@ -851,8 +878,16 @@ def main(argv=None):
     if dist is not None:
         dist.barrier()
     dt = time.perf_counter() - t0
-    ctx.profile(False)
-    prof = ctx.profile_collect()
+    if args.dump_outputs:
+        dump_outputs(torch, args.dump_outputs, (("d0", d0), ("d1", d1), ("d2", d2), ("c0", c0), ("c1", c1)), rank, world)
+    if args.full:
+        # the per-kernel breakdown: the same K steps again with HIP events around every launch, outside the timed region
+        ctx.profile(True)
+        for _ in range(args.steps):
+            step()
+        torch.cuda.synchronize()
+        ctx.profile(False)
+        prof = ctx.profile_collect()
     ranks_seen, devices = 1, ["cuda:%d" % dev_index]
     mine = {"rank": rank, "device": "cuda:%d" % dev_index, "batch": B, "he_mul_per_s": round(B * args.steps / dt_own, 1),
             "ms_per_step": round(dt_own / args.steps * 1e3, 3), "affinity": aff}
@@ -867,12 +902,38 @@ def main(argv=None):
     if rank == 0:
         total_he_mul = total_batch * args.steps
         value = total_he_mul / dt
+        chunk = min(B, args.chunk or 32)
+        out = {
+            "metric": "ciphertext he_mul/sec (RNS core: tensor 30 limbs + key-switch 45 limbs), N=2^16",
+            "value": round(value, 2), "unit": "he_mul/s", "n_gpus": world, "ranks_seen": ranks_seen, "devices": devices,
+            "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": scaling,
+            "vs_baseline": None, "dtype": "u64", "data": "synthetic",
+            "config": {"workload": "he_mul RNS core, n=2^16, dimA=30, dimB=45, %s; he_rescale has no RNS-domain work in the reference"
+                                   % ("batch=%d ciphertexts per GPU (BASELINE configs[2])" % B if scaling == "weak" else
+                                      "batch=%d ciphertexts block-partitioned over %d GPU(s) (BASELINE configs[3])" % (total_batch, world)),
+                       "batch_per_gpu": B, "total_batch": total_batch, "chunk": chunk,
+                       "parallelism": "ciphertext-per-GPU x%d, no data-path collective" % world,
+                       "launcher": "torchrun / external" if os.environ.get("TORCHELASTIC_RUN_ID") else ("self-launched ranks" if world > 1 else "single process"),
+                       "backend": (None if world == 1 else "gloo (control plane) + nccl/RCCL (slab transfers)" if args.backend == "nccl"
+                                   else args.backend)},
+            "he_mul_e2e": {"algo_bytes_per_he_mul": ALGO_BYTES_PER_HE_MUL,
+                           "achieved_GBps_per_gpu": round(ALGO_BYTES_PER_HE_MUL * value / world / 1e9, 1),
+                           "hbm_frac_per_gpu": round(ALGO_BYTES_PER_HE_MUL * value / world / 1e9 / HBM_PEAK_GBS, 4)},
+            # every rank's OWN rate over the same K steps (before the closing barrier), beside the aggregate that the MAX of the wall time gives:
+            # a slow device (the pool's parts differ by +-4 %) or a badly placed rank shows here, not only as a lower `value`
+            "per_rank": summarize_ranks(per_rank),
+            "affinity": aff,
+            # BASELINE's metric is "he_mul/sec + NTT GB/s": the second half and the whole-function rate as TOP-LEVEL scalars (filled in by the legs
+            # of --full; None when a leg was not run: plain run, N > 1, --no-ntt)
+            "ntt_GBps": None, "ntt_hbm_frac": None, "he_mul_whole_per_s": None, "he_mul_plus_he_rescale_whole_per_s": None,
+        }
+    if rank == 0 and args.full:
         # Dominant kernel by accumulated device time.  tensor_mid8 (10 launches) and the inverse strided pass (20 launches: it runs for
         # both stages) are within a few per cent of each other, and which one leads changes with the device: among the kernels within
         # 10 % of the largest share the one with the LOWER fraction of the roofline is reported (the conservative reading, and the same
         # kernel from run to run); `kernels` carries the rate of every kernel either way.
         # strided kernels run for both stages: average units per launch from the launch mix
-        chunk = min(B, args.chunk or 32)
         lb = args.limb_block or 0
         la, lbb = (min(lb, DIM_A), min(lb, DIM_B)) if lb else (DIM_A, DIM_B)
         na, nb = -(-DIM_A // la), -(-DIM_B // lbb)               # launch groups per stage: ceil(limbs / limb block)
@@ -892,36 +953,11 @@ def main(argv=None):
         kbytes = KERNEL_LIMB_PASSES[kname] * units[kname] * (8 << LOGN)
         achieved = kbytes / (kavg * 1e-3) / 1e9
         traffic, traffic_source = pmc_traffic(kname, chunk)
-        out = {
-            "metric": "ciphertext he_mul/sec (RNS core: tensor 30 limbs + key-switch 45 limbs), N=2^16",
-            "value": round(value, 2), "unit": "he_mul/s", "n_gpus": world, "ranks_seen": ranks_seen, "devices": devices,
-            "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": scaling,
-            "vs_baseline": None, "dtype": "u64", "data": "synthetic",
-            "config": {"workload": "he_mul RNS core, n=2^16, dimA=30, dimB=45, %s; he_rescale has no RNS-domain work in the reference"
-                                   % ("batch=%d ciphertexts per GPU (BASELINE configs[2])" % B if scaling == "weak" else
-                                      "batch=%d ciphertexts block-partitioned over %d GPU(s) (BASELINE configs[3])" % (total_batch, world)),
-                       "batch_per_gpu": B, "total_batch": total_batch, "chunk": chunk,
-                       "parallelism": "ciphertext-per-GPU x%d, no data-path collective" % world,
-                       "launcher": "torchrun / external" if os.environ.get("TORCHELASTIC_RUN_ID") else ("self-launched ranks" if world > 1 else "single process"),
-                       "backend": (None if world == 1 else "gloo (control plane) + nccl/RCCL (slab transfers)" if args.backend == "nccl"
-                                   else args.backend)},
-            "roofline": {"bound": "hbm", "kernel": kname, "kernel_rocprof": ROCPROF_NAMES.get(kname, kname),
-                         "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_source,
-                         "bytes_per_launch": int(kbytes), "avg_launch_ms": round(kavg, 4)},
-            "he_mul_e2e": {"algo_bytes_per_he_mul": ALGO_BYTES_PER_HE_MUL,
-                           "achieved_GBps_per_gpu": round(ALGO_BYTES_PER_HE_MUL * value / world / 1e9, 1),
-                           "hbm_frac_per_gpu": round(ALGO_BYTES_PER_HE_MUL * value / world / 1e9 / HBM_PEAK_GBS, 4)},
-            "kernels": kernels,
-            # every rank's OWN rate over the same K steps (before the closing barrier), beside the aggregate that the MAX of the wall time gives:
-            # a slow device (the pool's parts differ by +-4 %) or a badly placed rank shows here, not only as a lower `value`
-            "per_rank": summarize_ranks(per_rank),
-            "affinity": aff,
-            # BASELINE's metric is "he_mul/sec + NTT GB/s": the second half and the whole-function rate as TOP-LEVEL scalars (filled in by the legs
-            # below; None when a leg was not run: N > 1, --no-ntt)
-            "ntt_GBps": None, "ntt_hbm_frac": None, "he_mul_whole_per_s": None, "he_mul_plus_he_rescale_whole_per_s": None,
-        }
+        out["roofline"] = {"bound": "hbm", "kernel": kname, "kernel_rocprof": ROCPROF_NAMES.get(kname, kname),
+                           "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                           "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_source,
+                           "bytes_per_launch": int(kbytes), "avg_launch_ms": round(kavg, 4)}
+        out["kernels"] = kernels
         if world == 1 and args.cpu_sample > 0:
             s = min(args.cpu_sample, B)
             host_in = [gpqhe_amd.to_host(v[: s * DIM_A * ctx.n]) for v in (a0, a1, b0, b1)] + \
@@ -1018,7 +1054,7 @@ def main(argv=None):
             out["reference_default"] = rd
             if not args.no_check:
                 run_checks(out, checks)
-    if dist is not None and not args.no_scatter_gather:
+    if dist is not None and args.full and not args.no_scatter_gather:
         # BASELINE configs[3] with the transfers inside the timed region: rank 0 owns the whole batch, every rank works on its
         # shard, results return to rank 0.  A root-GPU scatter is bound by one xGMI link per peer.  This leg is
         # secondary: a failure is reported in the line, and if the transfers stall a watchdog prints the (complete) compute-only

@@ -70,6 +70,43 @@ def test_total_batch_partition_is_configs3():
     assert a.total_batch == 512 and a.gpus == 8 and not a.no_scatter_gather
 
 
+def test_steps_and_quick_are_checked_before_any_work():
+    b = _bench()
+    assert b.parse_args(["--steps", "7", "--warmup", "0"]).steps == 7
+    a = b.parse_args([])
+    assert not a.full and a.dump_outputs is None
+    for bad in (["--steps", "0"], ["--warmup", "-1"], ["--quick"]):
+        try:
+            b.parse_args(bad)
+        except SystemExit as exc:
+            assert exc.code != 0
+        else:
+            raise AssertionError("accepted %r" % bad)
+    assert b.parse_args(["--full", "--quick"]).quick
+
+
+def test_dump_outputs_is_an_exact_fixed_sample_within_the_size_budget(tmp_path):
+    """--dump-outputs: the same word positions in every run, every 60-bit word exact as a float64 pair [high 32, low 32], and five
+    output slabs of any size stay within 64 MB in all."""
+    import numpy as np
+    import torch
+    b = _bench()
+    big = torch.randint(0, 1 << 60, (b.DUMP_WORDS + 4096,), dtype=torch.int64)
+    small = torch.randint(0, 1 << 60, (1000,), dtype=torch.int64)
+    for d in ("a", "b"):
+        b.dump_outputs(torch, str(tmp_path / d), (("d0", big), ("c1", small)), 0, 1)
+    for name, t in (("d0", big), ("c1", small)):
+        x, y = np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy"))
+        assert x.dtype == np.float64 and x.shape[1] == 2 and np.array_equal(x, y)
+        words = x[:, 0].astype(np.uint64) << np.uint64(32) | x[:, 1].astype(np.uint64)
+        assert np.isin(words, t.numpy().view(np.uint64)).all()
+    assert np.load(tmp_path / "a" / "c1.npy").shape[0] == 1000          # a small slab is kept whole, in order
+    assert np.load(tmp_path / "a" / "d0.npy").shape[0] == b.DUMP_WORDS
+    assert 5 * b.DUMP_WORDS * 2 * 8 <= 64e6
+    b.dump_outputs(torch, str(tmp_path / "r"), (("d0", big),), 1, 2)
+    assert np.load(tmp_path / "r" / "d0_rank1.npy").shape[0] == b.DUMP_WORDS // 2
+
+
 def test_valu_issue_is_computed_from_committed_evidence_not_from_a_literal():
     """bench.py's `valu_issue`: the instruction count per he_mul comes from the newest committed PMC pass, the bound from the newest
     committed probe evaluation (tools/issue_probe + tools/valu_bound.py); both are named in the object, with the commits they were
@@ -112,12 +149,12 @@ import pytest
 
 @pytest.mark.gpu
 def test_the_quick_bench_line_prices_kernels_against_ceilings():
-    """`python bench.py --quick`: the yardstick of `of_copy_rate` is the best of the library's own plain copies measured in the same
+    """`python bench.py --full --quick`: the yardstick of `of_copy_rate` is the best of the library's own plain copies measured in the same
     process, so no kernel may exceed it; the VALU issue floor at the run's clock cannot be exceeded either; the contract keys are there."""
     import json
     import subprocess
     import sys
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--cpu-sample", "1", "--quick"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--cpu-sample", "1", "--full", "--quick"],
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -155,3 +192,45 @@ def test_top_level_metric_keys_are_in_every_line_shape():
     src = open(os.path.join(ROOT, "bench.py")).read()
     assert '"ntt_GBps": None, "ntt_hbm_frac": None, "he_mul_whole_per_s": None, "he_mul_plus_he_rescale_whole_per_s": None' in src
     assert src.index("affinity.bind_to_gpu(") < src.index("    import torch\n    import gpqhe_amd\n")   # placement before torch / HIP in a rank
+
+
+@pytest.mark.gpu
+def test_a_plain_run_times_the_headline_only_and_dumps_what_it_computed(tmp_path, oracle_ctx):
+    """Without --full the line is the headline (value = ciphertexts per step / step time) and none of the legs of --full run; two runs
+    with --dump-outputs write the same files, and the sampled words of ciphertext 0 are the oracle's on the inputs bench.py draws."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    import torch
+    from gpqhe_amd import to_host
+    b = _bench()
+    lines = []
+    for d in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "2", "--dump-outputs", str(tmp_path / d)],
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(json.loads(r.stdout.strip().splitlines()[-1]))
+    line = lines[0]
+    assert line["unit"] == "he_mul/s" and line["higher_is_better"] is True and line["dtype"] == "u64" and line["steps"] == 3
+    assert abs(line["value"] * line["ms_per_step"] / 2e3 - 1) < 5e-4 / line["ms_per_step"] + 1e-4     # (ms_per_step is rounded to 1 us)
+    for key in ("roofline", "kernels", "cpu_baseline", "copy_rate", "ntt", "he_mul_mpi_level", "with_host_scatter"):
+        assert key not in line, key
+    o = oracle_ctx(b.LOGN, b.DIM_B)
+    gen = torch.Generator(device="cuda")
+    gen.manual_seed(1000)
+    a0, a1, b0, b1 = (to_host(b.rand_slab(torch, o, b.DIM_A, 2, gen)) for _ in range(4))
+    x = to_host(b.rand_slab(torch, o, b.DIM_B, 2, gen))
+    gk = torch.Generator(device="cuda")
+    gk.manual_seed(3000)
+    e0, e1 = to_host(b.rand_slab(torch, o, b.DIM_B, 1, gk)), to_host(b.rand_slab(torch, o, b.DIM_B, 1, gk))
+    perA, perB = b.DIM_A * o.n, b.DIM_B * o.n
+    want = dict(zip(("d0", "d1", "d2"), o.he_mul_tensor(a0[:perA], a1[:perA], b0[:perA], b1[:perA], b.DIM_A)))
+    want.update(zip(("c0", "c1"), o.keyswitch(np.ascontiguousarray(x[:perB]), e0, e1, b.DIM_B)))
+    for name, per in (("d0", perA), ("d1", perA), ("d2", perA), ("c0", perB), ("c1", perB)):
+        got = np.load(tmp_path / "a" / (name + ".npy"))
+        assert np.array_equal(got, np.load(tmp_path / "b" / (name + ".npy")))
+        idx = np.sort(np.random.default_rng(b.DUMP_SEED).choice(2 * per, b.DUMP_WORDS, replace=False))
+        words = got[:, 0].astype(np.uint64) << np.uint64(32) | got[:, 1].astype(np.uint64)
+        first = idx < per
+        assert first.sum() > 1000 and np.array_equal(words[first], want[name][idx[first]]), name

@@ -114,7 +114,7 @@ def test_bench_starts_its_own_ranks():
     reports its placement and its OWN rate beside the MAX-time aggregate (round 6)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--backend", "gloo", "--total-batch", "9",
-           "--steps", "1", "--warmup", "1", "--cpu-sample", "0", "--no-ntt"]
+           "--steps", "1", "--warmup", "1", "--full", "--cpu-sample", "0", "--no-ntt"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=840, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -144,7 +144,7 @@ def test_a_stalled_scatter_gather_leg_is_a_failure_not_a_success():
     line (with the error, its rank and the stage it was stuck in), and the exit status that reaches the caller is non-zero."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--total-batch", "4",
-           "--steps", "1", "--warmup", "1", "--cpu-sample", "0", "--no-ntt", "--sg-stall-rank", "1", "--sg-deadline", "10"]
+           "--steps", "1", "--warmup", "1", "--full", "--cpu-sample", "0", "--no-ntt", "--sg-stall-rank", "1", "--sg-deadline", "10"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=540, cwd=ROOT)
     assert r.returncode == 3, (r.returncode, r.stderr[-2000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -162,7 +162,7 @@ def test_a_failing_rccl_group_costs_the_transfer_leg_only():
     scatter/gather entry carries the error, the exit status is non-zero."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "nccl", "--share-gpu", "--total-batch", "4",
-           "--steps", "1", "--warmup", "1", "--cpu-sample", "0", "--no-ntt", "--sg-deadline", "40"]
+           "--steps", "1", "--warmup", "1", "--full", "--cpu-sample", "0", "--no-ntt", "--sg-deadline", "40"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=540, cwd=ROOT)
     assert r.returncode == 3, (r.returncode, r.stderr[-2000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
