@@ -3,7 +3,8 @@
 // These keep the reference's calling convention exactly: one limb in host
 // memory, `const struct rns_ctx *` for the prime, ring degree from the global
 // `polyctx`, void return, abort() on misuse.  Each call ships the limb to the
-// GPU, runs the same kernels as the slab API and ships the result back, so a
+// GPU (words outside the kernels' domain aside: pointwise() below), runs the
+// same kernels as the slab API and ships the result back, so a
 // GPQHE binary linked against this library produces the reference's bits
 // while its own limb loops are still on the host.  The slab API
 // (gpqhe_hip.h) is the fast path; this file is the compatibility path.
@@ -85,7 +86,17 @@ void transform(uint64_t a[], const struct rns_ctx *rns, bool inverse) {
 void pointwise(uint64_t r[], const uint64_t a[], const uint64_t b[], const struct rns_ctx *rns, bool mul) {
   std::lock_guard<std::mutex> lock(g_mu);
   Slot &s = slot_for(rns);
-  const size_t bytes = sizeof(uint64_t) << s.logn;
+  const size_t n = (size_t)1 << s.logn, bytes = sizeof(uint64_t) << s.logn;
+  // The slab kernels are exact for words in [0, p] (p: what ntt stores for a residue 0, src/ntt.c:47).  src/poly.c:71-82 takes
+  // ANY 64-bit words to barrett_reduce, which outside that range is not even a mod p; a limb holding such a word runs that loop
+  // as written, on the host, with this library's barrett_reduce (below).
+  bool in_domain = true;
+  for (size_t i = 0; i < n; ++i) in_domain &= (a[i] <= s.p) & (b[i] <= s.p);
+  if (!in_domain) {
+    for (size_t i = 0; i < n; ++i)
+      r[i] = barrett_reduce(mul ? (gpq_u128)a[i] * b[i] : (gpq_u128)a[i] + b[i], rns->p, rns->pinv_barr);
+    return;
+  }
   int rc = gpq_upload(s.dev[0], a, bytes, nullptr);
   if (rc == GPQ_OK) rc = gpq_upload(s.dev[1], b, bytes, nullptr);
   if (rc == GPQ_OK)

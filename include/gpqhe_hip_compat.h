@@ -96,7 +96,10 @@ void poly_ntt(uint64_t a[], const struct rns_ctx *rns);
 void poly_invntt(uint64_t a[], const struct rns_ctx *rns);
 
 /* src/poly.c:71-82, declared src/poly.h:84-85.  rhat may alias ahat/bhat
- * (src/he-mult.c:130,183). */
+ * (src/he-mult.c:130,183).  Any 64-bit input words, as there: a limb whose
+ * words all lie in [0, p] (canonical residues, and p as ntt stores a residue
+ * 0) runs on the GPU; a limb holding any other word runs the reference's
+ * loop, barrett_reduce of the 128-bit product / sum, on the host. */
 void poly_rns_add(uint64_t rhat[], const uint64_t ahat[], const uint64_t bhat[], const struct rns_ctx *rns);
 void poly_rns_mul(uint64_t rhat[], const uint64_t ahat[], const uint64_t bhat[], const struct rns_ctx *rns);
 

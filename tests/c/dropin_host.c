@@ -7,7 +7,8 @@
  * d1 = x + y step of he_mul (src/he-mult.c:136) through poly_rns_add.
  *
  * usage: dropin_host <logn> <dim> <seed>   -> prints FNV-1a-64 digests
- * The pytest wrapper compares them with the oracle's.
+ * The pytest wrapper compares them with the oracle's.  The `xform` and
+ * `pointwise` modes below run single symbols on words read from files.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -75,9 +76,55 @@ static int xform(int argc, char **argv)
   return 0;
 }
 
+/* dropin_host pointwise <logn> <nprimes> <afile> <bfile> <outfile> <limb>...: rows k of two uint64[rows][n] files, row k with prime
+ * <limb k> of the first <nprimes> of the engine's chain for 2^logn, through the reference-named symbols: poly_rns_mul(r, a, b),
+ * poly_rns_add(s, a, b) and the aliased poly_rns_mul(a, a, b) (src/he-mult.c:130).  Writes uint64[3][rows][n]: r, s, a.  Any input
+ * words (the out-of-domain cases of tests/test_dropin_c_gpu.py). */
+static int pointwise(int argc, char **argv)
+{
+  if (argc < 8) return 2;
+  unsigned logn = (unsigned)atoi(argv[2]), nprimes = (unsigned)atoi(argv[3]);
+  size_t n = (size_t)1 << logn, rows = (size_t)(argc - 7);
+  memset(&polyctx, 0, sizeof polyctx);
+  polyctx.logn = logn; polyctx.n = (unsigned)n; polyctx.m = 2 * (unsigned)n;
+  polyctx.logR = 64; polyctx.R = (gpq_u128)1 << 64; polyctx.Rsub1 = polyctx.R - 1;
+  polyctx.dimub = nprimes;
+  gpq_ctx *ctx = NULL;
+  if (gpq_ctx_create(&ctx, logn, nprimes, 0) != GPQ_OK) { fprintf(stderr, "%s\n", gpq_last_error()); return 1; }
+  struct rns_ctx *nodes = calloc(nprimes, sizeof *nodes);
+  if (gpq_fill_rns_chain(nodes, nprimes, ctx, 0) != GPQ_OK) { fprintf(stderr, "gpq_fill_rns_chain failed\n"); return 1; }
+  polyctx.rns = nodes;
+  uint64_t *a = malloc(rows * n * 8), *b = malloc(rows * n * 8), *out = malloc(3 * rows * n * 8);
+  const char *in[2] = {argv[4], argv[5]};
+  uint64_t *dst[2] = {a, b};
+  for (int j = 0; j < 2; j++) {
+    FILE *f = fopen(in[j], "rb");
+    if (!f || fread(dst[j], 8, rows * n, f) != rows * n) { fprintf(stderr, "cannot read %s\n", in[j]); return 1; }
+    fclose(f);
+  }
+  for (size_t k = 0; k < rows; k++) {
+    const unsigned d = (unsigned)atoi(argv[7 + k]);
+    if (d >= nprimes) { fprintf(stderr, "limb %u out of the chain\n", d); return 1; }
+    uint64_t *r = out + k * n, *s = out + (rows + k) * n, *t = out + (2 * rows + k) * n;
+    poly_rns_mul(r, a + k * n, b + k * n, &nodes[d]);
+    poly_rns_add(s, a + k * n, b + k * n, &nodes[d]);
+    memcpy(t, a + k * n, n * 8);
+    poly_rns_mul(t, t, b + k * n, &nodes[d]);
+  }
+  FILE *f = fopen(argv[6], "wb");
+  if (!f || fwrite(out, 8, 3 * rows * n, f) != 3 * rows * n) { fprintf(stderr, "cannot write %s\n", argv[6]); return 1; }
+  fclose(f);
+  gpq_dropin_reset();
+  gpq_release_rns_chain(nodes);
+  gpq_ctx_destroy(ctx);
+  free(nodes); free(a); free(b); free(out);
+  return 0;
+}
+
 int main(int argc, char **argv)
 {
   if (argc > 1 && strcmp(argv[1], "xform") == 0) return xform(argc, argv);
+  if (argc > 1 && strcmp(argv[1], "pointwise") == 0) return pointwise(argc, argv);
   if (argc < 4) return 2;
   unsigned logn = (unsigned)atoi(argv[1]), dim = (unsigned)atoi(argv[2]);
   uint64_t seed = strtoull(argv[3], NULL, 10);

@@ -5,6 +5,7 @@ FORCED through the exact kernels behind the streaming tail (they are written unr
 launch groups and lanes, with the streaming bridge off (two calls inside), and for a Delta of more than one word (two calls inside)."""
 import pytest
 
+from tests.he_anchors import assert_anchored, expect_all, group_ends, he_mul_tasks
 from tests.test_stream_bridge_gpu import SHAPES, _centred
 
 pytestmark = pytest.mark.gpu
@@ -66,6 +67,7 @@ def test_he_mul_rs_equals_he_mul_then_he_rs(engine_ctx, logn, logqL, logql, batc
         g.set_stream_bridge(True)
 
 
+@pytest.mark.timeout(900)
 @pytest.mark.parametrize("lanes", [0, 1])
 def test_he_mul_rs_across_launch_groups_and_lanes(engine_ctx, lanes):
     torch = _torch()
@@ -93,6 +95,11 @@ def test_he_mul_rs_across_launch_groups_and_lanes(engine_ctx, lanes):
         g.set_overlap(-1)
     for a, b, c, d in zip(want, got, forced, plain):
         assert torch.equal(a, b) and torch.equal(a, c) and torch.equal(a, d)
+    # the restated reference (he_mul, then he_rs by Delta = 2^50) at the first and the last ciphertext of every launch group of 3
+    idx = group_ends(batch, 3)
+    res = expect_all(he_mul_tasks(logn, logq, W, dims, cts, rlk, idx, rs=50))
+    assert_anchored("c0", got[0], res, "rs0", idx, W * n)
+    assert_anchored("c1", got[1], res, "rs1", idx, W * n)
 
 
 def test_he_mul_rs_rejects_a_delta_that_is_not_inside_the_modulus(engine_ctx):

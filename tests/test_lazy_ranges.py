@@ -214,3 +214,28 @@ def test_wide_gs_stage_ranges_close(c):
             assert t < 2 * p
             r = t - p if t >= p else t
             assert r == val * w % p
+
+
+def barrett_reduce(a, q, qinv):
+    """src/reduce.c:88-106 on Python integers (128-bit input, 64-bit words)"""
+    shift = 2 * q.bit_length() - 64
+    lo, hi = a & M64, a >> 64
+    est = (((lo * qinv) >> 64) + hi * qinv) >> shift
+    r = (a - est * q) & M64
+    return r - q if r >= q else r
+
+
+@pytest.mark.parametrize("c", [257, 12582913, WIDE_CMAX, SPLIT_CMAX, 319000000])   # up to GPQ_FOLD_CMAX
+def test_barrett_is_exact_on_the_drop_in_device_domain(c):
+    """The drop-in poly_rns_mul / poly_rns_add (gpqhe_amd/csrc/dropin.hip) hand a limb to the device kernels only when every word
+    is in [0, p]; there src/poly.c's barrett_reduce of a*b and a+b is exactly the residue the kernels compute (a*b <= p^2 < 2^119
+    keeps Barrett's estimate within one of the quotient, so one conditional subtraction finishes), and the device is checked
+    against it bit for bit (tests/test_dropin_c_gpu.py).  Outside [0, p] it is not: there the library runs the reference's loop."""
+    p = (1 << 59) + c
+    pinv = (1 << (2 * p.bit_length())) // p                  # barrett_inv, src/reduce.c:75-78
+    rng = random.Random(c)
+    words = [0, 1, 2, p // 2, p - 2, p - 1, p] + [rng.randrange(0, p + 1) for _ in range(200)]
+    for a in words:
+        for b in words[:40]:
+            assert barrett_reduce(a * b, p, pinv) == a * b % p
+            assert barrett_reduce(a + b, p, pinv) == (a + b) % p

@@ -3,7 +3,11 @@ stream through a peer context (src/he-mult.c:116-141, :40-85 and src/he-automorp
 batch is this library's).  Same words as the single-stream order, for multiplications, squarings and key switches, with coefficients forced
 through the exact paths, with a ragged last group; the call stays ordered on the caller's stream (inputs written just before it, outputs read
 just after it, on a non-default stream, no host synchronisation in between); and it can be captured into a HIP graph with both lanes."""
+import numpy as np
 import pytest
+
+from gpqhe_amd import to_host
+from tests.he_anchors import assert_anchored, expect_all, group_ends, he_mul_tasks, he_swk_tasks
 
 pytestmark = pytest.mark.gpu
 
@@ -45,6 +49,7 @@ def _run(g, torch, cts, rlk, W, logq, dims, square=False):
     return o
 
 
+@pytest.mark.timeout(900)
 @pytest.mark.parametrize("logn,logq,batch,chunk", [(13, 438, 7, 2), (14, 438, 5, 1), (16, 850, 3, 1), (10, 130, 9, 4)])
 def test_two_lanes_give_the_words_of_one(engine_ctx, logn, logq, batch, chunk):
     import torch
@@ -71,6 +76,13 @@ def test_two_lanes_give_the_words_of_one(engine_ctx, logn, logq, batch, chunk):
         assert torch.equal(a, d), name + " (separate kernels)"
         assert torch.equal(e[0], e[1]), name + " (squaring)"
     assert bool((want[0] != 0).any()) and bool((want[3] != 0).any())
+    if logn <= 13:                                  # the restated reference at the ends of every launch group, the short last one included
+        idx = group_ends(batch, chunk)
+        res = expect_all(he_mul_tasks(logn, logq, W, dims, cts, rlk, idx) + he_swk_tasks(logn, logq, W, dims, cts[2:], rlk, idx))
+        per = W * g.n
+        for name, t, r, key in (("he_mul c0", got[0], res, "c0"), ("he_mul c1", got[1], res, "c1"),
+                                ("he_swk c0", got[2], res[len(idx):], "c0"), ("he_swk c1", got[3], res[len(idx):], "c1")):
+            assert_anchored(name, t, r, key, idx, per)
 
 
 def test_the_call_stays_ordered_on_the_callers_stream(engine_ctx):
@@ -156,7 +168,7 @@ def test_two_lanes_in_a_hip_graph(engine_ctx):
 
 
 @pytest.mark.parametrize("logn,dim,batch,chunk", [(13, 5, 7, 2), (16, 4, 5, 2), (17, 3, 3, 1)])
-def test_rns_core_on_two_lanes(engine_ctx, logn, dim, batch, chunk):
+def test_rns_core_on_two_lanes(engine_ctx, oracle_ctx, logn, dim, batch, chunk):
     """gpq_he_mul_tensor / gpq_keyswitch (the limb loops of src/he-mult.c:116-138, :58-66) over several launch groups: same words on one and two lanes"""
     import torch
     from bench import rand_slab
@@ -189,6 +201,18 @@ def test_rns_core_on_two_lanes(engine_ctx, logn, dim, batch, chunk):
     for i, (w, x, y) in enumerate(zip(want, got, again)):
         assert torch.equal(w, x) and torch.equal(w, y), "result %d" % i
     assert bool((want[1] != 0).any()) and bool((want[7] != 0).any())
+    # the oracle (src/he-mult.c:116-138, :58-66) at the first and the last ciphertext of every launch group, the short last one included
+    o = oracle_ctx(logn, dim)
+    per = dim * g.n
+    host = [to_host(t) for t in a]
+    keys = [to_host(t) for t in evk]
+    out = [to_host(t) for t in got]
+    for j in group_ends(batch, chunk):
+        sl = slice(j * per, (j + 1) * per)
+        x = [np.ascontiguousarray(h[sl]) for h in host]
+        ref = o.he_mul_tensor(x[0], x[1], x[2], x[3], dim) + o.he_mul_tensor(x[0], x[1], x[0], x[1], dim) + o.keyswitch(x[4], keys[0], keys[1], dim)
+        for i, (w, r) in enumerate(zip(ref, out)):
+            assert np.array_equal(r[sl], w), "result %d of ciphertext %d differs from the oracle" % (i, j)
 
 
 def test_a_peer_that_cannot_be_created_means_one_lane_not_an_error():

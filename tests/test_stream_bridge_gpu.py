@@ -6,6 +6,8 @@ for he_swk with and without an addend, across launch groups; and with coefficien
 ones (gpq_debug_force_redo: every k-th coefficient is flagged as if it sat in a rounding window), which must not change a word."""
 import pytest
 
+from tests.he_anchors import assert_anchored, expect_all, group_ends, he_mul_tasks, he_swk_tasks
+
 pytestmark = pytest.mark.gpu
 
 
@@ -81,6 +83,7 @@ def test_streaming_bridge_equals_the_separate_kernels(engine_ctx, logn, logqL, l
     assert bool((want[0] != 0).any()) and bool((want[3] != 0).any())
 
 
+@pytest.mark.timeout(900)
 def test_streaming_bridge_across_launch_groups(engine_ctx):
     """more ciphertexts than one launch group (gpq_set_chunk): the per-wave flag words and the scratch of a group are reused by the next"""
     torch = _torch()
@@ -110,6 +113,13 @@ def test_streaming_bridge_across_launch_groups(engine_ctx):
         g.set_chunk(32)
     for a, b, c in zip(want, got, forced):
         assert torch.equal(a, b) and torch.equal(a, c)
+    # the restated reference at the first and the last ciphertext of every launch group of 3, the short last one included
+    idx = group_ends(batch, 3)
+    dims = (dimA, dimB, dimP)
+    res = expect_all(he_mul_tasks(logn, logq, W, dims, cts, rlk, idx) + he_swk_tasks(logn, logq, W, dims, cts[:2], rlk, idx))
+    for name, t, r, key in (("he_mul c0", got[0], res, "c0"), ("he_mul c1", got[1], res, "c1"),
+                            ("he_swk c0", got[2], res[len(idx):], "c0"), ("he_swk c1", got[3], res[len(idx):], "c1")):
+        assert_anchored(name, t, r, key, idx, W * n)
 
 
 def test_flag_bytes_grow_inside_a_tail_that_cannot_stream():
