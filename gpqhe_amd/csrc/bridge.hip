@@ -1689,6 +1689,11 @@ int launch_smod_general(gpq_ctx *c, uint64_t *out, unsigned Wout, const uint64_t
   if (Wx > (unsigned)SMOD_MAXW) return gpq_fail(GPQ_ERR_UNSUPPORTED, "general modulus: value of %u words", Wx);
   Big mu = floor_pow2_div(128 * L, M), half = M;
   shr1(half);
+  // M = b^(L-1) exactly (q = 1, 2^64, 2^128, ...) gives mu = b^(L+1), one word more than the kernel reads: clamp it to
+  // b^(L+1) - 1.  The quotient estimate is then low by at most 3 (not 2), which the kernel's three subtractions absorb.
+  bool wide = false;
+  for (size_t j = L + 1; j < mu.size(); ++j) wide |= mu[j] != 0;
+  if (wide) mu.assign(L + 1, ~0ull);
   std::vector<uint64_t> consts(kModConstWords, 0);
   put(consts, 0, M, L); put(consts, 64, mu, L + 1); put(consts, 128, half, L);
   HIP_TRY(hipMemcpyAsync(dconst, consts.data(), consts.size() * 8, hipMemcpyHostToDevice, s));

@@ -646,7 +646,8 @@ __global__ __launch_bounds__(64) void bridge_smod_general(SmodArgs a) {
         bor = (uint64_t)(d >> 64) & 1;
       }
     }
-    // at most two corrective subtractions (HAC 14.42 step 4)
+    // corrective subtractions (HAC 14.42 step 4): two with the exact mu, three when the host clamped mu to b^(L+1) - 1
+    // (M = b^(L-1)); r < 4M < b^(L+1) then, so the value mod b^(L+1) above is still exact
     for (int rep = 0; rep < 3; ++rep) {
       uint64_t bor = 0;
       uint64_t t_[SMOD_MAXW / 2 + 3];

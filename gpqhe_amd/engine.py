@@ -263,9 +263,32 @@ class PolyContext:
         return ws
 
     @staticmethod
-    def _words(q):
-        L = (q.bit_length() + 63) // 64
+    def _words(q, Lq=None):
+        """q as little-endian words; Lq > the words q needs passes zero top words"""
+        L = Lq or (q.bit_length() + 63) // 64
         return (_native.u64 * L)(*[(q >> (64 * j)) & 0xFFFFFFFFFFFFFFFF for j in range(L)]), L
+
+    def rns_reconstruct_general(self, big, Wout, slab, dim, q, Lq=None):
+        """src/poly.c:109-120 for an arbitrary modulus q (Python int): centred mod P, then mpi_smod(., q)."""
+        torch = _torch()
+        batch = self._shape(slab, dim)
+        qw, L = self._words(q, Lq)
+        scratch = torch.empty(self.lib.gpq_poly_mul_general_workspace_bytes(self.h, dim, batch) // 8 + 8, dtype=torch.int64, device=self._dev)
+        _native.check(self.lib.gpq_rns_reconstruct_general(self.h, self._ptr(big), Wout, self._ptr(slab), dim, batch, qw, L, self._ptr(scratch), self._stream()),
+                      "gpq_rns_reconstruct_general")
+        return big
+
+    def relin_tail_general(self, out, chat, d, W, ql, dimB, dimP):
+        """src/he-mult.c:67-77 alone for an arbitrary q_l (d = None: nothing added)."""
+        torch = _torch()
+        batch = self._shape(chat, dimB)
+        qw, L = self._words(ql)
+        # the tail runs all `batch` polynomials in one group; the one-polynomial general workspace times batch covers it
+        nbytes = batch * self.lib.gpq_he_general_workspace_bytes(self.h, W, 0, dimB, dimP, 1)
+        ws = torch.empty(nbytes // 8 + 8, dtype=torch.int64, device=self._dev)
+        _native.check(self.lib.gpq_relin_tail_general(self.h, self._ptr(out), self._ptr(chat), self._ptr(d) if d is not None else None, W, qw, L, dimB, dimP,
+                                                      batch, self._ptr(ws), self._stream()), "gpq_relin_tail_general")
+        return out
 
     def he_mul_general(self, out_c0, out_c1, ct1c0, ct1c1, ct2c0, ct2c1, rlk0, rlk1, W, ql, dimA, dimB, dimP):
         """src/he-mult.c:88-156 for an arbitrary q_l (Python int)."""
@@ -300,6 +323,16 @@ class PolyContext:
         ws = torch.empty(self.lib.gpq_he_mulpt_workspace_bytes(self.h, dim, batch) // 8 + 8, dtype=torch.int64, device=self._dev)
         _native.check(self.lib.gpq_he_mulpt(self.h, self._ptr(out_c0), self._ptr(out_c1), self._ptr(c0), self._ptr(c1), self._ptr(m), W, logql, dim, batch,
                                             self._ptr(ws), self._stream()), "gpq_he_mulpt")
+
+    def he_mulpt_general(self, out_c0, out_c1, c0, c1, m, W, ql, dim):
+        """src/he-mult.c:159-196 for an arbitrary q_l (Python int)."""
+        torch = _torch()
+        batch = c0.numel() // (W * self.n)
+        qw, L = self._words(ql)
+        nbytes = self.lib.gpq_he_mulpt_workspace_bytes(self.h, dim, batch) + self.lib.gpq_poly_mul_general_workspace_bytes(self.h, dim, batch)
+        ws = torch.empty(nbytes // 8 + 8, dtype=torch.int64, device=self._dev)
+        _native.check(self.lib.gpq_he_mulpt_general(self.h, self._ptr(out_c0), self._ptr(out_c1), self._ptr(c0), self._ptr(c1), self._ptr(m), W, qw, L, dim,
+                                                    batch, self._ptr(ws), self._stream()), "gpq_he_mulpt_general")
 
     def he_genswk(self, evk0, evk1, p1, sk, e, sp, W, dimP, logqL, dimevk):
         """src/he-kem.c:74-118 from host-sampled p1 / e and the hidden polynomial sp; q_L = 2^logqL."""
