@@ -123,6 +123,11 @@ SIGNATURES = {
     "gpq_he_genswk": (C.c_int, [vp] * 7 + [C.c_uint] * 4 + [vp, vp]),
     "gpq_he_swk_workspace_bytes": (C.c_size_t, [vp, C.c_uint, C.c_uint, C.c_uint, C.c_uint]),
     "gpq_he_swk": (C.c_int, [vp] * 7 + [C.c_uint] * 5 + [vp, vp]),
+    "gpq_automorphism_index": (C.c_int, [C.c_uint, u64, vp]),
+    "gpq_he_rot_hoisted_workspace_bytes": (C.c_size_t, [vp] + [C.c_uint] * 5),
+    "gpq_he_rot_hoisted": (C.c_int, [vp] * 8 + [C.c_uint] * 6 + [vp, vp]),
+    "gpq_he_gemv_workspace_bytes": (C.c_size_t, [vp] + [C.c_uint] * 6),
+    "gpq_he_gemv": (C.c_int, [vp] * 8 + [C.c_uint] * 8 + [vp, vp]),
     "gpq_profile_enable": (C.c_int, [vp, C.c_int]),
     "gpq_profile_kernels": (C.c_int, []),
     "gpq_profile_kernel_name": (C.c_char_p, [C.c_int]),
@@ -166,6 +171,7 @@ SIGNATURES = {
 EXPORTED_ONLY = ["montgomery_reduce", "barrett_reduce",
                  # MPI-typed surface: driven from C with real libgcrypt MPIs (tests/c/mpi_host.c)
                  "rns_decompose", "rns_reconstruct", "poly_rns2mpi", "poly_mul", "he_mul", "he_rs", "he_rescale", "he_moddown", "he_mulpt", "he_add", "he_sub", "he_addpt", "he_subpt", "he_neg", "he_copy_ct", "he_dec", "he_conj", "he_rot", "he_genrlk", "he_genck", "he_genrk",
+                 "he_gemv", "he_sum", "he_idx",
                  ]
 # libgpqhe_hip_ctx.so (ctx_compat.hip): context construction / storage names for hosts that are not GPQHE; driven from C
 CTX_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libgpqhe_hip_ctx.so")

@@ -1527,6 +1527,193 @@ extern "C" size_t gpq_he_swk_workspace_bytes(gpq_ctx *c, unsigned W, unsigned di
   return align64((size_t)m * 3 * dimB * c->n * 8) + align64(gpq_keyswitch_workspace_bytes(c, dimB, m)) + align64(tp.bytes);
 }
 
+// ---------------------------------------------------------------------------
+// Hoisted rotations: he_rot (src/he-automorphism.c:101-115) of one ciphertext by several amounts.  The reference decomposes and transforms
+// poly_rot(c1, r) for every r (:59-61); here c1 is decomposed and transformed once per launch group and each rotation permutes that
+// transform (NTT(poly_rot(a, r)) = NTT(a) o sigma, ntt_kernels.hpp: automorphism_src).  The residues are those of the reference; the
+// words of a forward transform can differ only where the reference stores p for 0 (src/ntt.c:45-48), and the product with the key
+// reduces both to the same word, so every word from the product on is the reference's.
+// ---------------------------------------------------------------------------
+namespace {
+uint64_t rot_power(unsigned rot) {                  // 5^rot modulo 2^64, as src/poly.c:266-268's size_t computes it
+  uint64_t r = 1, b = 5;
+  for (unsigned e = rot; e; e >>= 1, b *= b) if (e & 1) r *= b;
+  return r;
+}
+struct HoistPlan { size_t x, chat, ks, rot, tail, total; };
+int hoist_plan(gpq_ctx *c, unsigned W, unsigned dimB, unsigned dimP, unsigned nrot, unsigned m, HoistPlan *h) {
+  TailPlan tp;
+  int rc = tail_plan(c, W, dimP, dimB, 2 * m, &tp);
+  if (rc) return rc;
+  const size_t n = c->n, slab = (size_t)m * dimB * n * 8, big = (size_t)m * W * n * 8;
+  if (nrot == 1) {                                   // he_swk as it is: both rotated polynomials, then gpq_he_swk
+    *h = HoistPlan{0, 0, 0, 2 * align64(big), 0, 0};
+    h->total = h->rot + align64(gpq_he_swk_workspace_bytes(c, W, dimB, dimP, m));
+    return GPQ_OK;
+  }
+  h->x = align64(slab);
+  h->chat = align64(2 * slab);
+  h->ks = c->logn > 12 ? 0 : align64(gpq_keyswitch_workspace_bytes(c, dimB, m));
+  h->rot = align64(big);
+  h->tail = align64(tp.bytes);
+  h->total = h->x + h->chat + h->ks + h->rot + h->tail;
+  return GPQ_OK;
+}
+}  // namespace
+
+extern "C" size_t gpq_he_rot_hoisted_workspace_bytes(gpq_ctx *c, unsigned W, unsigned dimB, unsigned dimP, unsigned nrot, unsigned batch) {
+  if (!c || !nrot || !batch) return 0;
+  HoistPlan h;
+  return hoist_plan(c, W, dimB, dimP, nrot, batch < c->chunk ? batch : c->chunk, &h) == GPQ_OK ? h.total : 0;
+}
+
+extern "C" int gpq_he_rot_hoisted(gpq_ctx *c, uint64_t *out_c0, uint64_t *out_c1, const uint64_t *c0, const uint64_t *c1,
+                                  const unsigned *rots, const uint64_t *const *rk0, const uint64_t *const *rk1, unsigned nrot,
+                                  unsigned W, unsigned logql, unsigned dimB, unsigned dimP, unsigned batch, void *workspace, void *stream) {
+  int rc = check(c, dimB, batch, "gpq_he_rot_hoisted");
+  if (rc) return rc;
+  if (!out_c0 || !out_c1 || !c0 || !c1 || !rots || !rk0 || !rk1 || !nrot || !workspace || !logql || W < (logql + 63) / 64)
+    return gpq_fail(GPQ_ERR_INVALID, "gpq_he_rot_hoisted: bad arguments");
+  for (unsigned r = 0; r < nrot; ++r)
+    if (!rk0[r] || !rk1[r]) return gpq_fail(GPQ_ERR_INVALID, "gpq_he_rot_hoisted: key %u is NULL", r);
+  hipStream_t s = (hipStream_t)stream;
+  const size_t n = c->n, bigpoly = (size_t)W * n;
+  {   // every rotation reads c0 / c1 again after earlier rotations wrote their outputs: no overlap anywhere among the four ranges
+    const size_t in_words = (size_t)batch * bigpoly, out_words = (size_t)nrot * in_words;
+    auto overlap = [](const uint64_t *a, size_t na, const uint64_t *b, size_t nb) { return a < b + nb && b < a + na; };
+    if (overlap(out_c0, out_words, out_c1, out_words) || overlap(out_c0, out_words, c0, in_words) || overlap(out_c0, out_words, c1, in_words) ||
+        overlap(out_c1, out_words, c0, in_words) || overlap(out_c1, out_words, c1, in_words))
+      return gpq_fail(GPQ_ERR_INVALID, "gpq_he_rot_hoisted: the outputs alias each other or an input");
+  }
+  const unsigned m = batch < c->chunk ? batch : c->chunk;
+  HoistPlan hp;
+  if ((rc = hoist_plan(c, W, dimB, dimP, nrot, m, &hp))) return rc;
+  char *w = (char *)workspace;
+  if (nrot == 1) {                                   // nothing to share: poly_rot x2 + gpq_he_swk, group by group
+    uint64_t *d0 = (uint64_t *)w, *d1 = (uint64_t *)(w + hp.rot / 2);
+    for (unsigned k0 = 0; k0 < batch; k0 += m) {
+      const unsigned polys = batch - k0 < m ? batch - k0 : m;
+      const size_t o = k0 * bigpoly;
+      if ((rc = gpq_poly_rot(c, d0, c0 + o, W, rots[0], polys, stream)) || (rc = gpq_poly_rot(c, d1, c1 + o, W, rots[0], polys, stream))) return rc;
+      if ((rc = gpq_he_swk(c, out_c0 + o, out_c1 + o, d0, d1, rk0[0], rk1[0], W, logql, dimB, dimP, polys, w + hp.rot, stream))) return rc;
+    }
+    return launched("gpq_he_rot_hoisted");
+  }
+  uint64_t *X = (uint64_t *)w; w += hp.x;
+  uint64_t *chat = (uint64_t *)w; w += hp.chat;
+  void *wsK = w; w += hp.ks;
+  uint64_t *d0 = (uint64_t *)w; w += hp.rot;
+  void *wsTail = w;
+  const LimbTab *tabsP = nullptr;
+  int tail_mode = 0;
+  if ((rc = tail_prescale_mode(c, dimP, dimB, &tabsP, &tail_mode))) return rc;
+  const uint64_t mask2n = 2 * (uint64_t)n - 1;
+  for (unsigned k0 = 0; k0 < batch; k0 += m) {
+    const unsigned polys = batch - k0 < m ? batch - k0 : m;
+    const size_t pb = (size_t)polys * dimB * n;
+    {
+      StageRange stage("gpq_he_rot_hoisted: rns_decompose + forward transform of c1 (once per group)");
+      if ((rc = launch_decompose(c, X, c1 + k0 * bigpoly, W, 0, dimB, polys, s))) return rc;                 // src/he-automorphism.c:60
+      if ((rc = gpq_hoist_forward(c, X, dimB, polys, s))) return rc;                                       // :61
+    }
+    for (unsigned r = 0; r < nrot; ++r) {
+      StageRange stage("gpq_he_rot_hoisted: one rotation (permuted key switch + tail)");
+      const unsigned g = (unsigned)(rot_power(rots[r]) & mask2n);
+      if ((rc = gpq_poly_rot(c, d0, c0 + k0 * bigpoly, W, rots[r], polys, stream))) return rc;            // :108 (c1's is in the index map)
+      {
+        ScaledInverse scaled(c, tabsP);
+        if ((rc = gpq_keyswitch_rotated(c, chat, chat + pb, X, rk0[r], rk1[r], dimB, polys, g, wsK, s))) return rc;   // :61-65
+      }
+      const size_t o = ((size_t)r * batch + k0) * bigpoly;
+      if ((rc = relin_tail(c, Two<uint64_t>{out_c0 + o, out_c1 + o, polys}, chat, Two<const uint64_t>{d0, nullptr, polys},
+                           W, dimP, dimB, logql, 2 * polys, wsTail, s, tail_mode))) return rc;                // :68-75
+    }
+  }
+  return launched("gpq_he_rot_hoisted");
+}
+
+// ---------------------------------------------------------------------------
+// he_gemv, src/he-algo.c:47-93, on big slabs: baby steps j < n1 as ONE hoisted call (rk[j]), per giant step i the products with the
+// diagonals diag[i n1 + j] (one gpq_he_mulpt over n1 x batch ciphertexts), their sum, he_rot by i n1 (rk[i n1]), the sum of the giant
+// steps and he_rs.  With q_l = 2^logql every he_add (mpi_addm + mpi_smod, src/he-add.c:41-44) is the wrapping two's-complement sum of
+// the big slabs followed by one centring: the sum is exact modulo 2^(64 W) and hence modulo q_l, and centring is a function of the
+// residue modulo q_l.  So the sums run unreduced and are centred once -- before he_rot (whose rns_decompose reads the signed value)
+// and before he_rs (whose rounding division does).
+// ---------------------------------------------------------------------------
+namespace {
+void gemv_steps(unsigned slots, unsigned *n1, unsigned *n2) {  // :51-54 (sqrt of an unsigned, truncated)
+  unsigned a = (unsigned)std::sqrt((double)slots);
+  if (slots != a * a) a = (unsigned)std::sqrt((double)(2 * slots));
+  *n1 = a;
+  *n2 = slots / a;
+}
+struct GemvPlan { size_t r, mpt, p, g, ws, total; };
+void gemv_plan(gpq_ctx *c, unsigned W, unsigned slots, unsigned dimB, unsigned dimP, unsigned dimpt, unsigned batch, GemvPlan *g) {
+  unsigned n1, n2;
+  gemv_steps(slots, &n1, &n2);
+  const size_t big = (size_t)batch * W * c->n * 8;
+  g->r = 2 * align64(n1 * big);                       // baby rotations, c0 | c1
+  g->mpt = align64(n1 * big);                         // the diagonals of one giant step, one per ciphertext
+  g->p = 2 * align64(n1 * big);                       // their products
+  g->g = 2 * align64(big);                            // one giant rotation
+  const size_t wn = gpq_he_rot_hoisted_workspace_bytes(c, W, dimB, dimP, n1, batch), w1 = gpq_he_rot_hoisted_workspace_bytes(c, W, dimB, dimP, 1, batch),
+               wm = gpq_he_mulpt_workspace_bytes(c, dimpt, n1 * batch);
+  if (!wn || !w1) { g->ws = g->total = 0; return; }       // either rotation plan failed (its message is in gpq_last_error)
+  const size_t ws = wn > w1 ? wn : w1;
+  g->ws = align64(ws > wm ? ws : wm);
+  g->total = g->r + g->mpt + g->p + g->g + g->ws;
+}
+}  // namespace
+
+extern "C" size_t gpq_he_gemv_workspace_bytes(gpq_ctx *c, unsigned W, unsigned slots, unsigned dimB, unsigned dimP, unsigned dimpt, unsigned batch) {
+  if (!c || !slots || !batch || !W) return 0;
+  GemvPlan g;
+  gemv_plan(c, W, slots, dimB, dimP, dimpt, batch, &g);
+  return g.total;
+}
+
+extern "C" int gpq_he_gemv(gpq_ctx *c, uint64_t *out_c0, uint64_t *out_c1, const uint64_t *c0, const uint64_t *c1, const uint64_t *diag,
+                           const uint64_t *const *rk0, const uint64_t *const *rk1, unsigned slots, unsigned W, unsigned logql,
+                           unsigned logDelta, unsigned dimB, unsigned dimP, unsigned dimpt, unsigned batch, void *workspace, void *stream) {
+  int rc = check(c, dimB, batch, "gpq_he_gemv");
+  if (rc || (rc = check(c, dimpt, batch, "gpq_he_gemv"))) return rc;
+  if (!out_c0 || !out_c1 || !c0 || !c1 || !diag || !rk0 || !rk1 || !slots || !workspace || !logql || logDelta >= logql || W < (logql + 63) / 64)
+    return gpq_fail(GPQ_ERR_INVALID, "gpq_he_gemv: bad arguments");
+  unsigned n1, n2;
+  gemv_steps(slots, &n1, &n2);
+  hipStream_t s = (hipStream_t)stream;
+  const size_t bigpoly = (size_t)W * c->n, big = batch * bigpoly;
+  GemvPlan gp;
+  gemv_plan(c, W, slots, dimB, dimP, dimpt, batch, &gp);
+  if (!gp.total) return gpq_fail(GPQ_ERR_INVALID, "gpq_he_gemv: unsupported shape");
+  char *w = (char *)workspace;
+  uint64_t *R0 = (uint64_t *)w, *R1 = (uint64_t *)(w + gp.r / 2); w += gp.r;
+  uint64_t *M = (uint64_t *)w; w += gp.mpt;
+  uint64_t *P0 = (uint64_t *)w, *P1 = (uint64_t *)(w + gp.p / 2); w += gp.p;
+  uint64_t *G0 = (uint64_t *)w, *G1 = (uint64_t *)(w + gp.g / 2); w += gp.g;
+  void *ws = w;
+  std::vector<unsigned> baby(n1);
+  for (unsigned j = 0; j < n1; ++j) baby[j] = j;
+  if ((rc = gpq_he_rot_hoisted(c, R0, R1, c0, c1, baby.data(), rk0, rk1, n1, W, logql, dimB, dimP, batch, ws, stream))) return rc;   // :63-68
+  for (unsigned i = 0; i < n2; ++i) {
+    for (unsigned j = 0; j < n1; ++j)                                                                                 // :70-72
+      for (unsigned k = 0; k < batch; ++k)
+        HIP_TRY(hipMemcpyAsync(M + ((size_t)j * batch + k) * bigpoly, diag + ((size_t)i * n1 + j) * bigpoly, bigpoly * 8, hipMemcpyDeviceToDevice, s));
+    if ((rc = gpq_he_mulpt(c, P0, P1, R0, R1, M, W, logql, dimpt, n1 * batch, ws, stream))) return rc;                 // :74
+    for (unsigned j = 1; j < n1; ++j)                                                                                 // :75-78
+      if ((rc = gpq_big_addsub(c, P0, P0, P0 + j * big, W, batch, 0, stream)) || (rc = gpq_big_addsub(c, P1, P1, P1 + j * big, W, batch, 0, stream))) return rc;
+    if ((rc = gpq_he_rs(c, P0, P1, W, 0, logql, batch, stream))) return rc;                                            // centred: he_rot decomposes it
+    const unsigned shift = i * n1;
+    if (!rk0[shift] || !rk1[shift]) return gpq_fail(GPQ_ERR_INVALID, "gpq_he_gemv: key %u is NULL", shift);
+    uint64_t *g0 = i ? G0 : out_c0, *g1 = i ? G1 : out_c1;                                                              // :80-84
+    if ((rc = gpq_he_rot_hoisted(c, g0, g1, P0, P1, &shift, rk0 + shift, rk1 + shift, 1, W, logql, dimB, dimP, batch, ws, stream))) return rc;
+    if (i && ((rc = gpq_big_addsub(c, out_c0, out_c0, G0, W, batch, 0, stream)) || (rc = gpq_big_addsub(c, out_c1, out_c1, G1, W, batch, 0, stream)))) return rc;
+  }
+  if ((rc = gpq_he_rs(c, out_c0, out_c1, W, 0, logql, batch, stream))) return rc;                                      // the adds' mpi_smod
+  if (logDelta && (rc = gpq_he_rs(c, out_c0, out_c1, W, logDelta, logql - logDelta, batch, stream))) return rc;         // :87, src/he-rescale.c:33-54
+  return launched("gpq_he_gemv");
+}
+
 // Tail of he_relin / he_swk alone (src/he-mult.c:67-77): out = smod(rdiv(poly_rns2mpi(chat, P*q_l), P) + d, q_l).
 extern "C" size_t gpq_relin_tail_workspace_bytes(gpq_ctx *c, unsigned W, unsigned dimB, unsigned dimP, unsigned batch) {
   TailPlan tp;

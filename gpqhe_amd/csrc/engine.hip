@@ -447,7 +447,8 @@ namespace {
 static const char *const kKernelNames[GPQ_K_COUNT] = {"strided_fwd", "strided_inv", "contig_fwd", "contig_inv",
                                                       "tensor_mid", "keyswitch_mid", "pointwise", "small_ntt", "reference_redo",
                                                       "bridge_decompose", "bridge_reconstruct", "bridge_relin_front", "bridge_relin_tail_fused", "bridge_exact_paths", "bridge_rescale",
-                                                      "bridge_relin_tail_direct", "bridge_crt_decompose", "bridge_tail_stream"};
+                                                      "bridge_relin_tail_direct", "bridge_crt_decompose", "bridge_tail_stream",
+                                                      "keyswitch_rot_mid", "automorphism_gather"};
 
 int check_shape(const gpq_ctx *c, unsigned dim, unsigned batch, const char *who) {
   if (!c) return gpq_fail(GPQ_ERR_INVALID, "%s: null context", who);
@@ -1004,6 +1005,83 @@ extern "C" int gpq_keyswitch(gpq_ctx *c, uint64_t *c0, uint64_t *c1, const uint6
   if ((rc = gpq_peer_join(c, s, lane))) return rc;
   c->last_lanes = lanes_used;   // (after the nested entry points of the groups, which record their own)
   return after_launch("gpq_keyswitch");
+}
+
+// ---------------------------------------------------------------------------
+// hoisted rotations: sigma on the host, the shared forward transform, one key switch per rotation (ntt_kernels.hpp: keyswitch_rot_mid8x2)
+// ---------------------------------------------------------------------------
+extern "C" int gpq_automorphism_index(unsigned logn, uint64_t g, uint32_t *idx) {
+  if (logn < 1 || logn > 17 || !(g & 1) || !idx) return gpq_fail(GPQ_ERR_INVALID, "gpq_automorphism_index: logn in [1, 17], odd g, idx");
+  const uint64_t n = 1ull << logn, m = 2 * n, gm = g & (m - 1);
+  auto brv = [logn](uint64_t x) { uint64_t r = 0; for (unsigned b = 0; b < logn; ++b) r |= ((x >> b) & 1) << (logn - 1 - b); return r; };
+  for (uint64_t j = 0; j < n; ++j) idx[j] = (uint32_t)brv((((2 * brv(j) + 1) * gm) & (m - 1)) >> 1);
+  return GPQ_OK;
+}
+
+int gpq_hoist_forward(gpq_ctx *c, uint64_t *slab, unsigned dim, unsigned polys, hipStream_t s) {
+  PassArgs a = make_args(c, dim, 1, nt_for(c, polys, dim, 1));
+  a.src[0] = a.dst[0] = slab;
+  int rc;
+  if (!two_pass(c)) {
+    for (unsigned k0 = 0; k0 < polys; k0 += kMaxPolysPerLaunch) {
+      const unsigned cnt = polys - k0 < kMaxPolysPerLaunch ? polys - k0 : kMaxPolysPerLaunch;
+      a.src[0] = a.dst[0] = slab + (size_t)k0 * ((size_t)dim << c->logn);
+      if ((rc = launch_small<false>(c, a, dim, cnt, s))) return rc;
+    }
+    return after_launch("gpq_he_rot_hoisted: forward transform");
+  }
+  if ((rc = launch_strided<false>(c, a, dim, polys, s))) return rc;
+  if ((rc = launch_contig<false>(c, a, dim, polys, s))) return rc;
+  return after_launch("gpq_he_rot_hoisted: forward transform");
+}
+
+int gpq_keyswitch_rotated(gpq_ctx *c, uint64_t *c0, uint64_t *c1, const uint64_t *X, const uint64_t *evk0, const uint64_t *evk1,
+                          unsigned dim, unsigned polys, unsigned g, void *workspace, hipStream_t s) {
+  const size_t poly = (size_t)dim << c->logn;
+  int rc;
+  if (!two_pass(c)) {
+    uint64_t *ws = (uint64_t *)workspace;
+    const size_t rows = (size_t)polys * dim;
+    for (size_t r0 = 0; r0 < rows; r0 += 65535) {
+      const unsigned cnt = rows - r0 < 65535 ? (unsigned)(rows - r0) : 65535u;
+      ProfScope prof(c, GPQ_K_AUTOMORPHISM_GATHER, s);
+      hipLaunchKernelGGL(automorphism_gather, dim3((c->n + 255) / 256, cnt), dim3(256), 0, s, X + (r0 << c->logn), ws + (r0 << c->logn), c->logn, g);
+    }
+    for (unsigned k = 0; k < polys; ++k) {   // the key is shared by the batch
+      if ((rc = gpq_rns_mul(c, c0 + k * poly, ws + k * poly, evk0, dim, 1, s))) return rc;
+      if ((rc = gpq_rns_mul(c, c1 + k * poly, ws + k * poly, evk1, dim, 1, s))) return rc;
+    }
+    if ((rc = gpq_invntt(c, c0, dim, polys, s))) return rc;
+    return gpq_invntt(c, c1, dim, polys, s);
+  }
+  const unsigned nt = nt_for(c, polys, dim, 3);
+  KeyswitchArgs m;
+  m.p = make_args(c, dim, 1, nt);
+  m.p.src[0] = X; m.p.dst[0] = c0; m.p.dst[1] = c1;
+  m.evk0 = evk0; m.evk1 = evk1;
+  if ((rc = for_limb_ranges<true>(c, m.p, dim, &m.evk0, &m.evk1, [&](auto tag, const PassArgs &a, unsigned nl) {
+        using TW = decltype(tag);
+        KeyswitchArgs ka{a, m.evk0, m.evk1};
+        ProfScope prof(c, GPQ_K_KEYSWITCH_ROT_MID, s);
+        const dim3 block(CONTIG_WAVES * 64);
+        with_nt(a.nt, [&](auto ntv) {
+          constexpr bool NT = decltype(ntv)::value;
+          if (polys / 2) {
+            if (c->low9) hipLaunchKernelGGL((keyswitch_rot_mid8x2<TW, 9, true, NT>), dim3(c->n >> 11, polys / 2, nl), block, 0, s, ka, 0u, g);
+            else hipLaunchKernelGGL((keyswitch_rot_mid8x2<TW, 8, true, NT>), dim3(c->n >> 11, polys / 2, nl), block, 0, s, ka, 0u, g);
+          }
+          if (polys & 1) {
+            if (c->low9) hipLaunchKernelGGL((keyswitch_rot_mid8x2<TW, 9, false, NT>), dim3(c->n >> 11, 1, nl), block, 0, s, ka, polys - 1, g);
+            else hipLaunchKernelGGL((keyswitch_rot_mid8x2<TW, 8, false, NT>), dim3(c->n >> 11, 1, nl), block, 0, s, ka, polys - 1, g);
+          }
+        });
+        return (int)GPQ_OK;
+      }))) return rc;
+  PassArgs b = make_args(c, dim, 2, nt);
+  if (c->inv_tabs_override) b.tabs = c->inv_tabs_override;
+  b.src[0] = b.dst[0] = c0; b.src[1] = b.dst[1] = c1;
+  if ((rc = launch_strided<true>(c, b, dim, polys, s))) return rc;
+  return after_launch("gpq_he_rot_hoisted: key switch");
 }
 
 // Which butterflies a limb runs is decided by its c = p - 2^59 (modarith.hpp): the first `wide` limbs the wide-split ones, the

@@ -16,7 +16,10 @@ enum { GPQ_K_STRIDED_FWD = 0, GPQ_K_STRIDED_INV, GPQ_K_CONTIG_FWD, GPQ_K_CONTIG_
        // masked kernels (bridge_reconstruct, bridge_roundfix, bridge_addround, bridge_exactdiv), he_rs
        GPQ_K_DECOMPOSE, GPQ_K_RECONSTRUCT, GPQ_K_RELIN_FRONT, GPQ_K_RELIN_TAIL_FUSED, GPQ_K_BRIDGE_EXACT, GPQ_K_RESCALE, GPQ_K_RELIN_TAIL_DIRECT,
        // bridge_stream.hpp: CRT(d2hat) -> rns_decompose in one kernel; the one-product tail with its addend's CRT in the same kernel
-       GPQ_K_CRT_DECOMPOSE, GPQ_K_TAIL_STREAM, GPQ_K_COUNT };
+       GPQ_K_CRT_DECOMPOSE, GPQ_K_TAIL_STREAM,
+       // gpq_he_rot_hoisted: the key switch of one rotation from the shared NTT-domain input (keyswitch_rot_mid8x2, two-pass rings); the plain
+       // permutation of that input on single-pass rings (automorphism_gather)
+       GPQ_K_KEYSWITCH_ROT_MID, GPQ_K_AUTOMORPHISM_GATHER, GPQ_K_COUNT };
 
 // Constant matrix of the matrix-core CRT fast path for one basis and result width WL (bridge_mfma.hpp)
 struct gpq_recon_mfma {
@@ -189,6 +192,13 @@ int gpq_fail(int code, const char *fmt, ...);
 // cache) is the parent's, borrowed; its own are only the mutable words (zero flags, redo flags, wave words, scratch).  Default settings, no peer of
 // its own; must be destroyed before the parent (gpq_ctx_destroy does).
 int gpq_ctx_clone(const gpq_ctx *c, gpq_ctx **out);
+// Hoisted rotations (engine.hip; bridge.hip's gpq_he_rot_hoisted): the complete forward transform of `polys` polynomials of `dim` limbs
+// in place (slab[k][d][i], canonical in [0, p], no zero watch: only products with a key read it), and the key switch of one rotation
+// from it: c0 = invntt(X o sigma_g (*) evk0), c1 = invntt(X o sigma_g (*) evk1), with the inverse tables the context's ScaledInverse
+// selects.  `workspace`: gpq_keyswitch_workspace_bytes(c, dim, polys) (single-pass rings only).
+int gpq_hoist_forward(gpq_ctx *c, uint64_t *slab, unsigned dim, unsigned polys, hipStream_t s);
+int gpq_keyswitch_rotated(gpq_ctx *c, uint64_t *c0, uint64_t *c1, const uint64_t *X, const uint64_t *evk0, const uint64_t *evk1,
+                          unsigned dim, unsigned polys, unsigned g, void *workspace, hipStream_t s);
 // hipMalloc of a read-only table, accounted in the context's table cache (gpq_debug_table_bytes)
 inline hipError_t gpq_table_malloc(gpq_ctx *c, void **p, size_t bytes) {
   hipError_t e = hipMalloc(p, bytes);

@@ -26,6 +26,7 @@
 #include <functional>
 #include <map>
 #include <mutex>
+#include <set>
 #include <thread>
 #include <vector>
 
@@ -34,6 +35,8 @@ extern "C" struct he_ctx hectx __attribute__((weak));       // src/precomp.c:47
 // the reference's samplers (src/sample.c; externs at src/he-kem.c:33-34): key generation draws from them in the reference's order
 extern "C" void sample_error(poly_mpi_t *r) __attribute__((weak));
 extern "C" void sample_uniform(poly_mpi_t *r, const gpq_MPI q) __attribute__((weak));
+// the reference's encoder (src/he-encode.c:107-111): he_gemv / he_sum / he_idx encode their diagonals with the host program's own
+extern "C" void he_ecd(struct he_pt *pt, const _Complex double *m) __attribute__((weak));
 
 #include "mpi_convert.hpp"
 
@@ -425,6 +428,7 @@ void he_mulpt(struct he_ct *dest, const struct he_ct *src, const struct he_pt *p
 
 #include "shim_additive.hpp"
 #include "shim_keygen.hpp"
+#include "shim_algo.hpp"
 
 }  // extern "C"
 

@@ -957,6 +957,110 @@ __global__ __launch_bounds__(CONTIG_WAVES * 64, 3) void keyswitch_mid8x2(Keyswit
   }
 }
 
+// ---------------------------------------------------------------------------
+// Hoisted rotations (gpq_he_rot_hoisted).  With g = 5^rot mod 2n (g = 2n - 1 for poly_conj) and brv the logn-bit reversal,
+//   NTT(poly_rot(a, rot))[j] = NTT(a)[sigma(j)],   2 brv(sigma(j)) + 1 = (2 brv(j) + 1) g  (mod 2n)
+// in the forward output order (gpq_automorphism_index is the same map on the host).  The high bits of sigma(j) depend only on the high bits
+// of j, so an aligned block of 2^k outputs reads one aligned block of 2^k inputs: a tile of the low stages is a row of one source tile,
+// permuted inside.  (2n divides 2^32, so the product wraps harmlessly in 32 bits.)
+__device__ __forceinline__ unsigned automorphism_src(unsigned j, unsigned logn, unsigned g) {
+  const unsigned mask2n = (2u << logn) - 1;
+  const unsigned e = (((__brev(j) >> (32 - logn)) << 1) | 1u) * g & mask2n;
+  return __brev(e >> 1) >> (32 - logn);
+}
+
+// keyswitch_mid8x2 for a rotated input that is already in the NTT domain: src[0] = the COMPLETE forward transform of the unrotated
+// decomposed c1 (shared by every rotation of a call); each wave reads the 512 words of its source tile (coalesced, H layout) into its LDS
+// region, takes its L-layout words through sigma from there, multiplies by the key and runs the inverse low stages.  dst[0..1] as in
+// keyswitch_mid8x2; the strided inverse pass follows.  Same pairing of polynomials, limb classes and cache policy.
+template <typename TW, int LOW, bool TWO = true, bool NT = false>
+__global__ __launch_bounds__(CONTIG_WAVES * 64, 3) void keyswitch_rot_mid8x2(KeyswitchArgs ka, unsigned first, unsigned g) {
+  using TT = TwTraits<TW>;
+  using L8 = Lane8N<LOW, NT>;
+  __shared__ uint64_t lds[CONTIG_WAVES * LANE8_LDS_PER_WAVE];
+  const PassArgs &a = ka.p;
+  L8 ln(lds + (threadIdx.x >> 6) * LANE8_LDS_PER_WAVE);
+  const unsigned wave0 = (blockIdx.x * CONTIG_WAVES + (threadIdx.x >> 6)) << 9;
+  const unsigned limb = a.limb0 + blockIdx.z;
+  const PrimeK k = a.tabs[limb].k;
+  const size_t toff = (size_t)limb << a.logn;
+  const TW *__restrict__ wi = TT::table(a, true) + toff;
+  const unsigned p0 = first + 2 * blockIdx.y;
+  constexpr bool two = TWO;
+  const size_t off0 = (size_t)p0 * a.poly_stride + ((size_t)blockIdx.z << a.logn) + wave0;
+  const size_t off1 = two ? off0 + a.poly_stride : off0;
+  const size_t koff = ((size_t)blockIdx.z << a.logn) + wave0;
+  const unsigned src0 = automorphism_src(wave0, a.logn, g) & ~511u;    // the source tile (one per wave, see above)
+  const size_t soff0 = off0 - wave0 + src0, soff1 = off1 - wave0 + src0;
+  unsigned sl[8];                                                       // in-tile source of the lane's L-layout words
+#pragma unroll
+  for (int e = 0; e < 8; ++e) sl[e] = automorphism_src(wave0 + ln.lk + e, a.logn, g) & 511u;
+  auto gather = [&](uint64_t (&x)[8], size_t soff) {
+    ln.load_h(x, a.src[0] + soff);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) ln.lds[L8::pad2(ln.hk + (e << L8::JB))] = x[e];
+    wave_lds_sync();
+#pragma unroll
+    for (int e = 0; e < 8; ++e) x[e] = ln.lds[L8::pad2(sl[e])];
+    wave_lds_sync();
+  };
+  uint64_t x0[8], x1[8], e0[8], e1[8];
+  Tw8<TW, LOW> tw;
+  gather(x0, soff0);
+  if constexpr (two) gather(x1, soff1);
+  ln.load_l(e0, ka.evk0 + koff);
+  ln.load_l(e1, ka.evk1 + koff);
+  tw.load_l(ln, wave0, a.logn, wi);
+  uint64_t y0[8], y1[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const uint64_t u0 = TT::right(x0[e], k);          // canonical words: inside every class's right-operand range
+    x0[e] = TT::inv_from4(mulmod_lazy(u0, e0[e], k), k);
+    y0[e] = TT::inv_from4(mulmod_lazy(u0, e1[e], k), k);
+  }
+  if constexpr (two) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const uint64_t u1 = TT::right(x1[e], k);
+      x1[e] = TT::inv_from4(mulmod_lazy(u1, e0[e], k), k);
+      y1[e] = TT::inv_from4(mulmod_lazy(u1, e1[e], k), k);
+    }
+  }
+  L8::gs_l(x0, tw.u, k); ln.l_to_m(x0);
+  L8::gs_l(y0, tw.u, k); ln.l_to_m(y0);
+  if constexpr (two) {
+    L8::gs_l(x1, tw.u, k); ln.l_to_m(x1);
+    L8::gs_l(y1, tw.u, k); ln.l_to_m(y1);
+  }
+  tw.load_m(ln, wave0, a.logn, wi);
+  L8::gs_hm(x0, tw.t, k); ln.m_to_h(x0);
+  L8::gs_hm(y0, tw.t, k); ln.m_to_h(y0);
+  if constexpr (two) {
+    L8::gs_hm(x1, tw.t, k); ln.m_to_h(x1);
+    L8::gs_hm(y1, tw.t, k); ln.m_to_h(y1);
+  }
+  tw.load_h(ln, wave0, a.logn, wi);
+  L8::gs_hm(x0, tw.t, k);
+  ln.store_h(a.dst[0] + off0, x0);
+  L8::gs_hm(y0, tw.t, k);
+  ln.store_h(a.dst[1] + off0, y0);
+  if constexpr (two) {
+    L8::gs_hm(x1, tw.t, k);
+    ln.store_h(a.dst[0] + off1, x1);
+    L8::gs_hm(y1, tw.t, k);
+    ln.store_h(a.dst[1] + off1, y1);
+  }
+}
+
+// The same permutation on single-pass rings (n <= 2^12), as a plain gather: dst[row][j] = src[row][sigma(j)] over rows of n words
+// (polynomial x limb), one thread per word.  gpq_rns_mul and gpq_invntt follow.
+__global__ __launch_bounds__(256) void automorphism_gather(const uint64_t *__restrict__ src, uint64_t *__restrict__ dst, unsigned logn, unsigned g) {
+  const unsigned j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= (1u << logn)) return;
+  const size_t row = (size_t)blockIdx.y << logn;
+  dst[row + j] = src[row + automorphism_src(j, logn, g)];
+}
+
 // contig_pass in the 8-per-lane geometry (n = 2^17): CONTIG8_POLYS polynomials of the same limb and tile share each twiddle group.
 constexpr int CONTIG8_POLYS = 2;
 template <bool INV, typename TW, int LOW, bool NT = false>

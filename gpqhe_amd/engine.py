@@ -344,6 +344,35 @@ class PolyContext:
         _native.check(self.lib.gpq_he_genswk(self.h, self._ptr(evk0), self._ptr(evk1), self._ptr(p1), self._ptr(sk), self._ptr(e), self._ptr(sp), W, dimP, logqL, dimevk,
                                              self._ptr(ws), self._stream()), "gpq_he_genswk")
 
+    def _key_ptrs(self, keys):
+        """host array of device pointers (None stays NULL)"""
+        return (C.c_void_p * len(keys))(*[None if k is None else self._ptr(k).value for k in keys])
+
+    def he_rot_hoisted(self, out_c0, out_c1, c0, c1, rots, rk0, rk1, W, logql, dimB, dimP):
+        """he_rot (src/he-automorphism.c:101-115) of the batch by every rots[r] with key (rk0[r], rk1[r]); c1 is decomposed and transformed
+        once.  Outputs rotation-major: len(rots) x batch big slabs each."""
+        torch = _torch()
+        batch, nrot = c0.numel() // (W * self.n), len(rots)
+        nbytes = self.lib.gpq_he_rot_hoisted_workspace_bytes(self.h, W, dimB, dimP, nrot, batch)
+        ws = torch.empty(nbytes // 8 + 8, dtype=torch.int64, device=self._dev)
+        r = (C.c_uint * max(nrot, 1))(*rots)
+        _native.check(self.lib.gpq_he_rot_hoisted(self.h, self._ptr(out_c0), self._ptr(out_c1), self._ptr(c0), self._ptr(c1), r, self._key_ptrs(rk0),
+                                                  self._key_ptrs(rk1), nrot, W, logql, dimB, dimP, batch, self._ptr(ws), self._stream()), "gpq_he_rot_hoisted")
+        return ws
+
+    def he_gemv(self, out_c0, out_c1, c0, c1, diag, rk0, rk1, slots, W, logql, logDelta, dimB, dimP, dimpt):
+        """he_gemv (src/he-algo.c:47-93) + its he_rs on big slabs: diag = slots plaintext big slabs (index i*n1 + j), rk0 / rk1 = per-rotation
+        key slabs (lists indexed by the rotation; unused entries may be None)."""
+        torch = _torch()
+        batch = c0.numel() // (W * self.n)
+        nbytes = self.lib.gpq_he_gemv_workspace_bytes(self.h, W, slots, dimB, dimP, dimpt, batch)
+        if not nbytes:
+            raise _native.GpqError("gpq_he_gemv_workspace_bytes: " + self.lib.gpq_last_error().decode())
+        ws = torch.empty(nbytes // 8 + 8, dtype=torch.int64, device=self._dev)
+        _native.check(self.lib.gpq_he_gemv(self.h, self._ptr(out_c0), self._ptr(out_c1), self._ptr(c0), self._ptr(c1), self._ptr(diag), self._key_ptrs(rk0),
+                                           self._key_ptrs(rk1), slots, W, logql, logDelta, dimB, dimP, dimpt, batch, self._ptr(ws), self._stream()), "gpq_he_gemv")
+        return ws
+
     def poly_rot(self, r, a, W, rot):
         _native.check(self.lib.gpq_poly_rot(self.h, self._ptr(r), self._ptr(a), W, rot, a.numel() // (W * self.n), self._stream()), "gpq_poly_rot")
         return r
@@ -432,6 +461,23 @@ class PolyContext:
         _native.check(self.lib.gpq_keyswitch(self.h, self._ptr(c0), self._ptr(c1), self._ptr(x), self._ptr(evk0), self._ptr(evk1),
                                              dim, batch, self._ptr(ws), self._stream()), "gpq_keyswitch")
         return c0, c1
+
+
+def automorphism_index(logn, g):
+    """sigma of X -> X^g in the NTT domain (include/gpqhe_hip.h: gpq_automorphism_index): NTT(a o X^g)[j] = NTT(a)[idx[j]].  No device."""
+    lib = _native.load()
+    idx = np.empty(1 << logn, dtype=np.uint32)
+    _native.check(lib.gpq_automorphism_index(logn, g, idx.ctypes.data_as(C.c_void_p)), "gpq_automorphism_index")
+    return idx
+
+
+def gemv_steps(slots):
+    """(n1, n2) of he_gemv, src/he-algo.c:51-54"""
+    import math
+    n1 = int(math.sqrt(slots))
+    if slots != n1 * n1:
+        n1 = int(math.sqrt(2 * slots))
+    return n1, slots // n1
 
 
 def ints_to_big(values, W):

@@ -353,6 +353,30 @@ int gpq_he_mulpt(gpq_ctx *ctx, uint64_t *out_c0, uint64_t *out_c1, const uint64_
 int gpq_poly_rot(gpq_ctx *ctx, uint64_t *r, const uint64_t *a, unsigned W, unsigned rot, unsigned batch, void *stream);
 int gpq_poly_conj(gpq_ctx *ctx, uint64_t *r, const uint64_t *a, unsigned W, unsigned batch, void *stream);
 
+/* ---- hoisted rotations and he_gemv --------------------------------------------------------------------------------------------
+ * sigma of the automorphism X -> X^g (g odd) in the NTT domain, in the reference's forward output order (bit-reversed):
+ *   NTT(poly_rot(a, rot))[j] = NTT(a)[idx[j]] (mod p) with g = 5^rot mod 2n (g = 2n - 1 for poly_conj), where
+ *   2 brv(idx[j]) + 1 = (2 brv(j) + 1) g (mod 2n), brv = logn-bit reversal.  Host only (no device); idx holds n = 2^logn words.
+ *   GPQ_ERR_INVALID for an even g or logn outside [1, 17]. */
+int gpq_automorphism_index(unsigned logn, uint64_t g, uint32_t *idx);
+/* he_rot (src/he-automorphism.c:101-115) of the same `batch` ciphertexts by rots[0..nrot): for every r the words of gpq_poly_rot on c0 and
+ * c1 followed by gpq_he_swk with the key rk0[r] / rk1[r] (host arrays of device pointers, NTT-domain keys of >= dimB limbs), q_l = 2^logql.
+ * c1 is decomposed and transformed once per launch group and every rotation permutes that transform ("Hoisted rotations").
+ * Outputs are rotation-major: ciphertext k of rotation r at (r * batch + k) * W * n.  Any rot (0, repeats, >= slots); nrot = 1 runs
+ * poly_rot + gpq_he_swk.  GPQ_ERR_INVALID when an output overlaps the other output or an input. */
+size_t gpq_he_rot_hoisted_workspace_bytes(gpq_ctx *ctx, unsigned W, unsigned dimB, unsigned dimP, unsigned nrot, unsigned batch);
+int gpq_he_rot_hoisted(gpq_ctx *ctx, uint64_t *out_c0, uint64_t *out_c1, const uint64_t *c0, const uint64_t *c1,
+                       const unsigned *rots, const uint64_t *const *rk0, const uint64_t *const *rk1, unsigned nrot,
+                       unsigned W, unsigned logql, unsigned dimB, unsigned dimP, unsigned batch, void *workspace, void *stream);
+/* he_gemv, src/he-algo.c:47-93, followed by its he_rs (Delta = 2^logDelta; logDelta = 0: no rescale): n1, n2 as :51-54; diag[i n1 + j]
+ * = the plaintext big slab (W words) of he_ecd(zrotdiag(A, i n1 + j, -i n1)), shared by the batch; rk0 / rk1 indexed by the rotation
+ * (rk[j] for the baby steps, rk[i n1] for the giant ones); dimpt = he_mulpt's limb count (src/he-mult.c:168).  The output is centred
+ * mod 2^(logql - logDelta); the l / nu / B bookkeeping stays with the caller.  out may alias c0 / c1. */
+size_t gpq_he_gemv_workspace_bytes(gpq_ctx *ctx, unsigned W, unsigned slots, unsigned dimB, unsigned dimP, unsigned dimpt, unsigned batch);
+int gpq_he_gemv(gpq_ctx *ctx, uint64_t *out_c0, uint64_t *out_c1, const uint64_t *c0, const uint64_t *c1, const uint64_t *diag,
+                const uint64_t *const *rk0, const uint64_t *const *rk1, unsigned slots, unsigned W, unsigned logql,
+                unsigned logDelta, unsigned dimB, unsigned dimP, unsigned dimpt, unsigned batch, void *workspace, void *stream);
+
 /* ---- general moduli: any q_l (little-endian words ql_words[0..Lq)) and any Delta (uint64_t, as hectx_init takes it,
  * src/gpqhe.h:100).  Same reference semantics, through the multiword Barrett kernel: slow-path quality, meant for parameter
  * sets outside the powers of two that the fast entry points above cover. */

@@ -144,6 +144,11 @@ void he_copy_ct(struct he_ct *dest, const struct he_ct *src);
 void he_dec(struct he_pt *pt, const struct he_ct *ct, const poly_mpi_t *sk);
 void he_conj(he_ct_t *ct, const he_evk_t *ck);                                          /* src/gpqhe.h:151  */
 void he_rot(he_ct_t *ct, const int rot, const he_evk_t *rk);                            /* src/gpqhe.h:152  */
+/* src/he-algo.c:47-113: the baby steps as one hoisted call, the whole body on the device (gpq_he_gemv) for power-of-two q_l, q_(l-1); the
+ * reference's loop over this library's per-call functions otherwise.  The diagonals are encoded by the host program's he_ecd (weak reference). */
+void he_gemv(he_ct_t *ct_dest, const _Complex double *A, const he_ct_t *ct, const he_evk_t *rk);   /* src/gpqhe.h:155 */
+void he_sum(he_ct_t *ct_sum, const he_ct_t *ct, const he_evk_t *rk);                               /* src/gpqhe.h:156 */
+void he_idx(he_ct_t *ct_idx, const he_ct_t *ct, const unsigned int idx, const he_evk_t *rk);       /* src/gpqhe.h:157 */
 /* Key generation, src/he-kem.c:120-170 (decl src/gpqhe.h:131-133).  The randomness comes from the host program's own
  * sample_error / sample_uniform (src/sample.c), called in the reference's order; everything else runs on the device. */
 void he_genrlk(he_evk_t *rlk, const poly_mpi_t *sk);
