@@ -128,6 +128,16 @@ SIGNATURES = {
     "gpq_he_rot_hoisted": (C.c_int, [vp] * 8 + [C.c_uint] * 6 + [vp, vp]),
     "gpq_he_gemv_workspace_bytes": (C.c_size_t, [vp] + [C.c_uint] * 6),
     "gpq_he_gemv": (C.c_int, [vp] * 8 + [C.c_uint] * 8 + [vp, vp]),
+    "gpq_gemv_acc_dim": (C.c_uint, [C.c_uint] * 4),
+    "gpq_gemv_plan_create": (C.c_int, [vp, C.POINTER(vp), vp, C.c_uint, C.c_uint, C.c_uint, C.c_uint, vp]),
+    "gpq_gemv_plan_destroy": (None, [vp]),
+    "gpq_gemv_plan_info": (C.c_int, [vp, C.POINTER(C.c_uint), C.POINTER(C.c_size_t), C.POINTER(C.c_uint), C.POINTER(C.c_int)]),
+    "gpq_gemv_plan_rotations": (C.c_int, [vp, vp]),
+    "gpq_shim_gemv_plan_cache": (None, [C.c_uint]),
+    "gpq_gemv_inner_workspace_bytes": (C.c_size_t, [vp, vp, C.c_uint]),
+    "gpq_gemv_inner": (C.c_int, [vp] * 6 + [C.c_uint] * 3 + [vp, vp]),
+    "gpq_he_gemv_planned_workspace_bytes": (C.c_size_t, [vp, vp] + [C.c_uint] * 4),
+    "gpq_he_gemv_planned": (C.c_int, [vp] * 8 + [C.c_uint] * 5 + [vp, vp]),
     "gpq_profile_enable": (C.c_int, [vp, C.c_int]),
     "gpq_profile_kernels": (C.c_int, []),
     "gpq_profile_kernel_name": (C.c_char_p, [C.c_int]),

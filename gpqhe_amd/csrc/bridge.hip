@@ -10,6 +10,8 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
+#include <new>
 
 using namespace gpq;
 
@@ -1713,6 +1715,8 @@ extern "C" int gpq_he_gemv(gpq_ctx *c, uint64_t *out_c0, uint64_t *out_c1, const
   if (logDelta && (rc = gpq_he_rs(c, out_c0, out_c1, W, logDelta, logql - logDelta, batch, stream))) return rc;         // :87, src/he-rescale.c:33-54
   return launched("gpq_he_gemv");
 }
+
+#include "gemv_plan.hpp"   // he_gemv for a fixed matrix: gpq_gemv_plan_*, gpq_gemv_inner, gpq_he_gemv_planned
 
 // Tail of he_relin / he_swk alone (src/he-mult.c:67-77): out = smod(rdiv(poly_rns2mpi(chat, P*q_l), P) + d, q_l).
 extern "C" size_t gpq_relin_tail_workspace_bytes(gpq_ctx *c, unsigned W, unsigned dimB, unsigned dimP, unsigned batch) {

@@ -835,6 +835,25 @@ __global__ __launch_bounds__(256) void bridge_addsub(AddSubArgs p) {
   }
 }
 
+// gpq_gemv_plan_create: bits[k] = max over the coefficients of big-slab polynomial k (blockIdx.y) of the bit length of |coefficient|
+// (two's complement over 64 W bits; 0 for a polynomial that is identically zero).  bits[] is zero on entry.
+struct MagnitudeArgs { const uint64_t *a; unsigned *bits; unsigned W, logn; };
+
+__global__ __launch_bounds__(256) void bridge_magnitude_bits(MagnitudeArgs p) {
+  const unsigned i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= (1u << p.logn)) return;
+  const size_t base = ((size_t)blockIdx.y * p.W << p.logn) + i;
+  const uint64_t neg = 0 - (p.a[base + ((size_t)(p.W - 1) << p.logn)] >> 63);   // all ones for a negative coefficient
+  uint64_t carry = neg & 1;
+  unsigned len = 0;
+  for (unsigned j = 0; j < p.W; ++j) {                                            // |x| = (x ^ neg) + (neg & 1), word by word
+    const uint64_t v = (p.a[base + ((size_t)j << p.logn)] ^ neg) + carry;
+    carry = carry && v == 0;
+    if (v) len = 64 * j + 64 - (unsigned)__builtin_clzll(v);
+  }
+  if (len) atomicMax(p.bits + blockIdx.y, len);
+}
+
 // ---------------------------------------------------------------------------
 // he_rs on one big slab, Delta = 2^s and q_l = 2^logql (the reference's test
 // parameters, tests/gpqhe.c:1349-1352): c <- smod(rdiv(c, Delta), q_l), in place.

@@ -448,7 +448,7 @@ static const char *const kKernelNames[GPQ_K_COUNT] = {"strided_fwd", "strided_in
                                                       "tensor_mid", "keyswitch_mid", "pointwise", "small_ntt", "reference_redo",
                                                       "bridge_decompose", "bridge_reconstruct", "bridge_relin_front", "bridge_relin_tail_fused", "bridge_exact_paths", "bridge_rescale",
                                                       "bridge_relin_tail_direct", "bridge_crt_decompose", "bridge_tail_stream",
-                                                      "keyswitch_rot_mid", "automorphism_gather"};
+                                                      "keyswitch_rot_mid", "automorphism_gather", "gemv_mac"};
 
 int check_shape(const gpq_ctx *c, unsigned dim, unsigned batch, const char *who) {
   if (!c) return gpq_fail(GPQ_ERR_INVALID, "%s: null context", who);
@@ -1082,6 +1082,21 @@ int gpq_keyswitch_rotated(gpq_ctx *c, uint64_t *c0, uint64_t *c1, const uint64_t
   b.src[0] = b.dst[0] = c0; b.src[1] = b.dst[1] = c1;
   if ((rc = launch_strided<true>(c, b, dim, polys, s))) return rc;
   return after_launch("gpq_he_rot_hoisted: key switch");
+}
+
+// Inner sum of one giant step of a planned he_gemv (ntt_kernels.hpp: gemv_mac).  One launch for all limbs (no twiddles: no limb classes) and
+// the whole launch group: 4 ciphertexts per workgroup share every diagonal word (a larger group reads it once per tile of 4).
+int gpq_gemv_mac(gpq_ctx *c, uint64_t *acc0, uint64_t *acc1, const uint64_t *r0, const uint64_t *r1, const uint64_t *diag,
+                 const void *terms, unsigned nterms, unsigned dim, unsigned polys, hipStream_t s) {
+  constexpr int BT = 4;
+  GemvMacArgs a{c->d_tabs, r0, r1, diag, acc0, acc1, (const uint2 *)terms, nterms, polys, dim, c->logn};
+  const dim3 grid((polys + BT - 1) / BT, c->n >= 512 ? c->n / 512 : 1, dim);
+  ProfScope prof(c, GPQ_K_GEMV_MAC, s);
+  // (the rotations' transforms: 2 x nterms x polys polynomials read once per giant step)
+  with_nt(nt_for(c, (size_t)polys * (nterms ? nterms : 1), dim, 2), [&](auto nt) {
+    hipLaunchKernelGGL((gemv_mac<BT, decltype(nt)::value>), grid, dim3(256), 0, s, a);
+  });
+  return after_launch("gemv_mac");
 }
 
 // Which butterflies a limb runs is decided by its c = p - 2^59 (modarith.hpp): the first `wide` limbs the wide-split ones, the

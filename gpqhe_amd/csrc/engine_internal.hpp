@@ -19,7 +19,9 @@ enum { GPQ_K_STRIDED_FWD = 0, GPQ_K_STRIDED_INV, GPQ_K_CONTIG_FWD, GPQ_K_CONTIG_
        GPQ_K_CRT_DECOMPOSE, GPQ_K_TAIL_STREAM,
        // gpq_he_rot_hoisted: the key switch of one rotation from the shared NTT-domain input (keyswitch_rot_mid8x2, two-pass rings); the plain
        // permutation of that input on single-pass rings (automorphism_gather)
-       GPQ_K_KEYSWITCH_ROT_MID, GPQ_K_AUTOMORPHISM_GATHER, GPQ_K_COUNT };
+       GPQ_K_KEYSWITCH_ROT_MID, GPQ_K_AUTOMORPHISM_GATHER,
+       // planned he_gemv: the inner sum of one giant step in the NTT domain (gemv_mac)
+       GPQ_K_GEMV_MAC, GPQ_K_COUNT };
 
 // Constant matrix of the matrix-core CRT fast path for one basis and result width WL (bridge_mfma.hpp)
 struct gpq_recon_mfma {
@@ -199,6 +201,10 @@ int gpq_ctx_clone(const gpq_ctx *c, gpq_ctx **out);
 int gpq_hoist_forward(gpq_ctx *c, uint64_t *slab, unsigned dim, unsigned polys, hipStream_t s);
 int gpq_keyswitch_rotated(gpq_ctx *c, uint64_t *c0, uint64_t *c1, const uint64_t *X, const uint64_t *evk0, const uint64_t *evk1,
                           unsigned dim, unsigned polys, unsigned g, void *workspace, hipStream_t s);
+// Planned he_gemv (engine.hip; bridge.hip's gpq_gemv_inner): acc0 / acc1[polys][dim][n] = the sums over `nterms` (rotation slot, diagonal)
+// pairs (device array) of r0 / r1[slot][polys][dim][n] (*) diag[diagonal][dim][n], all in the NTT domain; canonical output, ONE launch.
+int gpq_gemv_mac(gpq_ctx *c, uint64_t *acc0, uint64_t *acc1, const uint64_t *r0, const uint64_t *r1, const uint64_t *diag,
+                 const void *terms, unsigned nterms, unsigned dim, unsigned polys, hipStream_t s);
 // hipMalloc of a read-only table, accounted in the context's table cache (gpq_debug_table_bytes)
 inline hipError_t gpq_table_malloc(gpq_ctx *c, void **p, size_t bytes) {
   hipError_t e = hipMalloc(p, bytes);

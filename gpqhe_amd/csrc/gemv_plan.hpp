@@ -1,0 +1,300 @@
+// gemv_plan.hpp -- he_gemv for a fixed matrix (include/gpqhe_hip.h, "he_gemv with a plan"): the plan object, one giant step's inner sum in
+// the NTT domain (gpq_gemv_inner) and the whole call (gpq_he_gemv_planned).  Part of bridge.hip's translation unit (it uses that file's
+// launch_decompose, gemv_steps, align64 and check); the kernel is gemv_mac in ntt_kernels.hpp, launched by engine.hip's gpq_gemv_mac.
+//
+// The inner sum is exact, not approximate: see the header for the identity, the bound behind gpq_gemv_acc_dim and the guard.  What runs per
+// call: the live baby rotations as ONE gpq_he_rot_hoisted, their rns_decompose + complete forward transform over `dim` limbs once, and per
+// live giant step gemv_mac -> gpq_invntt -> gpq_rns_reconstruct (centred mod 2^logql) -> he_rot by i n1 -> wrapping sum.  The inverse low
+// stages are NOT fused into gemv_mac and c1 of the inner sum goes to the giant rotation as words (reconstruct + decompose), not through
+// bridge_crt_decompose: DESIGN.md says what that leaves on the table.
+#pragma once
+
+struct gpq_gemv_plan {
+  gpq_ctx *ctx = nullptr;
+  unsigned slots = 0, n1 = 0, n2 = 0, logql = 0, dimpt = 0, dim = 0, diag_bits = 0, live = 0;
+  int exact = 0;
+  uint64_t *d_hat = nullptr;            // [slots][dim][n], NTT domain, words in [0, p]
+  size_t bytes = 0;
+  // (rotation slot, diagonal) of the live terms of giant step i at [i * n1 ...): slot = j for gpq_gemv_inner (`full`), slot = the rank of j
+  // among the live baby rotations for gpq_he_gemv_planned (`packed`)
+  uint2 *d_full = nullptr, *d_packed = nullptr;
+  std::vector<unsigned> nterms;         // per giant step
+  std::vector<unsigned> baby;           // live baby rotations, ascending
+  std::vector<unsigned char> live_diag; // per diagonal
+};
+
+namespace {
+unsigned ceil_log2(unsigned v) { unsigned b = 0; while ((1ull << b) < v) ++b; return b; }
+
+int plan_usable(const gpq_ctx *c, const gpq_gemv_plan *p, const char *who) {
+  if (!p) return gpq_fail(GPQ_ERR_INVALID, "%s: null plan", who);
+  if (p->ctx != c) return gpq_fail(GPQ_ERR_INVALID, "%s: the plan belongs to another context", who);
+  if (!p->exact)
+    return gpq_fail(GPQ_ERR_INVALID, "%s: the plan is not exact (diagonals of %u bits at q = 2^%u: one product can wrap the %u-limb basis of he_mulpt, or %u limbs exceed the context's %u): use gpq_he_gemv",
+                    who, p->diag_bits, p->logql, p->dimpt, p->dim, c->nprimes);
+  return GPQ_OK;
+}
+bool ranges_overlap(const uint64_t *a, size_t na, const uint64_t *b, size_t nb) { return a < b + nb && b < a + na; }
+
+// acc -> words: inverse transform of both sums (acc0 | acc1 contiguous), then one reconstruction per polynomial of the ciphertext
+int inner_finish(gpq_ctx *c, const gpq_gemv_plan *p, uint64_t *out0, uint64_t *out1, uint64_t *acc, unsigned W, unsigned polys, void *stream) {
+  const size_t slab = (size_t)polys * p->dim * c->n;
+  int rc;
+  if ((rc = gpq_invntt(c, acc, p->dim, 2 * polys, stream))) return rc;
+  if ((rc = gpq_rns_reconstruct(c, out0, W, acc, p->dim, polys, p->logql, stream))) return rc;
+  return gpq_rns_reconstruct(c, out1, W, acc + slab, p->dim, polys, p->logql, stream);
+}
+}  // namespace
+
+extern "C" unsigned gpq_gemv_acc_dim(unsigned logql, unsigned diag_bits, unsigned logn, unsigned n1) {
+  const unsigned long long need = (unsigned long long)logql - (logql ? 1 : 0) + diag_bits + logn + ceil_log2(n1 ? n1 : 1) + 1;   // L + 1 <= 59 d
+  const unsigned long long d = (need + 58) / 59;
+  return d ? (unsigned)d : 1u;
+}
+
+extern "C" void gpq_gemv_plan_destroy(gpq_gemv_plan *p) {
+  if (!p) return;
+  DeviceScope on_device(p->ctx->device);
+  if (p->d_hat) (void)hipFree(p->d_hat);
+  if (p->d_full) (void)hipFree(p->d_full);
+  if (p->d_packed) (void)hipFree(p->d_packed);
+  delete p;
+}
+
+extern "C" int gpq_gemv_plan_info(const gpq_gemv_plan *p, unsigned *dim, size_t *bytes, unsigned *live, int *exact) {
+  if (!p) return gpq_fail(GPQ_ERR_INVALID, "gpq_gemv_plan_info: null plan");
+  if (dim) *dim = p->dim;
+  if (bytes) *bytes = p->bytes;
+  if (live) *live = p->live;
+  if (exact) *exact = p->exact;
+  return GPQ_OK;
+}
+
+extern "C" int gpq_gemv_plan_rotations(const gpq_gemv_plan *p, unsigned char *needed) {
+  if (!p || !needed) return gpq_fail(GPQ_ERR_INVALID, "gpq_gemv_plan_rotations: null argument");
+  memset(needed, 0, p->slots);
+  for (unsigned j : p->baby) needed[j] = 1;
+  for (unsigned i = 0; i < p->n2; ++i) if (p->nterms[i]) needed[i * p->n1] = 1;
+  return GPQ_OK;
+}
+
+extern "C" int gpq_gemv_plan_create(gpq_ctx *c, gpq_gemv_plan **out, const uint64_t *diag, unsigned slots, unsigned W, unsigned logql,
+                                    unsigned dimpt, void *stream) {
+  int rc = check(c, dimpt, slots, "gpq_gemv_plan_create");
+  if (rc) return rc;
+  if (!out || !diag || !logql || W < 1 || W > 32) return gpq_fail(GPQ_ERR_INVALID, "gpq_gemv_plan_create: bad arguments");
+  hipStream_t s = (hipStream_t)stream;
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
+    return gpq_fail(GPQ_ERR_INVALID, "gpq_gemv_plan_create allocates and waits for the stream: not inside a stream capture");
+  std::unique_ptr<gpq_gemv_plan, void (*)(gpq_gemv_plan *)> p(new (std::nothrow) gpq_gemv_plan(), gpq_gemv_plan_destroy);
+  if (!p) return gpq_fail(GPQ_ERR_NOMEM, "out of host memory");
+  p->ctx = c; p->slots = slots; p->logql = logql; p->dimpt = dimpt;
+  gemv_steps(slots, &p->n1, &p->n2);
+  // the largest coefficient of every diagonal, on the device
+  std::vector<unsigned> bits(slots, 0);
+  {
+    unsigned *d_bits = nullptr;
+    HIP_TRY(hipMalloc((void **)&d_bits, slots * sizeof(unsigned)));
+    hipError_t e = hipMemsetAsync(d_bits, 0, slots * sizeof(unsigned), s);
+    for (unsigned k0 = 0; k0 < slots && e == hipSuccess; k0 += 65535) {
+      const unsigned cnt = slots - k0 < 65535 ? slots - k0 : 65535u;
+      MagnitudeArgs m{diag + (size_t)k0 * W * c->n, d_bits + k0, W, c->logn};
+      hipLaunchKernelGGL(bridge_magnitude_bits, dim3((c->n + 255) / 256, cnt), dim3(256), 0, s, m);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(bits.data(), d_bits, slots * sizeof(unsigned), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    (void)hipFree(d_bits);
+    if (e != hipSuccess) return gpq_fail(GPQ_ERR_HIP, "gpq_gemv_plan_create: measuring the diagonals: %s", hipGetErrorString(e));
+  }
+  p->live_diag.resize(slots);
+  for (unsigned k = 0; k < slots; ++k) {
+    p->live_diag[k] = bits[k] != 0;
+    p->live += bits[k] != 0;
+    if (bits[k] > p->diag_bits) p->diag_bits = bits[k];
+  }
+  const unsigned acc = gpq_gemv_acc_dim(logql, p->diag_bits, c->logn, p->n1);
+  p->dim = acc > dimpt ? acc : dimpt;
+  const bool product_exact = (unsigned long long)logql - 1 + p->diag_bits + c->logn + 1 <= 59ull * dimpt;
+  p->exact = product_exact && p->dim <= c->nprimes;
+  // the live terms of every giant step
+  std::vector<unsigned> rank(p->n1, 0);
+  for (unsigned j = 0; j < p->n1; ++j) {
+    bool any = false;
+    for (unsigned i = 0; i < p->n2; ++i) any = any || p->live_diag[i * p->n1 + j];
+    if (any) { rank[j] = (unsigned)p->baby.size(); p->baby.push_back(j); }
+  }
+  std::vector<uint2> full((size_t)p->n1 * p->n2), packed(full.size());
+  p->nterms.assign(p->n2, 0);
+  for (unsigned i = 0; i < p->n2; ++i)
+    for (unsigned j = 0; j < p->n1; ++j)
+      if (p->live_diag[i * p->n1 + j]) {
+        const size_t t = (size_t)i * p->n1 + p->nterms[i]++;
+        full[t] = make_uint2(j, i * p->n1 + j);
+        packed[t] = make_uint2(rank[j], i * p->n1 + j);
+      }
+  if (!p->exact) { *out = p.release(); return GPQ_OK; }            // holds nothing: the entry points refuse it
+  DeviceScope on_device(c->device);
+  HIP_TRY(hipMalloc((void **)&p->d_full, full.size() * sizeof(uint2)));
+  HIP_TRY(hipMalloc((void **)&p->d_packed, full.size() * sizeof(uint2)));
+  HIP_TRY(hipMemcpy(p->d_full, full.data(), full.size() * sizeof(uint2), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(p->d_packed, packed.data(), full.size() * sizeof(uint2), hipMemcpyHostToDevice));
+  const size_t poly = (size_t)p->dim * c->n;
+  p->bytes = (size_t)slots * poly * 8;
+  if (hipMalloc((void **)&p->d_hat, p->bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    return gpq_fail(GPQ_ERR_NOMEM, "gpq_gemv_plan_create: no room for %zu bytes of transformed diagonals", p->bytes);
+  }
+  {
+    StageRange stage("gpq_gemv_plan_create: rns_decompose + forward transform of the diagonals");
+    for (unsigned k0 = 0; k0 < slots; k0 += c->chunk) {               // (zero diagonals too: their words are never read, but stay defined)
+      const unsigned cnt = slots - k0 < c->chunk ? slots - k0 : c->chunk;
+      if ((rc = launch_decompose(c, p->d_hat + k0 * poly, diag + (size_t)k0 * W * c->n, W, 0, p->dim, cnt, s))) return rc;
+      if ((rc = gpq_hoist_forward(c, p->d_hat + k0 * poly, p->dim, cnt, s))) return rc;
+    }
+  }
+  if ((rc = launched("gpq_gemv_plan_create"))) return rc;
+  *out = p.release();
+  return GPQ_OK;
+}
+
+extern "C" size_t gpq_gemv_inner_workspace_bytes(gpq_ctx *c, const gpq_gemv_plan *p, unsigned batch) {
+  if (!c || !p || !batch) return 0;
+  const unsigned m = batch < c->chunk ? batch : c->chunk;
+  const size_t slab = (size_t)m * p->dim * c->n * 8;
+  return align64(2 * p->n1 * slab) + align64(2 * slab);
+}
+
+extern "C" int gpq_gemv_inner(gpq_ctx *c, uint64_t *out_c0, uint64_t *out_c1, const uint64_t *R0, const uint64_t *R1, const gpq_gemv_plan *p,
+                              unsigned giant, unsigned W, unsigned batch, void *workspace, void *stream) {
+  int rc = check(c, 1, batch, "gpq_gemv_inner");
+  if (rc || (rc = plan_usable(c, p, "gpq_gemv_inner"))) return rc;
+  if (!out_c0 || !out_c1 || !R0 || !R1 || !workspace || giant >= p->n2 || W < (p->logql + 63) / 64 || W > 32)
+    return gpq_fail(GPQ_ERR_INVALID, "gpq_gemv_inner: bad arguments (giant step < %u, W words must hold q = 2^%u)", p->n2, p->logql);
+  const size_t n = c->n, bigpoly = (size_t)W * n, out_words = batch * bigpoly, in_words = p->n1 * out_words;
+  if (ranges_overlap(out_c0, out_words, out_c1, out_words) || ranges_overlap(out_c0, out_words, R0, in_words) || ranges_overlap(out_c0, out_words, R1, in_words) ||
+      ranges_overlap(out_c1, out_words, R0, in_words) || ranges_overlap(out_c1, out_words, R1, in_words))
+    return gpq_fail(GPQ_ERR_INVALID, "gpq_gemv_inner: the outputs alias each other or an input");
+  hipStream_t s = (hipStream_t)stream;
+  const unsigned nterms = p->nterms[giant];
+  if (!nterms) {                                                        // every diagonal of the step is zero: an exact zero
+    HIP_TRY(hipMemsetAsync(out_c0, 0, out_words * 8, s));
+    HIP_TRY(hipMemsetAsync(out_c1, 0, out_words * 8, s));
+    return GPQ_OK;
+  }
+  const unsigned m = batch < c->chunk ? batch : c->chunk;
+  const size_t group_slab = (size_t)m * p->dim * n;
+  uint64_t *hat = (uint64_t *)workspace, *acc = (uint64_t *)((char *)workspace + align64(2 * p->n1 * group_slab * 8));
+  for (unsigned k0 = 0; k0 < batch; k0 += m) {
+    const unsigned polys = batch - k0 < m ? batch - k0 : m;
+    const size_t slab = (size_t)polys * p->dim * n;
+    uint64_t *hat0 = hat, *hat1 = hat + p->n1 * slab;
+    {
+      StageRange stage("gpq_gemv_inner: rns_decompose + forward transform of the rotations");
+      for (unsigned j = 0; j < p->n1; ++j) {
+        const size_t src = ((size_t)j * batch + k0) * bigpoly;
+        if (!p->live_diag[giant * p->n1 + j]) {                       // not read by gemv_mac; keeps the transform below on defined words
+          HIP_TRY(hipMemsetAsync(hat0 + j * slab, 0, slab * 8, s));
+          HIP_TRY(hipMemsetAsync(hat1 + j * slab, 0, slab * 8, s));
+          continue;
+        }
+        if ((rc = launch_decompose(c, hat0 + j * slab, R0 + src, W, 0, p->dim, polys, s))) return rc;
+        if ((rc = launch_decompose(c, hat1 + j * slab, R1 + src, W, 0, p->dim, polys, s))) return rc;
+      }
+      if ((rc = gpq_hoist_forward(c, hat, p->dim, 2 * p->n1 * polys, s))) return rc;
+    }
+    if ((rc = gpq_gemv_mac(c, acc, acc + slab, hat0, hat1, p->d_hat, p->d_full + (size_t)giant * p->n1, nterms, p->dim, polys, s))) return rc;
+    if ((rc = inner_finish(c, p, out_c0 + k0 * bigpoly, out_c1 + k0 * bigpoly, acc, W, polys, stream))) return rc;
+  }
+  return launched("gpq_gemv_inner");
+}
+
+namespace {
+struct PlannedLayout { size_t rb, hat, acc, p, g, ws, total; };
+int planned_layout(gpq_ctx *c, const gpq_gemv_plan *p, unsigned W, unsigned dimB, unsigned dimP, unsigned m, PlannedLayout *l) {
+  const size_t nb = p->baby.size(), big = (size_t)m * W * c->n * 8, slab = (size_t)m * p->dim * c->n * 8;
+  l->rb = 2 * align64(nb * big);                       // the live baby rotations, c0 | c1
+  l->hat = align64(2 * nb * slab);                     // ... decomposed and transformed
+  l->acc = align64(2 * slab);                          // one giant step's sums
+  l->p = 2 * align64(big);                             // ... as words
+  l->g = 2 * align64(big);                             // one giant rotation
+  const size_t wn = nb ? gpq_he_rot_hoisted_workspace_bytes(c, W, dimB, dimP, (unsigned)nb, m) : 0, w1 = gpq_he_rot_hoisted_workspace_bytes(c, W, dimB, dimP, 1, m);
+  if ((nb && !wn) || !w1) return GPQ_ERR_INVALID;      // (the rotation plan's message is in gpq_last_error)
+  l->ws = align64(wn > w1 ? wn : w1);
+  l->total = l->rb + l->hat + l->acc + l->p + l->g + l->ws;
+  return GPQ_OK;
+}
+}  // namespace
+
+extern "C" size_t gpq_he_gemv_planned_workspace_bytes(gpq_ctx *c, const gpq_gemv_plan *p, unsigned W, unsigned dimB, unsigned dimP, unsigned batch) {
+  if (!c || !p || !batch || !W) return 0;
+  PlannedLayout l;
+  return planned_layout(c, p, W, dimB, dimP, batch < c->chunk ? batch : c->chunk, &l) == GPQ_OK ? l.total : 0;
+}
+
+extern "C" int gpq_he_gemv_planned(gpq_ctx *c, uint64_t *out_c0, uint64_t *out_c1, const uint64_t *c0, const uint64_t *c1, const gpq_gemv_plan *p,
+                                   const uint64_t *const *rk0, const uint64_t *const *rk1, unsigned W, unsigned logDelta, unsigned dimB,
+                                   unsigned dimP, unsigned batch, void *workspace, void *stream) {
+  int rc = check(c, dimB, batch, "gpq_he_gemv_planned");
+  if (rc || (rc = plan_usable(c, p, "gpq_he_gemv_planned"))) return rc;
+  const unsigned logql = p->logql, n1 = p->n1;
+  if (!out_c0 || !out_c1 || !c0 || !c1 || !rk0 || !rk1 || !workspace || logDelta >= logql || W < (logql + 63) / 64 || W > 32)
+    return gpq_fail(GPQ_ERR_INVALID, "gpq_he_gemv_planned: bad arguments (W words must hold q = 2^%u, Delta below q)", logql);
+  const size_t n = c->n, bigpoly = (size_t)W * n, words = batch * bigpoly;
+  if (ranges_overlap(out_c0, words, out_c1, words) || ranges_overlap(out_c0, words, c0, words) || ranges_overlap(out_c0, words, c1, words) ||
+      ranges_overlap(out_c1, words, c0, words) || ranges_overlap(out_c1, words, c1, words))
+    return gpq_fail(GPQ_ERR_INVALID, "gpq_he_gemv_planned: the outputs alias each other or an input");
+  const unsigned nb = (unsigned)p->baby.size();
+  std::vector<const uint64_t *> bk0(nb), bk1(nb);
+  for (unsigned r = 0; r < nb; ++r) {
+    bk0[r] = rk0[p->baby[r]]; bk1[r] = rk1[p->baby[r]];
+    if (!bk0[r] || !bk1[r]) return gpq_fail(GPQ_ERR_INVALID, "gpq_he_gemv_planned: key %u is NULL (a live baby rotation)", p->baby[r]);
+  }
+  for (unsigned i = 0; i < p->n2; ++i)
+    if (p->nterms[i] && (!rk0[i * n1] || !rk1[i * n1])) return gpq_fail(GPQ_ERR_INVALID, "gpq_he_gemv_planned: key %u is NULL (a live giant rotation)", i * n1);
+  hipStream_t s = (hipStream_t)stream;
+  const unsigned m = batch < c->chunk ? batch : c->chunk;
+  PlannedLayout l;
+  if (planned_layout(c, p, W, dimB, dimP, m, &l)) return gpq_fail(GPQ_ERR_INVALID, "gpq_he_gemv_planned: unsupported shape");
+  char *w = (char *)workspace;
+  uint64_t *RB0 = (uint64_t *)w, *RB1 = (uint64_t *)(w + l.rb / 2); w += l.rb;
+  uint64_t *hat = (uint64_t *)w; w += l.hat;
+  uint64_t *acc = (uint64_t *)w; w += l.acc;
+  uint64_t *P0 = (uint64_t *)w, *P1 = (uint64_t *)(w + l.p / 2); w += l.p;
+  uint64_t *G0 = (uint64_t *)w, *G1 = (uint64_t *)(w + l.g / 2); w += l.g;
+  void *ws = w;
+  for (unsigned k0 = 0; k0 < batch; k0 += m) {
+    const unsigned polys = batch - k0 < m ? batch - k0 : m;
+    const size_t o = k0 * bigpoly, slab = (size_t)polys * p->dim * n;
+    uint64_t *o0 = out_c0 + o, *o1 = out_c1 + o;
+    if (!nb) {                                                           // the zero matrix
+      HIP_TRY(hipMemsetAsync(o0, 0, polys * bigpoly * 8, s));
+      HIP_TRY(hipMemsetAsync(o1, 0, polys * bigpoly * 8, s));
+      continue;
+    }
+    uint64_t *hat0 = hat, *hat1 = hat + nb * slab;
+    if ((rc = gpq_he_rot_hoisted(c, RB0, RB1, c0 + o, c1 + o, p->baby.data(), bk0.data(), bk1.data(), nb, W, logql, dimB, dimP, polys, ws, stream))) return rc;   // src/he-algo.c:63-68
+    {
+      StageRange stage("gpq_he_gemv_planned: rns_decompose + forward transform of the baby rotations (once per group)");
+      if ((rc = launch_decompose(c, hat0, RB0, W, 0, p->dim, nb * polys, s))) return rc;
+      if ((rc = launch_decompose(c, hat1, RB1, W, 0, p->dim, nb * polys, s))) return rc;
+      if ((rc = gpq_hoist_forward(c, hat, p->dim, 2 * nb * polys, s))) return rc;
+    }
+    bool first = true;
+    for (unsigned i = 0; i < p->n2; ++i) {
+      if (!p->nterms[i]) continue;                                       // he_swk of an exact zero is zero
+      StageRange stage("gpq_he_gemv_planned: one giant step (inner sum + rotation)");
+      if ((rc = gpq_gemv_mac(c, acc, acc + slab, hat0, hat1, p->d_hat, p->d_packed + (size_t)i * n1, p->nterms[i], p->dim, polys, s))) return rc;   // :70-78
+      if ((rc = inner_finish(c, p, P0, P1, acc, W, polys, stream))) return rc;
+      const unsigned shift = i * n1;
+      uint64_t *g0 = first ? o0 : G0, *g1 = first ? o1 : G1;                                                             // :80-84
+      if ((rc = gpq_he_rot_hoisted(c, g0, g1, P0, P1, &shift, rk0 + shift, rk1 + shift, 1, W, logql, dimB, dimP, polys, ws, stream))) return rc;
+      if (!first && ((rc = gpq_big_addsub(c, o0, o0, G0, W, polys, 0, stream)) || (rc = gpq_big_addsub(c, o1, o1, G1, W, polys, 0, stream)))) return rc;
+      first = false;
+    }
+  }
+  if ((rc = gpq_he_rs(c, out_c0, out_c1, W, 0, logql, batch, stream))) return rc;                                      // the adds' mpi_smod
+  if (logDelta && (rc = gpq_he_rs(c, out_c0, out_c1, W, logDelta, logql - logDelta, batch, stream))) return rc;         // :87, src/he-rescale.c:33-54
+  return launched("gpq_he_gemv_planned");
+}

@@ -25,6 +25,7 @@
 #include <condition_variable>
 #include <functional>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <set>
 #include <thread>
@@ -47,6 +48,7 @@ extern "C" void he_ecd(struct he_pt *pt, const _Complex double *m) __attribute__
 #error "mpi_shim.hip relies on the legacy (process-wide) null stream: build without -fgpu-default-stream=per-thread"
 #endif
 
+#include "shim_gemv_plans.hpp"
 #include "shim_staging.hpp"
 #include "shim_keys.hpp"
 #include "shim_polys.hpp"

@@ -1061,6 +1061,69 @@ __global__ __launch_bounds__(256) void automorphism_gather(const uint64_t *__res
   dst[row + j] = src[row + automorphism_src(j, logn, g)];
 }
 
+// ---------------------------------------------------------------------------
+// Inner sum of one giant step of a planned he_gemv (gpq_gemv_inner, gpq_he_gemv_planned), in the NTT domain:
+//   acc0[b][l][x] = sum_t r0[terms[t].x][b][l][x] * diag[terms[t].y][l][x]  (mod p_l),   acc1 the same from r1,
+// over the live terms of the step (terms[t] = (rotation slot in r0 / r1, diagonal of the plan): uniform, read with scalar loads).  r0 / r1 =
+// the complete forward transforms of the baby rotations, words in [0, p] (the reference's p-for-zero words included); diag = the plan's
+// diagonals, words in [0, p]; acc canonical.  The complete inverse transform follows (gpq_invntt).
+// Exactness, for ANY number of terms: a product is mulmod_lazy(u <= p, d <= p) in (0, 4p) (modarith.hpp: a < 8p, x = a w <= p^2 < 8p^2),
+// the running sum enters a step below 4p, sum + product < 8p < 2^63 does not wrap, and one conditional subtraction of 4p brings it back
+// below 4p; canon4 at the end.  (tests/test_gemv_acc_dim.py is the integer model, at n1 = 511, the largest the reference can produce.)
+// Traffic: a workgroup keeps BT ciphertexts (2 BT polynomials, 16 bytes per lane each) in registers and reads every diagonal word ONCE for
+// all of them.  A launch group of more than BT ciphertexts has one workgroup per tile of BT (blockIdx.x, the fastest grid index); measured,
+// these do NOT meet in L2: each tile fetches its diagonal words again (PMC at n = 2^16, 16 limbs, n1 = 8, 16 ciphertexts: 2560 MiB per launch
+// against 2368 MiB algorithmic, 1.08x -- the 192 MiB are the three extra reads of the 64 MiB of diagonals; profiles/r08).  16 bytes per lane
+// and load; NT = the rotations' words pass with the nt policy (they are read once per giant step; the diagonals and the sums keep the
+// default policy).
+typedef unsigned long long v2u64 __attribute__((ext_vector_type(2)));
+struct GemvMacArgs {
+  const LimbTab *tabs;
+  const uint64_t *r0, *r1;            // [slot][polys][dim][n]
+  const uint64_t *diag;               // [slots][dim][n]
+  uint64_t *acc0, *acc1;              // [polys][dim][n]
+  const uint2 *terms;
+  unsigned nterms, polys, dim, logn;
+};
+template <bool NT>
+__device__ __forceinline__ v2u64 gemv_ld16(const v2u64 *p) {
+  if constexpr (NT) return __builtin_nontemporal_load(p);
+  else return *p;
+}
+template <int BT, bool NT>
+__global__ __launch_bounds__(256) void gemv_mac(GemvMacArgs a) {
+  const PrimeK k = a.tabs[blockIdx.z].k;
+  const unsigned i2 = 2 * (blockIdx.y * 256 + threadIdx.x);
+  if (i2 >= (1u << a.logn)) return;
+  const unsigned b0 = blockIdx.x * BT, cnt = a.polys - b0 < (unsigned)BT ? a.polys - b0 : (unsigned)BT;   // b0 < polys by the grid
+  const size_t limb_off = ((size_t)blockIdx.z << a.logn) + i2, poly = (size_t)a.dim << a.logn;
+  v2u64 s0[BT], s1[BT];
+#pragma unroll
+  for (int b = 0; b < BT; ++b) s0[b] = s1[b] = v2u64{0, 0};
+  for (unsigned t = 0; t < a.nterms; ++t) {
+    const uint2 e = a.terms[t];
+    const v2u64 d = *reinterpret_cast<const v2u64 *>(a.diag + (size_t)e.y * poly + limb_off);
+    const size_t roff = ((size_t)e.x * a.polys + b0) * poly + limb_off;
+#pragma unroll
+    for (int b = 0; b < BT; ++b)
+      if (b < (int)cnt) {
+        const v2u64 *p0 = reinterpret_cast<const v2u64 *>(a.r0 + roff + b * poly), *p1 = reinterpret_cast<const v2u64 *>(a.r1 + roff + b * poly);
+        const v2u64 u = gemv_ld16<NT>(p0), v = gemv_ld16<NT>(p1);
+        s0[b].x = csub4(s0[b].x + mulmod_lazy(u.x, d.x, k), k);
+        s0[b].y = csub4(s0[b].y + mulmod_lazy(u.y, d.y, k), k);
+        s1[b].x = csub4(s1[b].x + mulmod_lazy(v.x, d.x, k), k);
+        s1[b].y = csub4(s1[b].y + mulmod_lazy(v.y, d.y, k), k);
+      }
+  }
+#pragma unroll
+  for (int b = 0; b < BT; ++b)
+    if (b < (int)cnt) {
+      const size_t o = (size_t)(b0 + b) * poly + limb_off;
+      *reinterpret_cast<v2u64 *>(a.acc0 + o) = v2u64{canon4(s0[b].x, k), canon4(s0[b].y, k)};
+      *reinterpret_cast<v2u64 *>(a.acc1 + o) = v2u64{canon4(s1[b].x, k), canon4(s1[b].y, k)};
+    }
+}
+
 // contig_pass in the 8-per-lane geometry (n = 2^17): CONTIG8_POLYS polynomials of the same limb and tile share each twiddle group.
 constexpr int CONTIG8_POLYS = 2;
 template <bool INV, typename TW, int LOW, bool NT = false>

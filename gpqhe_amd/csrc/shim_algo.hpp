@@ -1,6 +1,7 @@
 // shim_algo.hpp -- he_gemv / he_sum / he_idx (src/he-algo.c:47-113) with the reference's signatures.  Included inside mpi_shim.hip's extern "C"
 // block.  With q_l and q_(l-1) powers of two (and Delta = q_l / q_(l-1)) the whole body is one gpq_he_gemv: ct goes up once (or is used where
-// it is resident), the diagonals he_ecd encodes go up once, the keys come through the key cache, ct_dest comes back once.  Otherwise the
+// it is resident), the diagonals he_ecd encodes go up once, the keys come through the key cache, ct_dest comes back once -- or, for a matrix seen
+// before (shim_gemv_plans.hpp), one gpq_he_gemv_planned on the plan made then: no he_ecd, no conversion, no upload of diagonals.  Otherwise the
 // reference's loop runs over this library's per-call functions: the same words, no speed-up.  l / nu / B are replayed on the host in the
 // reference's order, as doubles.
 
@@ -68,7 +69,8 @@ static void gemv_loop(he_ct_t *ct_dest, const GemvMatrix &A, const he_ct_t *ct, 
   for (he_ct_t *t : {&inner, &outer, &ct_rot}) { free_poly(&t->c0, n); free_poly(&t->c1, n); }
 }
 
-static void gemv_impl(he_ct_t *ct_dest, const GemvMatrix &A, const he_ct_t *ct, const he_evk_t *rk) {
+// kind 0: he_gemv (raw = the caller's slots x slots matrix), 1: he_sum, 2: he_idx (idx): what the plan cache keys on (shim_gemv_plans.hpp)
+static void gemv_impl(he_ct_t *ct_dest, const GemvMatrix &A, const he_ct_t *ct, const he_evk_t *rk, unsigned kind, unsigned idx, const gpq_zc *raw) {
   SHIM_CALL();
   need_gcrypt();
   if (&hectx == nullptr || !hectx.q) die("`hectx` is not initialised (hectx_init first)");
@@ -86,12 +88,21 @@ static void gemv_impl(he_ct_t *ct_dest, const GemvMatrix &A, const he_ct_t *ct, 
   for (unsigned j = 0; j < n1; ++j) rots.insert(j);
   for (unsigned i = 0; i < n2; ++i) rots.insert(i * n1);
   if (!is_pow2(qw) || !is_pow2(qw1) || !delta_pow2 || logql1 >= logql || rots.size() > g_key_slots) { gemv_loop(ct_dest, A, ct, rk); return; }
-  // the diagonals, encoded by the host program's he_ecd on the reference's vectors in the reference's order (:70-72)
-  std::vector<he_pt_t> pts(slots);
+  // a plan for this very matrix at this level?  Then nothing is encoded, converted or uploaded for the diagonals.
+  GemvPlanKey key;
+  GemvPlanEntry *hit = nullptr;
+  if (g_gemv_plan_slots) {
+    key.kind = kind; key.idx = kind == 2 ? idx : 0; key.n = n; key.slots = slots; key.l = l; key.logql = logql; key.Delta = hectx.Delta;
+    if (kind == 0) key.A.assign((const unsigned char *)raw, (const unsigned char *)raw + (size_t)slots * slots * sizeof(gpq_zc));
+    hit = gemv_plan_find(key);
+  }
+  // otherwise the diagonals, encoded by the host program's he_ecd on the reference's vectors in the reference's order (:70-72)
+  std::vector<he_pt_t> pts(hit ? 0 : slots);
   std::vector<gpq_zc> rd;
   unsigned bits = logql + 1;
   bool same_nu = true;
-  for (unsigned i = 0; i < n2; ++i)
+  if (hit) bits = hit->bits;
+  for (unsigned i = 0; i < n2 && !hit; ++i)
     for (unsigned j = 0; j < n1; ++j) {
       he_pt_t &pt = pts[i * n1 + j];
       pt.nu = 0;
@@ -104,12 +115,13 @@ static void gemv_impl(he_ct_t *ct_dest, const GemvMatrix &A, const he_ct_t *ct, 
     }
   auto release_pts = [&]() { for (he_pt_t &pt : pts) free_poly(&pt.m, n); };
   if (!same_nu) { release_pts(); gemv_loop(ct_dest, A, ct, rk); return; }
+  const double ptnu = hit ? hit->nu : pts[0].nu;                   // every diagonal's
   // l / nu / B as the reference's he_mulpt (src/he-mult.c:162-164), he_add (src/he-add.c:36-38) in loop order, he_copy_ct, he_rs (src/he-rescale.c:36-38)
   double onu = 0, oB = 0;
   for (unsigned i = 0; i < n2; ++i) {
     double inu = 0, iB = 0;
     for (unsigned j = 0; j < n1; ++j) {
-      const double pnu = ct->nu * pts[i * n1 + j].nu, pB = ct->B * pts[i * n1 + j].nu;
+      const double pnu = ct->nu * ptnu, pB = ct->B * ptnu;
       if (!j) { inu = pnu; iB = pB; } else { inu = inu >= pnu ? inu : pnu; iB = iB + pB; }
     }
     if (!i) { onu = inu; oB = iB; } else { onu = onu >= inu ? onu : inu; oB = oB + iB; }
@@ -117,14 +129,37 @@ static void gemv_impl(he_ct_t *ct_dest, const GemvMatrix &A, const he_ct_t *ct, 
   const unsigned W = bits / 64 + 1;
   const unsigned nbPqL = G.mpi_get_nbits(hectx.PqL);
   const unsigned dimB = (logql + 1 + nbPqL + polyctx.logn) / 59 + 1, dimP = hectx.dim;                                // src/he-automorphism.c:52
-  const unsigned dimpt = (unsigned)((logql + 1 + log2(pts[0].nu) + polyctx.logn) / 59u + 1);                       // src/he-mult.c:169
+  const unsigned dimpt = (unsigned)((logql + 1 + log2(ptnu) + polyctx.logn) / 59u + 1);                            // src/he-mult.c:169
   const size_t big = (size_t)W * n;
-  std::vector<uint64_t> hd((size_t)slots * big);
-  for (unsigned d = 0; d < slots; ++d) to_slab(hd.data() + d * big, &pts[d].m, n, W);
-  release_pts();
+  gpq_gemv_plan *plan = hit ? hit->plan : nullptr;
+  std::unique_ptr<DevBuf> dg;
+  std::vector<uint64_t> hd;
+  if (!hit) {
+    hd.resize((size_t)slots * big);
+    for (unsigned d = 0; d < slots; ++d) to_slab(hd.data() + d * big, &pts[d].m, n, W);
+    release_pts();
+    dg.reset(new DevBuf(hd.size() * 8));
+    up(*dg, hd);
+    if (g_gemv_plan_slots && W <= 32) {                             // a plan that is not exact (or does not fit the context) is not kept: today's path
+      gpq_gemv_plan *made = nullptr;
+      int exact = 0;
+      if (gpq_gemv_plan_create(c, &made, (const uint64_t *)dg->p, slots, W, logql, dimpt, nullptr) != GPQ_OK) die("he_gemv: cannot build the plan");
+      (void)gpq_gemv_plan_info(made, nullptr, nullptr, nullptr, &exact);
+      if (exact) {
+        GemvPlanEntry e;
+        e.key = std::move(key); e.plan = made; e.nu = ptnu; e.bits = bits;
+        plan = gemv_plan_insert(std::move(e))->plan;
+      } else gpq_gemv_plan_destroy(made);
+    }
+  }
+  if (plan) {                                                      // keys of the rotations the plan reads only (he_idx: rk[0] alone)
+    std::vector<unsigned char> needed(slots, 0);
+    (void)gpq_gemv_plan_rotations(plan, needed.data());
+    for (auto it = rots.begin(); it != rots.end();) it = needed[*it] ? std::next(it) : rots.erase(it);
+  }
   HostBuf s0(big * 8), s1(big * 8), t0s(big * 8), t1s(big * 8);
-  DevBuf a0(big * 8), a1(big * 8), o0(big * 8), o1(big * 8), dg(hd.size() * 8), ws(gpq_he_gemv_workspace_bytes(c, W, slots, dimB, dimP, dimpt, 1));
-  up(dg, hd);
+  DevBuf a0(big * 8), a1(big * 8), o0(big * 8), o1(big * 8),
+         ws(plan ? gpq_he_gemv_planned_workspace_bytes(c, plan, W, dimB, dimP, 1) : gpq_he_gemv_workspace_bytes(c, W, slots, dimB, dimP, dimpt, 1));
   std::vector<const uint64_t *> k0(slots, nullptr), k1(slots, nullptr);
   for (unsigned r : rots) {                                        // at most g_key_slots keys: none of them is evicted by the next one
     KeyPrint kp(&rk[r], dimB, n);
@@ -139,9 +174,10 @@ static void gemv_impl(he_ct_t *ct_dest, const GemvMatrix &A, const he_ct_t *ct, 
   Operands ops(2, in, dd, ss, n, W);
   ops.prepare(true);
   auto device_work = [&]() {
-    if (gpq_he_gemv(c, o0.u64(), o1.u64(), ops.x[0], ops.x[1], (const uint64_t *)dg.p, k0.data(), k1.data(), slots, W, logql, logql - logql1, dimB, dimP,
-                    dimpt, 1, ws.p, nullptr) != GPQ_OK)
-      die("he_gemv failed");
+    const int rc = plan ? gpq_he_gemv_planned(c, o0.u64(), o1.u64(), ops.x[0], ops.x[1], plan, k0.data(), k1.data(), W, logql - logql1, dimB, dimP, 1, ws.p, nullptr)
+                        : gpq_he_gemv(c, o0.u64(), o1.u64(), ops.x[0], ops.x[1], (const uint64_t *)dg->p, k0.data(), k1.data(), slots, W, logql, logql - logql1,
+                                      dimB, dimP, dimpt, 1, ws.p, nullptr);
+    if (rc != GPQ_OK) die("he_gemv failed");
     download_issue(ts, oo, 2, n, W);
   };
   device_work();
@@ -160,13 +196,20 @@ static void gemv_impl(he_ct_t *ct_dest, const GemvMatrix &A, const he_ct_t *ct, 
 
 void he_gemv(he_ct_t *ct_dest, const _Complex double *A, const he_ct_t *ct, const he_evk_t *rk) {
   const unsigned m = hectx.slots;
-  gemv_impl(ct_dest, [A, m](unsigned r, unsigned col) { return A[(size_t)r * m + col]; }, ct, rk);
+  gemv_impl(ct_dest, [A, m](unsigned r, unsigned col) { return A[(size_t)r * m + col]; }, ct, rk, 0, 0, A);
 }
 // he_sum, :95-103: A = ones in row 0 (the slots x slots matrix is never built: zrotdiag reads it through this function)
 void he_sum(he_ct_t *ct_sum, const he_ct_t *ct, const he_evk_t *rk) {
-  gemv_impl(ct_sum, [](unsigned r, unsigned) { return r == 0 ? (gpq_zc)1.0 : (gpq_zc)0.0; }, ct, rk);
+  gemv_impl(ct_sum, [](unsigned r, unsigned) { return r == 0 ? (gpq_zc)1.0 : (gpq_zc)0.0; }, ct, rk, 1, 0, nullptr);
 }
 // he_idx, :105-113: A[idx][idx] = 1
 void he_idx(he_ct_t *ct_idx, const he_ct_t *ct, const unsigned int idx, const he_evk_t *rk) {
-  gemv_impl(ct_idx, [idx](unsigned r, unsigned col) { return r == idx && col == idx ? (gpq_zc)1.0 : (gpq_zc)0.0; }, ct, rk);
+  gemv_impl(ct_idx, [idx](unsigned r, unsigned col) { return r == idx && col == idx ? (gpq_zc)1.0 : (gpq_zc)0.0; }, ct, rk, 2, idx, nullptr);
+}
+// Entries of he_gemv's plan cache (default 4, least recently used out); 0 frees every plan and makes every call encode, convert and upload
+// its diagonals and run gpq_he_gemv, as before the cache existed.
+void gpq_shim_gemv_plan_cache(unsigned entries) {
+  SHIM_CALL();
+  g_gemv_plan_slots = entries;
+  gemv_plans_drop(entries);
 }

@@ -170,6 +170,7 @@ void gpq_mpi_shim_release(void) {
   g_keys.clear();
   for (hipEvent_t e : g_events) (void)hipEventDestroy(e);
   g_events.clear();
+  gemv_plans_drop(0);
   if (g_engine) { gpq_ctx_destroy(g_engine); g_engine = nullptr; }
 }
 

@@ -12,6 +12,7 @@ gpq_ctx *g_engine = nullptr;
 gpq_ctx *engine() {
   if (&polyctx == nullptr || !polyctx.n) die("`polyctx` is not initialised (polyctx_init / hectx_init first)");
   if (g_engine && gpq_ctx_logn(g_engine) == polyctx.logn && gpq_ctx_nprimes(g_engine) >= polyctx.dimub) return g_engine;
+  gemv_plans_drop(0);                        // (plans belong to the context that goes)
   if (g_engine) gpq_ctx_destroy(g_engine);
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) die("no HIP device");

@@ -373,6 +373,34 @@ class PolyContext:
                                            self._key_ptrs(rk1), slots, W, logql, logDelta, dimB, dimP, dimpt, batch, self._ptr(ws), self._stream()), "gpq_he_gemv")
         return ws
 
+    def gemv_plan(self, diag, slots, W, logql, dimpt):
+        """A plan for he_gemv with a fixed matrix: diag = slots plaintext big slabs (index i*n1 + j) as he_gemv takes them."""
+        return GemvPlan(self, diag, slots, W, logql, dimpt)
+
+    def gemv_inner(self, out_c0, out_c1, R0, R1, plan, giant, W):
+        """One giant step's inner sum smod(sum_j R_j * diag[giant n1 + j], 2^logql); R0 / R1 = n1 x batch big slabs, rotation-major."""
+        torch = _torch()
+        batch = out_c0.numel() // (W * self.n)
+        nbytes = self.lib.gpq_gemv_inner_workspace_bytes(self.h, plan.h, batch)
+        ws = torch.empty(nbytes // 8 + 8, dtype=torch.int64, device=self._dev)
+        _native.check(self.lib.gpq_gemv_inner(self.h, self._ptr(out_c0), self._ptr(out_c1), self._ptr(R0), self._ptr(R1), plan.h, giant, W, batch,
+                                              self._ptr(ws), self._stream()), "gpq_gemv_inner")
+        return ws
+
+    def he_gemv_planned(self, out_c0, out_c1, c0, c1, plan, rk0, rk1, W, logDelta, dimB, dimP, workspace=None):
+        """he_gemv + he_rs as `he_gemv` computes them, with the matrix held by `plan`; keys of rotations the plan does not need may be None."""
+        torch = _torch()
+        batch = c0.numel() // (W * self.n)
+        ws = workspace
+        if ws is None:
+            nbytes = self.lib.gpq_he_gemv_planned_workspace_bytes(self.h, plan.h, W, dimB, dimP, batch)
+            if not nbytes:
+                raise _native.GpqError("gpq_he_gemv_planned_workspace_bytes: " + self.lib.gpq_last_error().decode())
+            ws = torch.empty(nbytes // 8 + 8, dtype=torch.int64, device=self._dev)
+        _native.check(self.lib.gpq_he_gemv_planned(self.h, self._ptr(out_c0), self._ptr(out_c1), self._ptr(c0), self._ptr(c1), plan.h, self._key_ptrs(rk0),
+                                                   self._key_ptrs(rk1), W, logDelta, dimB, dimP, batch, self._ptr(ws), self._stream()), "gpq_he_gemv_planned")
+        return ws
+
     def poly_rot(self, r, a, W, rot):
         _native.check(self.lib.gpq_poly_rot(self.h, self._ptr(r), self._ptr(a), W, rot, a.numel() // (W * self.n), self._stream()), "gpq_poly_rot")
         return r
@@ -461,6 +489,38 @@ class PolyContext:
         _native.check(self.lib.gpq_keyswitch(self.h, self._ptr(c0), self._ptr(c1), self._ptr(x), self._ptr(evk0), self._ptr(evk1),
                                              dim, batch, self._ptr(ws), self._stream()), "gpq_keyswitch")
         return c0, c1
+
+
+class GemvPlan:
+    """gpq_gemv_plan: the diagonals of a fixed matrix, decomposed and forward-transformed once.  `.dim` limbs of the inner sum, `.bytes` held
+    on the device, `.live` non-zero diagonals, `.exact` False when the plan cannot reproduce he_gemv (the calls then refuse it).  `close()`
+    (or leaving a `with` block) frees the device memory at once."""
+
+    def __init__(self, ctx, diag, slots, W, logql, dimpt):
+        self.lib, self.h = ctx.lib, C.c_void_p()
+        _native.check(self.lib.gpq_gemv_plan_create(ctx.h, C.byref(self.h), ctx._ptr(diag), slots, W, logql, dimpt, ctx._stream()), "gpq_gemv_plan_create")
+        dim, nbytes, live, exact = C.c_uint(), C.c_size_t(), C.c_uint(), C.c_int()
+        _native.check(self.lib.gpq_gemv_plan_info(self.h, C.byref(dim), C.byref(nbytes), C.byref(live), C.byref(exact)), "gpq_gemv_plan_info")
+        self.dim, self.bytes, self.live, self.exact = dim.value, nbytes.value, live.value, bool(exact.value)
+        self.slots, self.logql, self.dimpt = slots, logql, dimpt
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.gpq_gemv_plan_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def gemv_acc_dim(logql, diag_bits, logn, n1):
+    """limbs the accumulated inner sum of a planned he_gemv needs to be exact (include/gpqhe_hip.h: gpq_gemv_acc_dim).  No device."""
+    return int(_native.load().gpq_gemv_acc_dim(logql, diag_bits, logn, n1))
 
 
 def automorphism_index(logn, g):

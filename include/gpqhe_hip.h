@@ -377,6 +377,49 @@ int gpq_he_gemv(gpq_ctx *ctx, uint64_t *out_c0, uint64_t *out_c1, const uint64_t
                 const uint64_t *const *rk0, const uint64_t *const *rk1, unsigned slots, unsigned W, unsigned logql,
                 unsigned logDelta, unsigned dimB, unsigned dimP, unsigned dimpt, unsigned batch, void *workspace, void *stream);
 
+/* ---- he_gemv with a plan: a FIXED matrix applied to many ciphertexts ("Planned he_gemv") --------------------------------
+ * A plan holds the matrix's diagonals once, decomposed and forward-transformed, and the inner sum of a giant step is accumulated in the
+ * NTT domain (gemv_mac): one inverse transform and one reconstruction per ciphertext polynomial and giant step instead of n1, and no
+ * per-call work on the diagonals at all.  The words are those of gpq_he_gemv.  Why: for q_l = 2^logql the reference's inner sum
+ * (src/he-algo.c:65-79: he_mulpt -> poly_rns2mpi(., q) -> he_add -> mpi_smod) is the centred residue mod q_l of S = sum_j rot_j(ct) (*)
+ * pt_ij whenever each product is exact in the reference's own dimpt-limb basis; S is exact in a basis that holds its bits, and
+ * gpq_rns_reconstruct returns the centred residue mod 2^logql of the centred value mod P.
+ *   Bound: ciphertext coefficients are centred, |c| <= 2^(logql-1); diagonal coefficients |d| <= 2^diag_bits - 1; a product coefficient
+ *   is a sum of n = 2^logn terms and S of at most n1 products: |S| < 2^(logql - 1 + diag_bits + logn + ceil(log2 n1)) =: 2^L.  S is
+ *   recovered from its residues when 2 |S| < P, and P > 2^(59 d) for d primes (every prime exceeds 2^59): L + 1 <= 59 d suffices.
+ *   gpq_gemv_acc_dim is the smallest such d (host only, no device).
+ *   Guard: when ONE product can wrap the reference's basis (logql - 1 + diag_bits + logn + 1 > 59 dimpt) the reference's result is not the
+ *   exact product any more and summing first cannot reproduce it: the plan is created with exact = 0 and holds nothing, and
+ *   gpq_gemv_inner / gpq_he_gemv_planned refuse it with GPQ_ERR_INVALID (callers use gpq_he_gemv).  The same when
+ *   dim = max(dimpt, gpq_gemv_acc_dim(..)) exceeds the context's limbs.
+ * gpq_gemv_plan_create: diag = device big slabs [slots][W][n] as gpq_he_gemv takes them (index i n1 + j); measures diag_bits on the device
+ * and returns after the plan's slab (slots x dim x n words, gpq_gemv_plan_info's `bytes`) is queued on `stream`: work on another stream
+ * orders itself with gpq_stream_wait.  It waits for `stream` once (the measurement).  Diagonals that are identically zero are recorded and
+ * never read again: `live` counts the others.  A plan belongs to its context and must be destroyed before it. */
+typedef struct gpq_gemv_plan gpq_gemv_plan;
+unsigned gpq_gemv_acc_dim(unsigned logql, unsigned diag_bits, unsigned logn, unsigned n1);
+int gpq_gemv_plan_create(gpq_ctx *ctx, gpq_gemv_plan **plan, const uint64_t *diag, unsigned slots, unsigned W, unsigned logql,
+                         unsigned dimpt, void *stream);
+void gpq_gemv_plan_destroy(gpq_gemv_plan *plan);
+int gpq_gemv_plan_info(const gpq_gemv_plan *plan, unsigned *dim, size_t *bytes, unsigned *live, int *exact);
+/* needed[r] = 1 for every rotation r < slots whose key gpq_he_gemv_planned reads (live baby rotations, giant steps with a live diagonal), else 0 */
+int gpq_gemv_plan_rotations(const gpq_gemv_plan *plan, unsigned char *needed);
+/* One giant step's inner sum: out = smod(sum_j R_j (*) diag[giant n1 + j], 2^logql) for `batch` ciphertexts; R0 / R1 = n1 x batch big slabs,
+ * rotation-major as gpq_he_rot_hoisted writes them (rotations whose diagonal is zero are not read); a giant step without a live diagonal
+ * gives zeros.  Outputs may not overlap the inputs. */
+size_t gpq_gemv_inner_workspace_bytes(gpq_ctx *ctx, const gpq_gemv_plan *plan, unsigned batch);
+int gpq_gemv_inner(gpq_ctx *ctx, uint64_t *out_c0, uint64_t *out_c1, const uint64_t *R0, const uint64_t *R1, const gpq_gemv_plan *plan,
+                   unsigned giant, unsigned W, unsigned batch, void *workspace, void *stream);
+/* gpq_he_gemv with the plan in place of `diag`, `slots`, `logql` and `dimpt`: the same words.  Baby rotations none of whose diagonals is
+ * live and giant steps without a live diagonal are skipped (both contribute exact zeros), so rk0[r] / rk1[r] may be NULL exactly for the
+ * rotations the plan does not need; the rotation by 0 is a key switch with rk[0] like any other.  Launch groups of gpq_set_chunk;
+ * outputs may not overlap the inputs or each other (GPQ_ERR_INVALID before anything is launched, as for a NULL key of a live rotation, a
+ * plan of another context, or W words that cannot hold q_l). */
+size_t gpq_he_gemv_planned_workspace_bytes(gpq_ctx *ctx, const gpq_gemv_plan *plan, unsigned W, unsigned dimB, unsigned dimP, unsigned batch);
+int gpq_he_gemv_planned(gpq_ctx *ctx, uint64_t *out_c0, uint64_t *out_c1, const uint64_t *c0, const uint64_t *c1, const gpq_gemv_plan *plan,
+                        const uint64_t *const *rk0, const uint64_t *const *rk1, unsigned W, unsigned logDelta, unsigned dimB, unsigned dimP,
+                        unsigned batch, void *workspace, void *stream);
+
 /* ---- general moduli: any q_l (little-endian words ql_words[0..Lq)) and any Delta (uint64_t, as hectx_init takes it,
  * src/gpqhe.h:100).  Same reference semantics, through the multiword Barrett kernel: slow-path quality, meant for parameter
  * sets outside the powers of two that the fast entry points above cover. */

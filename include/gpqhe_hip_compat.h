@@ -182,6 +182,11 @@ void gpq_mpi_shim_last_timing(double ms[4]);
 /* Number of evaluation keys the MPI-typed calls keep on the device between calls (default 64, least recently used out; lowering
  * the number evicts at once). */
 void gpq_mpi_shim_set_key_slots(unsigned slots);
+/* he_gemv / he_sum / he_idx keep a plan (gpqhe_hip.h: gpq_gemv_plan, the diagonals decomposed and forward-transformed) per matrix they have
+ * seen -- recognised by ring, slots, level, Delta and an exact copy of the slots x slots entries (he_sum / he_idx: by kind and idx) -- and a
+ * repeat call neither encodes (no he_ecd call), converts nor uploads diagonals.  `entries` plans are kept (default 4, least recently used
+ * out; each holds slots x limbs x n words on the device); 0 frees them and restores the per-call path.  Same results either way. */
+void gpq_shim_gemv_plan_cache(unsigned entries);
 /* How a resident key is recognised: by the caller's two pointers and a fingerprint of EVERY word, limb by limb (full != 0, the
  * default: a key edited in place multiplies as edited, like the reference, which reads its key on every call), computed by the
  * conversion threads while the device works; a call at a lower level, which reads fewer limbs of the same key (src/he-mult.c:51),
