@@ -256,7 +256,10 @@ void he_mul(he_ct_t *ct, const he_ct_t *ct1, const he_ct_t *ct2, const he_evk_t 
   gpq_ctx *c = engine();
   const unsigned n = polyctx.n, l = ct1->l;
   const double nu = ct1->nu * ct2->nu;                                                        // :93
-  const double B = ct1->nu * ct2->B + ct2->nu * ct1->B + ct1->B * ct2->B + hectx.bnd.Bmult[l];  // :94-95
+  // :94-95 read ct1->nu / ct2->nu AFTER :93 has stored the product in ct->nu: where ct is one of the operands (he_mul(&ct, &ct, &ct),
+  // src/he-algo.c:151) the reference builds B from the NEW nu -- measured against the executed reference (tests/c/mpi_host.c, mode ref)
+  const double nu1 = ct == ct1 ? nu : ct1->nu, nu2 = ct == ct2 ? nu : ct2->nu;
+  const double B = nu1 * ct2->B + nu2 * ct1->B + ct1->B * ct2->B + hectx.bnd.Bmult[l];         // :94-95
   const std::vector<uint64_t> qw = words_of(hectx.q[l], "he_mul: q_l must be positive");
   const bool pow2 = is_pow2(qw);
   const unsigned nbq = G.mpi_get_nbits(hectx.q[l]), logql = nbq - 1, nbPqL = G.mpi_get_nbits(hectx.PqL);

@@ -222,3 +222,34 @@ def he_dec_sparse(ct, sk_terms, ql):
                 prod[k - n] -= c1[i] * v
     return [mpi_smod((mpi_smod(p % ql, ql) + c) % ql, ql) for p, c in zip(prod, c0)]
 
+
+
+def gemv_steps(slots):
+    """(n1, n2) of he_gemv, src/he-algo.c:51-54"""
+    import math
+    n1 = int(math.sqrt(slots))
+    if slots != n1 * n1:
+        n1 = int(math.sqrt(2 * slots))
+    return n1, slots // n1
+
+
+def ref_gemv(o, ct, diags, keys, slots, dimP, dimB, dimpt, logql, logdelta=30):
+    """he_gemv, src/he-algo.c:47-93: baby steps he_rot(ct, j), he_mulpt by diagonal i n1 + j, he_add; giant step he_rot(inner, i n1), he_add;
+    then he_rs (src/he-rescale.c:36-50).  diags[k] is the ENCODED plaintext of the reference's k-th he_ecd call; keys[r] = (rk[r].p0, rk[r].p1)."""
+    ql = 1 << logql
+    n1, n2 = gemv_steps(slots)
+
+    def rot(c, r):
+        return he_swk(o, poly_rot(c[0], r), poly_rot(c[1], r), *keys[r], dimP, dimB, logql)
+
+    baby = [rot(ct, j) for j in range(n1)]      # the reference rotates ct again in every giant step: the same values
+    outer = None
+    for i in range(n2):
+        inner = None
+        for j in range(n1):
+            prod = he_mulpt(o, baby[j], diags[i * n1 + j], dimpt, logql)
+            inner = prod if inner is None else he_add(inner, prod, ql)
+        g = rot(inner, i * n1)
+        outer = g if outer is None else he_add(outer, g, ql)
+    qd = 1 << (logql - logdelta)
+    return [[mpi_smod(mpi_rdiv(x, 1 << logdelta), qd) for x in c] for c in outer]   # src/he-rescale.c:36-50

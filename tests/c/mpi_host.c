@@ -11,11 +11,14 @@
  *   mpi_host hemultime <logn> <logq> [threads]   wall time of he_mul / he_rescale through the MPI-typed symbols (conversions and copies included)
  *   mpi_host hemul  <in.txt>             he_mul on ciphertexts read as hex, then he_rs, then he_moddown
  *   mpi_host ctxcheck <logn> <logq> <Delta>   every field hectx_init / polyctx_init fill, for comparison with the restated formulas
+ *   mpi_host ref <path> <logn> <logq> <logDelta> <seed>   the same MPIs through the reference built into oracle/_ref/ (dlopen) and through this library;
+ *                                        path "-": this library alone; `refonly <path> ...`: the reference alone, no device (see refmode)
  *
  * `polyctx`, `hectx`, polyctx_init, hectx_init and the poly_*_alloc functions are the library's (weak) definitions of the
  * reference's symbols (src/poly.h:80-83,94-95, src/gpqhe.h:100-101), so this host restates nothing of src/precomp.c.
  * libgcrypt's public functions are declared here by hand: the image has the runtime library only.
  */
+#define _GNU_SOURCE            /* RTLD_DEEPBIND */
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -887,6 +890,151 @@ static int residentfuzz(unsigned logn, unsigned logq, unsigned logDelta, unsigne
   return 0;
 }
 
+/* `ref <path> logn logq logDelta seed`: the SAME MPIs through the reference itself and through this library's symbols of the same names.
+ * <path> is a build of the reference made by `make -C oracle ref` (oracle/_ref/; tests/test_ref_parity_gpu.py passes oracle.ref.which()),
+ * opened RTLD_LOCAL | RTLD_DEEPBIND: it keeps its own polyctx / hectx, initialised by its own hectx_init.  After every call every coefficient,
+ * l and the bits of nu and B must be equal, and each side prints a digest of its result (`lib ..` / `ref ..`).
+ *   ref <path>      both sides, compared word for word
+ *   ref -           this library alone (a machine without the reference): its digests, to be compared with the reference's recorded ones
+ *   refonly <path>  the reference alone, no device touched: how tests/golden/ref_hosts.json is written and re-checked on a CPU
+ * Inputs are functions of the seed alone and evaluation keys are seeded residue slabs (fill_key), so that the reference's side can be
+ * reproduced without a device; key generation has its own test (`keygen`). */
+#include <dlfcn.h>
+static uint64_t fnv_bytes(uint64_t h, const void *p, size_t bytes) { for (size_t i = 0; i < bytes; i++) { h ^= ((const unsigned char *)p)[i]; h *= 0x100000001b3ull; } return h; }
+
+static uint64_t ct_digest(const he_ct_t *a, unsigned n)      /* FNV-1a over l, the bits of nu and B and every coefficient in hex */
+{
+  uint64_t w[3] = {a->l, 0, 0};
+  memcpy(&w[1], &a->nu, 8); memcpy(&w[2], &a->B, 8);
+  uint64_t h = fnv_bytes(0xcbf29ce484222325ull, w, sizeof w);
+  const poly_mpi_t *p[2] = {&a->c0, &a->c1};
+  for (int c = 0; c < 2; c++)
+    for (unsigned k = 0; k < n; k++) {
+      unsigned char *t = NULL;
+      gcry_mpi_aprint(FMT_HEX, &t, NULL, p[c]->coeffs[k]);
+      h = fnv_bytes(h, t, strlen((char *)t) + 1);
+      gcry_free(t);
+    }
+  return h;
+}
+
+static int same_ct(const char *what, const he_ct_t *a, const he_ct_t *b, unsigned n)
+{
+  if (a->l != b->l) { printf("%s: l %u (library) vs %u (reference)\n", what, a->l, b->l); return 1; }
+  if (memcmp(&a->nu, &b->nu, 8) || memcmp(&a->B, &b->B, 8)) { printf("%s: nu %a B %a (library) vs nu %a B %a (reference)\n", what, a->nu, a->B, b->nu, b->B); return 1; }
+  for (unsigned k = 0; k < n; k++)
+    if (gcry_mpi_cmp(a->c0.coeffs[k], b->c0.coeffs[k]) || gcry_mpi_cmp(a->c1.coeffs[k], b->c1.coeffs[k])) { printf("%s: coefficient %u differs from the reference\n", what, k); return 1; }
+  return 0;
+}
+
+static int refmode(const char *path, int with_lib, unsigned logn, unsigned logq, unsigned logDelta, uint64_t seed)
+{
+  const int have = strcmp(path, "-") != 0;                   /* the reference is at hand */
+  if (!have && !with_lib) return 2;
+  void *h = have ? dlopen(path, RTLD_NOW | RTLD_LOCAL | RTLD_DEEPBIND) : NULL;
+  if (have && !h) { fprintf(stderr, "ref: cannot open %s: %s\n", path, dlerror()); return 2; }
+#define SYM(type, name) type = have ? dlsym(h, #name) : NULL; if (have && !r_##name) { fprintf(stderr, "ref: no symbol %s\n", #name); return 2; }
+  void (*r_hectx_init)(unsigned int, MPI, unsigned int, uint64_t); SYM(r_hectx_init, hectx_init)
+  void (*r_poly_mpi_alloc)(poly_mpi_t *); SYM(r_poly_mpi_alloc, poly_mpi_alloc)
+  void (*r_he_mul)(he_ct_t *, const he_ct_t *, const he_ct_t *, const he_evk_t *); SYM(r_he_mul, he_mul)
+  void (*r_he_rs)(he_ct_t *); SYM(r_he_rs, he_rs)
+  void (*r_he_moddown)(he_ct_t *); SYM(r_he_moddown, he_moddown)
+  void (*r_he_rot)(he_ct_t *, const int, const he_evk_t *); SYM(r_he_rot, he_rot)
+  void (*r_he_conj)(he_ct_t *, const he_evk_t *); SYM(r_he_conj, he_conj)
+  void (*r_he_mulpt)(he_ct_t *, const he_ct_t *, const he_pt_t *); SYM(r_he_mulpt, he_mulpt)
+  void (*r_he_add)(he_ct_t *, const he_ct_t *, const he_ct_t *); SYM(r_he_add, he_add)
+  void (*r_he_sub)(he_ct_t *, const he_ct_t *, const he_ct_t *); SYM(r_he_sub, he_sub)
+  void (*r_he_neg)(he_ct_t *); SYM(r_he_neg, he_neg)
+  void (*r_he_addpt)(he_ct_t *, const he_ct_t *, const he_pt_t *); SYM(r_he_addpt, he_addpt)
+  void (*r_he_subpt)(he_ct_t *, const he_ct_t *, const he_pt_t *); SYM(r_he_subpt, he_subpt)
+  struct he_ctx *r_hectx = have ? dlsym(h, "hectx") : NULL;
+  struct poly_ctx *r_polyctx = have ? dlsym(h, "polyctx") : NULL;
+  if (have && (!r_hectx || !r_polyctx || (void *)r_hectx == (void *)&hectx)) { fprintf(stderr, "ref: the reference's hectx is not its own\n"); return 2; }
+#undef SYM
+  MPI q = pow2(logq);
+  if (with_lib) hectx_init(logn, q, 2, 1ull << logDelta);     /* this library's context, bounds as hectx_init computes them */
+  if (have) r_hectx_init(logn, q, 2, 1ull << logDelta);       /* the reference's own */
+  const struct he_ctx *hx = with_lib ? &hectx : r_hectx;      /* whichever side is there describes the shape */
+  const struct poly_ctx *px = with_lib ? &polyctx : r_polyctx;
+  if (with_lib && have) {
+    if (hectx.L != r_hectx->L || hectx.dim != r_hectx->dim || hectx.dimevk != r_hectx->dimevk) { printf("hectx: L / dim / dimevk differ\n"); return 1; }
+    if (memcmp(&hectx.bnd.Brs, &r_hectx->bnd.Brs, 8)) { printf("hectx.bnd.Brs: %a vs %a\n", hectx.bnd.Brs, r_hectx->bnd.Brs); return 1; }
+    for (unsigned l = 0; l <= hectx.L; l++)
+      if (memcmp(&hectx.bnd.Bmult[l], &r_hectx->bnd.Bmult[l], 8)) { printf("hectx.bnd.Bmult[%u]: %a vs %a\n", l, hectx.bnd.Bmult[l], r_hectx->bnd.Bmult[l]); return 1; }
+  }
+  for (int side = 0; side < 2; side++) {                      /* the context as a digest line: L, dim, dimevk, the bits of Brs and of every Bmult[l] */
+    if (side ? !have : !with_lib) continue;
+    const struct he_ctx *x = side ? r_hectx : &hectx;
+    uint64_t w[4] = {x->L, x->dim, x->dimevk, 0};
+    memcpy(&w[3], &x->bnd.Brs, 8);
+    uint64_t hh = fnv_bytes(0xcbf29ce484222325ull, w, sizeof w);
+    hh = fnv_bytes(hh, x->bnd.Bmult, (x->L + 1) * sizeof(double));
+    printf("%s hectx %016llx\n", side ? "ref" : "lib", (unsigned long long)hh);
+  }
+  const unsigned n = px->n;
+  void (*palloc)(poly_mpi_t *) = with_lib ? poly_mpi_alloc : r_poly_mpi_alloc;
+  uint64_t st = seed;
+  he_evk_t keys[4];                                          /* rlk, ck, rk[0], rk[1]: seeded residues of each prime */
+  const size_t words = (size_t)hx->dimevk * n;
+  for (int k = 0; k < 4; k++) {
+    keys[k].p0.coeffs = malloc(words * 8); keys[k].p1.coeffs = malloc(words * 8);
+    uint64_t ks = seed + 7000 + (uint64_t)k;
+    const struct rns_ctx *r = px->rns;
+    for (unsigned d = 0; d < hx->dimevk; d++, r = r->next)
+      for (unsigned i = 0; i < n; i++) { keys[k].p0.coeffs[(size_t)d * n + i] = splitmix64(&ks) % r->p; keys[k].p1.coeffs[(size_t)d * n + i] = splitmix64(&ks) % r->p; }
+  }
+  enum { K = 3 };
+  he_ct_t x[K], y[K];                                        /* x: this library; y: the reference */
+  unsigned char *buf = malloc(logq / 8 + 16);
+  for (int i = 0; i < K; i++) {
+    palloc(&x[i].c0); palloc(&x[i].c1); palloc(&y[i].c0); palloc(&y[i].c1);
+    poly_mpi_t *ps[2] = {&x[i].c0, &x[i].c1}, *pt[2] = {&y[i].c0, &y[i].c1};
+    for (int c = 0; c < 2; c++)
+      for (unsigned k = 0; k < n; k++) {
+        const unsigned nb = (logq - 2) / 8;
+        for (unsigned b = 0; b < nb; b += 8) { uint64_t v = splitmix64(&st); memcpy(buf + b, &v, 8); }
+        MPI t = NULL;
+        gcry_mpi_scan(&t, 5, buf, nb, NULL);
+        if (k < 3) gcry_mpi_set_ui(t, k);                     /* 0, 1 and -2 among them */
+        if ((splitmix64(&st) & 1) || k == 2) gcry_mpi_neg(t, t);
+        gcry_mpi_set(ps[c]->coeffs[k], t);
+        gcry_mpi_set(pt[c]->coeffs[k], t);
+        gcry_mpi_release(t);
+      }
+    x[i].l = y[i].l = hx->L; x[i].nu = y[i].nu = 3.0 + i; x[i].B = y[i].B = 17.25 * (i + 1);
+  }
+  he_pt_t pt;
+  palloc(&pt.m);
+  pt.nu = (double)(1ull << logDelta);
+  for (unsigned i = 0; i < n; i++) { gcry_mpi_set_ui(pt.m.coeffs[i], (unsigned long)(splitmix64(&st) >> (64 - logDelta))); if (i & 1) gcry_mpi_neg(pt.m.coeffs[i], pt.m.coeffs[i]); }
+  unsigned calls = 0;
+#define BOTH(what, d, lib_call, ref_call) do { calls++; \
+    if (with_lib) { lib_call; printf("lib %s %016llx\n", what, (unsigned long long)ct_digest(&x[d], n)); } \
+    if (have) { ref_call; printf("ref %s %016llx\n", what, (unsigned long long)ct_digest(&y[d], n)); } \
+    if (with_lib && have && same_ct(what, &x[d], &y[d], n)) return 1; } while (0)
+  BOTH("he_add", 2, he_add(&x[2], &x[0], &x[1]), r_he_add(&y[2], &y[0], &y[1]));
+  BOTH("he_sub", 2, he_sub(&x[2], &x[0], &x[1]), r_he_sub(&y[2], &y[0], &y[1]));
+  BOTH("he_addpt", 2, he_addpt(&x[2], &x[0], &pt), r_he_addpt(&y[2], &y[0], &pt));
+  BOTH("he_subpt", 2, he_subpt(&x[2], &x[1], &pt), r_he_subpt(&y[2], &y[1], &pt));
+  BOTH("he_neg", 2, he_neg(&x[2]), r_he_neg(&y[2]));
+  BOTH("he_mulpt", 2, he_mulpt(&x[2], &x[0], &pt), r_he_mulpt(&y[2], &y[0], &pt));
+  BOTH("he_rs after he_mulpt", 2, he_rs(&x[2]), r_he_rs(&y[2]));
+  BOTH("he_mul", 2, he_mul(&x[2], &x[0], &x[1], &keys[0]), r_he_mul(&y[2], &y[0], &y[1], &keys[0]));
+  BOTH("he_rs", 2, he_rs(&x[2]), r_he_rs(&y[2]));
+  BOTH("he_mul of a ciphertext with itself, in place", 2, he_mul(&x[2], &x[2], &x[2], &keys[0]), r_he_mul(&y[2], &y[2], &y[2], &keys[0]));
+  BOTH("he_rot 1", 0, he_rot(&x[0], 1, &keys[2]), r_he_rot(&y[0], 1, &keys[2]));
+  BOTH("he_rot 0", 0, he_rot(&x[0], 0, &keys[2]), r_he_rot(&y[0], 0, &keys[2]));
+  BOTH("he_conj", 1, he_conj(&x[1], &keys[1]), r_he_conj(&y[1], &keys[1]));
+  BOTH("he_moddown", 1, he_moddown(&x[1]), r_he_moddown(&y[1]));
+  BOTH("he_moddown", 0, he_moddown(&x[0]), r_he_moddown(&y[0]));
+  BOTH("he_mul one level down", 1, he_mul(&x[1], &x[0], &x[1], &keys[0]), r_he_mul(&y[1], &y[0], &y[1], &keys[0]));
+  BOTH("he_rs one level down", 1, he_rs(&x[1]), r_he_rs(&y[1]));
+#undef BOTH
+  if (with_lib && have) printf("ref ok: %u calls equal to the reference (logn %u, q = 2^%u, Delta = 2^%u, L %u, dim %u, dimevk %u)\n", calls, logn, logq, logDelta, hx->L, hx->dim, hx->dimevk);
+  else printf("%s alone: %u calls, digests above\n", with_lib ? "library" : "reference", calls);
+  return 0;
+}
+
 /* hectx_init / polyctx_init / poly_*_alloc of the library (weak definitions), printed field by field for the Python side to compare
  * with the restated formulas (src/precomp.c:266-293, :328-450) and with the dims SURVEY.md 8c captured from the reference */
 static int ctxcheck(unsigned logn, unsigned logq, unsigned long long Delta)
@@ -930,6 +1078,8 @@ static int ctxcheck(unsigned logn, unsigned logq, unsigned long long Delta)
 
 int main(int argc, char **argv)
 {
+  if (argc >= 7 && (!strcmp(argv[1], "ref") || !strcmp(argv[1], "refonly")))
+    return refmode(argv[2], !strcmp(argv[1], "ref"), atoi(argv[3]), atoi(argv[4]), atoi(argv[5]), strtoull(argv[6], NULL, 10));
   if (argc >= 5 && !strcmp(argv[1], "ctxcheck")) return ctxcheck(atoi(argv[2]), atoi(argv[3]), strtoull(argv[4], NULL, 10));
   if (argc >= 2 && !strcmp(argv[1], "polymul")) return polymul(0);
   if (argc >= 2 && !strcmp(argv[1], "polymulodd")) return polymul(1);

@@ -34,23 +34,9 @@ def _dimpt(logql, logn):
 
 
 def _ref_gemv(o, ct, diags, keys, slots, dimP, dimB, dimpt, logql):
-    ql = 1 << logql
-    n1, n2 = gemv_steps(slots)
-
-    def rot(c, r):
-        return ref.he_swk(o, ref.poly_rot(c[0], r), ref.poly_rot(c[1], r), *keys[r], dimP, dimB, logql)
-
-    baby = [rot(ct, j) for j in range(n1)]      # the reference rotates ct again in every giant step: the same values
-    outer = None
-    for i in range(n2):
-        inner = None
-        for j in range(n1):
-            prod = ref.he_mulpt(o, baby[j], diags[i * n1 + j], dimpt, logql)
-            inner = prod if inner is None else ref.he_add(inner, prod, ql)
-        g = rot(inner, i * n1)
-        outer = g if outer is None else ref.he_add(outer, g, ql)
-    qd = 1 << (logql - LOGDELTA)
-    return [[ref.mpi_smod(ref.mpi_rdiv(x, 1 << LOGDELTA), qd) for x in c] for c in outer]   # src/he-rescale.c:36-50
+    """the loop itself lives in oracle/bigint_ref.py, where tests/test_ref_functions.py pins it to the executed reference's he_gemv"""
+    assert ref.gemv_steps(slots) == gemv_steps(slots)
+    return ref.ref_gemv(o, ct, diags, keys, slots, dimP, dimB, dimpt, logql, LOGDELTA)
 
 
 @pytest.mark.parametrize("logn,slots,batch,sparse", [(10, 1, 2, True), (10, 2, 1, False), (12, 4, 1, True), (10, 8, 2, False),

@@ -85,7 +85,7 @@ def test_reduce_edge_cases(oracle_ctx):
 
 def test_golden_fixture_is_a_faithful_transcription_of_the_survey(golden):
     """tests/golden/survey_8c.json carries the values SURVEY.md section 8c recorded from the compiled reference
-    (the reference cannot be rebuilt here: no <gcrypt.h>).  The fixture names, per entry, the SURVEY.md line its values
+    (tests/test_ref_limbs.py regenerates them from the reference built by `make -C oracle ref`).  The fixture names, per entry, the SURVEY.md line its values
     were taken from (`_survey_rows`); every number and digest must stand ON that line -- location, not mere occurrence --
     so the pin is the survey's capture of the reference's output and not something re-derived from our own code."""
     import os
