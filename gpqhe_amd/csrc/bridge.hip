@@ -163,6 +163,13 @@ int get_relin(gpq_ctx *c, unsigned dimP, unsigned dimB, gpq_relin_tables **out) 
 // stage, ntt_kernels.hpp gs_last) -- multiplied by (P/p_d)^-1 mod p_d for the limbs d of basis b: an inverse transform that reads it
 // hands out y_d = ahat_d * phat_invmp_d, the first product of rns_reconstruct (src/rns.c:66-68), for free -- one modular multiply
 // and a canonicalisation per (coefficient, limb) less in the CRT kernels that follow (`prescaled`).  Limbs outside the basis keep n^-1.
+// The scaled constants are NEW split pairs that gs_last of the wide class reads with multiplicands up to 8p - 1: they pass the same check as
+// every other entry of a wide limb (engine.hip: upload_tables).  Returns the first limb below nwide_max whose pair fails, or ~0u.
+static unsigned first_unfit_wide_limb(const gpq_ctx *c, const std::vector<LimbTab> &t, unsigned first, unsigned count) {
+  for (unsigned d = first; d < first + count && d < c->nwide_max; ++d)
+    if (!split_entry_fits_wide(t[d].k.p, t[d].ninv_s.x, t[d].ninv_s.y) || !split_entry_fits_wide(t[d].k.p, t[d].winv1_ninv_s.x, t[d].winv1_ninv_s.y)) return d;
+  return ~0u;
+}
 int get_scaled_tabs(gpq_ctx *c, gpq_bridge_basis *b, const LimbTab **out) {
   if (!b->d_tabs_scaled) {
     std::vector<LimbTab> t = c->h_tabs;
@@ -174,17 +181,29 @@ int get_scaled_tabs(gpq_ctx *c, gpq_bridge_basis *b, const LimbTab **out) {
       e.winv1_ninv = (uint64_t)((u128h)e.winv1_ninv * s % p);
       if (b->first + d < c->nsplit_tables) { e.ninv_s = pair_of(e.ninv, p); e.winv1_ninv_s = pair_of(e.winv1_ninv, p); }
     }
+    const unsigned unfit = first_unfit_wide_limb(c, t, b->first, b->dim);
     DeviceScope on_device(c->device);
     HIP_TRY(gpq_table_malloc(c, (void **)&b->d_tabs_scaled, t.size() * sizeof(LimbTab)));
     HIP_TRY(hipMemcpy(b->d_tabs_scaled, t.data(), t.size() * sizeof(LimbTab), hipMemcpyHostToDevice));
+    if (unfit != ~0u) c->cache->scaled_wide_limit[b->d_tabs_scaled] = unfit;
   }
   *out = b->d_tabs_scaled;
   return GPQ_OK;
 }
-// for the duration of one gpq_he_mul_tensor / gpq_keyswitch call
+// for the duration of one gpq_he_mul_tensor / gpq_keyswitch call.  A table with a pair that does not fit the wide class ends the context's
+// wide range at that limb, for good (the calls between which this happens hand over canonical residues: any class reads them).
 struct ScaledInverse {
   gpq_ctx *c;
-  ScaledInverse(gpq_ctx *ctx, const LimbTab *tabs) : c(ctx) { c->inv_tabs_override = tabs; }
+  ScaledInverse(gpq_ctx *ctx, const LimbTab *tabs) : c(ctx) {
+    c->inv_tabs_override = tabs;
+    if (tabs && c->cache && !c->cache->scaled_wide_limit.empty()) {
+      const auto it = c->cache->scaled_wide_limit.find(tabs);
+      if (it != c->cache->scaled_wide_limit.end()) {
+        if (c->nwide_max > it->second) c->nwide_max = it->second;
+        if (c->nwide > it->second) c->nwide = it->second;
+      }
+    }
+  }
   ~ScaledInverse() { c->inv_tabs_override = nullptr; }
 };
 inline bool can_prescale(const gpq_ctx *c) { return c->prescale && c->logn > 12 && !c->h_tabs.empty(); }   // the two-pass transforms only (small rings: gpq_invntt)
@@ -949,6 +968,8 @@ int get_relin_front(gpq_ctx *c, unsigned dimP, unsigned dimB, gpq_relin_tables *
     HIP_TRY(hipMemcpy(rt->d_pk_w, pkw.data(), pkw.size() * 8, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(rt->d_tkp_w, tkpw.data(), tkpw.size() * 8, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(rt->d_tabs_w, tw.data(), tw.size() * sizeof(LimbTab), hipMemcpyHostToDevice));
+    const unsigned unfit = first_unfit_wide_limb(c, tw, 0, dimB);
+    if (unfit != ~0u) c->cache->scaled_wide_limit[rt->d_tabs_w] = unfit;
   }
   rt->NT = NT; rt->KS = KS; rt->lds_bytes = lds;
   return GPQ_OK;

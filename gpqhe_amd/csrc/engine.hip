@@ -192,9 +192,8 @@ static int upload_tables(gpq_ctx *c) {
     }
     LimbTab &t = tabs[d];
     t.k.p = p; t.k.p2 = 2 * p; t.k.p4 = 4 * p; t.k.c = (uint32_t)(p - (1ull << 59)); t.k.c1 = t.k.c + 1;
-    t.k.kx0 = t.k.c1; t.k.kx1 = (uint64_t)t.k.c1 - 4 * p; t.k.ky = 4 * p - 2 * (uint64_t)t.k.c1;
-    t.k.kys = 2 * p - 2 * (uint64_t)t.k.c1;
-    t.k.p3 = 3 * p; t.k.np3 = (uint64_t)0 - 3 * p; t.k.kx1x = (uint64_t)t.k.c1 - 3 * p; t.k.kyx = 3 * p - 2 * (uint64_t)t.k.c1;
+    t.k.kinj = 31 * (uint64_t)t.k.c - 1; t.k.one = 1;     // mulmod_split's injected K = 2^64 + 31c - 1 (modarith.hpp)
+    t.k.p3 = 3 * p; t.k.np3 = (uint64_t)0 - 3 * p;
     t.k.np = (uint64_t)0 - p; t.k.np2 = (uint64_t)0 - 2 * p; t.k.np4 = (uint64_t)0 - 4 * p;
     t.ninv = from_mont(c->ninv_mont[d]);
     t.winv1_ninv = n >= 2 ? mulm(wistd[d * n + 1], t.ninv, p) : t.ninv;
@@ -206,7 +205,7 @@ static int upload_tables(gpq_ctx *c) {
   // ... and among them the leading limbs whose forward stages may skip every other conditional subtraction (ct_bfly_wide)
   c->nwide = 0;
   while (c->nwide < c->nsplit && c->p[c->nwide] - (1ull << 59) < GPQ_WIDE_CMAX) ++c->nwide;
-  c->nsplit_tables = c->nsplit; c->nwide_max = c->nwide;
+  c->nsplit_tables = c->nsplit;
   c->low9 = c->logn == 17;            // n = 2^17: 8 strided stages over 512-coefficient rows + 9 low stages
   if (c->nsplit) {
     const size_t ns = c->nsplit;
@@ -220,12 +219,22 @@ static int upload_tables(gpq_ctx *c) {
       }
       tabs[d].ninv_s = pair_of(tabs[d].ninv, p);
       tabs[d].winv1_ninv_s = pair_of(tabs[d].winv1_ninv, p);
+      // the wide butterflies run multiplicands up to 8p - 1 through the injected multiply: every entry they read (index 0, the
+      // twiddle 1, is read by no stage) must keep th in 32 bits.  A limb with a failing entry ends the wide range: it and the
+      // limbs after it take the split class, whose multiplicands (< 6p) leave the margin for any entry.
+      if (d < c->nwide) {
+        bool ok = split_entry_fits_wide(p, tabs[d].ninv_s.x, tabs[d].ninv_s.y) && split_entry_fits_wide(p, tabs[d].winv1_ninv_s.x, tabs[d].winv1_ninv_s.y);
+        for (size_t i = 1; ok && i < n; ++i)
+          ok = split_entry_fits_wide(p, ws[d * n + i].x, ws[d * n + i].y) && split_entry_fits_wide(p, wis[d * n + i].x, wis[d * n + i].y);
+        if (!ok) c->nwide = (unsigned)d;
+      }
     }
     HIP_TRY(gpq_table_malloc(c, (void **)&c->d_ws, ns * n * sizeof(TwS)));
     HIP_TRY(gpq_table_malloc(c, (void **)&c->d_winvs, ns * n * sizeof(TwS)));
     HIP_TRY(hipMemcpy(c->d_ws, ws.data(), ns * n * sizeof(TwS), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(c->d_winvs, wis.data(), ns * n * sizeof(TwS), hipMemcpyHostToDevice));
   }
+  c->nwide_max = c->nwide;
   HIP_TRY(hipMemcpy(c->d_w, wstd.data(), np * n * 8, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(c->d_winv, wistd.data(), np * n * 8, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(c->d_tabs, tabs.data(), np * sizeof(LimbTab), hipMemcpyHostToDevice));
@@ -1116,6 +1125,12 @@ extern "C" int gpq_set_limb_classes(gpq_ctx *c, unsigned wide, unsigned split) {
   c->nwide = wide < c->nwide_max ? wide : c->nwide_max;
   if (c->nwide > c->nsplit) c->nwide = c->nsplit;
   return GPQ_OK;
+}
+
+// Tests: the table check of the wide class (modarith.hpp: split_entry_fits_wide) on one entry.  Host code only; needs no device.
+extern "C" int gpq_debug_split_entry_fits_wide(uint64_t p, uint64_t x, uint64_t y) {
+  if (p <= (1ull << 59) || p - (1ull << 59) >= GPQ_WIDE_CMAX || x > p || y > p) return -1;
+  return split_entry_fits_wide(p, x, y) ? 1 : 0;
 }
 
 extern "C" int gpq_set_limb_block(gpq_ctx *c, unsigned limbs) {

@@ -84,6 +84,10 @@ struct gpq_table_cache {
   std::map<std::pair<unsigned, unsigned>, gpq_relin_tables> relins;  // by (dimP, dimB)
   std::map<std::pair<std::pair<unsigned, unsigned>, unsigned>, gpq_decomp_mfma> decomps;  // by ((first limb, limbs), W)
   size_t device_bytes = 0;            // read-only device memory behind this cache and the transform tables (gpq_table_malloc)
+  // Scaled per-limb tables (ScaledInverse, bridge.hip) one of whose split pairs fails the wide class's table check (modarith.hpp:
+  // split_entry_fits_wide), with the first such limb: a context that reads the table runs that limb and those after it in the split class.
+  // Empty for every chain met so far (the failing constants are ~100 values in 2^59).
+  std::map<const gpq::LimbTab *, unsigned> scaled_wide_limit;
 };
 
 struct gpq_ctx {

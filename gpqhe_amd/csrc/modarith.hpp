@@ -11,12 +11,14 @@
 // of the product itself a modular multiply is 7 v_mad_u64_u32.
 //
 // Lazy ranges (Harvey-style), all values unsigned 64-bit:
-//   mulmod_lazy(a, w): a < 8p, w < p   ->  result in (0, 4p), == a*w (mod p)
+//   mulmod_lazy(a, w): a < 8p, w < p   ->  result in [0, 3.42p), == a*w (mod p)
 //   butterflies keep data in [0, 8p) (forward) / [0, 4p) (inverse)
 // Bounds hold for c < GPQ_FOLD_CMAX (checked at context creation):
-//   x = a*w < 8p^2, xh = x>>59 < 8p(1+c/2^59) < 2^62.01
+//   x = a*w + (c+1) < 8p^2, xh = x>>59 < 8p(1+c/2^59) < 2^62.01
 //   t = c*xh < 2^90.3, th = t>>59 < 2^31.3 (fits 32 bits), u = c*th < 8c^2(1+eps) < 2^59.5
-//   r = xl + u + p - tl  in (p-2^59, 2^59 + 2^59.5 + p)  subset (0, 3.42p)
+//   r = xl + u + (2^59-1-tl)  in [0, 2^59 + 2^59.5 + 2^59)  subset [0, 3.42p)
+// The multiplies return a value CONGRUENT to the product: the (c+1) that the complement trick leaves over (-tl = 2^59-1-tl + 1 - 2^59
+// and -2^59 == c) is cancelled by a constant that rides in a mad addend which was zero (mulmod_raw_t: m00; mulmod_split: see there).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -29,10 +31,12 @@
 // Forward butterflies that skip every other conditional subtraction (ct_bfly_wide below) need c < 2^27.
 #define GPQ_WIDE_CMAX 134217000u
 // The margins of the split class are narrow (0.25 % and 2.5 %): raising GPQ_SPLIT_CMAX must fail here, not in a product.
-//   7 * 2^29 * c < 2^60   one fold finishes: a multiplicand < 6p has th <= 3.5 * 2^30 and t = c*th + 2^59 + (c+1) stays below 3p
+//   (7 * 2^29 + 33) * c < 2^60   one fold finishes: a multiplicand < 6p has th <= 3.5 * 2^30 + 33 (the injected constant, mulmod_split) and
+//                                t = c*th + 2^59 - 1 stays below 3p
 //   12 * c < 2^32         variable * variable products of the middle kernels, left < 2p, right < 6p (TwTraits<TwS>): the 7-mad fold's th fits 32 bits
 //   12 * c^2 < 2^60       ... and such a product leaves below 4p (tests/test_lazy_ranges.py: the integer model of all three)
-static_assert(7ull * (1ull << 29) * GPQ_SPLIT_CMAX < (1ull << 60), "GPQ_SPLIT_CMAX: the single fold of mulmod_split no longer finishes below 3p");
+static_assert((7ull * (1ull << 29) + 33) * GPQ_SPLIT_CMAX < (1ull << 60), "GPQ_SPLIT_CMAX: the single fold of mulmod_split no longer finishes below 3p");
+static_assert(31ull * GPQ_SPLIT_CMAX < (1ull << 33) + (1ull << 32), "GPQ_SPLIT_CMAX: the low column of mulmod_split (two 31 x 32 products + 31c - 1) no longer fits 64 bits");
 static_assert(12ull * GPQ_SPLIT_CMAX < (1ull << 32), "GPQ_SPLIT_CMAX: th of mulmod_lazy(left < 2p, right < 6p) no longer fits 32 bits");
 static_assert(12ull * GPQ_SPLIT_CMAX * GPQ_SPLIT_CMAX < (1ull << 60), "GPQ_SPLIT_CMAX: a product of the split class no longer leaves below 4p");
 static_assert(GPQ_WIDE_CMAX <= (1u << 27) && GPQ_WIDE_CMAX <= GPQ_SPLIT_CMAX && GPQ_SPLIT_CMAX <= GPQ_FOLD_CMAX, "butterfly classes must nest: wide <= split <= 7-mad");
@@ -48,15 +52,27 @@ typedef unsigned __int128 u128;
 struct PrimeK {        // per-limb constants handed to kernels (uniform per block)
   uint64_t p;          // modulus
   uint64_t p2, p4;     // 2p, 4p
-  uint64_t kx0, kx1;   // c+1 and c+1-4p (mod 2^64): the two addends of the CT x-leg select
-  uint64_t ky;         // 4p - 2(c+1)
-  uint64_t kys;        // wide-split forward butterflies: 2p - 2(c+1)
   uint64_t p3, np3;    // 3p and -3p (mod 2^64): the split class subtracts 3p (forward data < 6p, inverse data < 3p)
-  uint64_t kx1x, kyx;  // split-twiddle forward butterflies: c+1-3p (mod 2^64) and 3p - 2(c+1)
   uint64_t np, np2, np4;  // -p, -2p, -4p (mod 2^64): a conditional subtraction is an ADD of one of these or of zero (csub1/2/4)
+  uint64_t kinj;       // 31c - 1: low part of the constant mulmod_split injects (K = 2^64 + 31c - 1 == -(c+1) mod p)
   uint32_t c;          // p - 2^59
-  uint32_t c1;         // c + 1
+  uint32_t c1;         // c + 1: what mulmod_raw_t injects
+  uint32_t one;        // 1: the high dword of K's carry word; the kernels keep it in one VGPR (pin_consts)
 };
+
+// The 1 in the high dword of mulmod_split's carry word has to sit in a VGPR next to the carry.  As a literal or a table scalar the
+// compiler re-materialises it with a v_mov per multiply (what the removed 64-bit add cost, back again); pinned once at kernel entry
+// it is an opaque value in ONE VGPR that every multiply of the kernel shares, as they shared the zero register.  (31c - 1, the other
+// injected word, needs no such care: the compiler keeps it in a register pair of its own where a mad cannot read it as a scalar.)
+// Plain asm, not volatile: a volatile one counts as a possible store, and every uniform table read behind it -- the twiddles of a
+// grid-uniform group, the LimbTab -- turns from a scalar load into a vector load (+70 VGPRs in the strided passes).
+__device__ __forceinline__ PrimeK pin_consts(const PrimeK &src) {
+  PrimeK k = src;
+  uint32_t one = 1;
+  asm("" : "+v"(one));
+  k.one = one;
+  return k;
+}
 
 __device__ __forceinline__ uint64_t mad_u64(uint32_t a, uint32_t b, uint64_t acc) {
   return (uint64_t)a * b + acc;  // v_mad_u64_u32
@@ -71,16 +87,17 @@ __device__ __forceinline__ uint64_t pack64(uint32_t lo, uint32_t hi) { return ((
 // move issues like a 64-bit operation.
 __device__ __forceinline__ uint32_t not_low27(uint32_t x) { return __builtin_amdgcn_bitop3_b32(x, 0x7ffffffu, x, 0x0c); }
 
-// Core of the modular multiply: returns T' with  a*w == T' + (c+1)  (mod p).
-//   x = a*w by 32-bit pieces (a < 2^62.1, w < 2^60: the middle column cannot overflow),
+// Core of the modular multiply: returns T' == a*w (mod p), T' in [0, 3.42p).
+//   x = a*w + (c+1) by 32-bit pieces (a < 2^62.1, w < 2^60: the middle column cannot overflow; the c+1 is the addend of the
+//   first mad, (2^32-1)^2 + c + 1 < 2^64),
 //   xh = x >> 59, xl = x mod 2^59, t = c*xh, th = t >> 59, tl = t mod 2^59,
-//   x == xl - t == xl + c*th - tl == xl + c*th + (2^59-1-tl) + (c+1) - p.
+//   x == xl - t == xl + c*th - tl == xl + c*th + (2^59-1-tl) + (c+1) - p,   so   T' = xl + c*th + (2^59-1-tl) == x - (c+1) = a*w.
 // The complement 2^59-1-tl is two bit operations where -tl would be a 64-bit subtract.
-// T' < 2^59 + 2^59 + 2^59.5 < 3.42p - (c+1).
+// T' < 2^59 + 2^59.5 + 2^59 < 3.42p.
 template <bool PIN>
 __device__ __forceinline__ uint64_t mulmod_raw_t(uint64_t a, uint64_t w, const PrimeK &k) {
   const uint32_t a0 = (uint32_t)a, a1 = (uint32_t)(a >> 32), w0 = (uint32_t)w, w1 = (uint32_t)(w >> 32);
-  const uint64_t m00 = mad_u64(a0, w0, 0);
+  const uint64_t m00 = mad_u64(a0, w0, k.c1);
   uint64_t mid = mad_u64(a0, w1, (uint32_t)(m00 >> 32));
   // PIN keeps the carry inside the mad: stops hipcc re-associating it into a mad + 64-bit add.
   // Measured (profiles/r01): +5 % on forward butterflies, a loss on the inverse ones, hence per call site.
@@ -107,10 +124,8 @@ __device__ __forceinline__ uint64_t mulmod_raw_t(uint64_t a, uint64_t w, const P
 #endif
 __device__ __forceinline__ uint64_t mulmod_raw(uint64_t a, uint64_t w, const PrimeK &k) { return mulmod_raw_t<false>(a, w, k); }
 
-// a*w mod p, lazily reduced: a < 8p, w < p -> (0, 4p)
-__device__ __forceinline__ uint64_t mulmod_lazy(uint64_t a, uint64_t w, const PrimeK &k) {
-  return mulmod_raw(a, w, k) + k.c1;
-}
+// a*w mod p, lazily reduced: a < 8p, w < p -> [0, 3.42p)
+__device__ __forceinline__ uint64_t mulmod_lazy(uint64_t a, uint64_t w, const PrimeK &k) { return mulmod_raw(a, w, k); }
 
 // x - m if x >= m else x, for m = p, 2p, 4p: compare, select the addend (-m or 0), one 64-bit add = 4 VALU instructions.
 // Written as `x >= m ? x - m : x` (or with `0 - m` the compiler can see through) it becomes compare, select, v_sub_co,
@@ -131,14 +146,13 @@ __device__ __forceinline__ uint64_t canon4(uint64_t x, const PrimeK &k) {
 }
 
 // Cooley-Tukey butterfly of src/ntt.c:45-49 in lazy form.
-// in: x,y < 8p ; out: x,y < 8p.  With t = T' + (c+1) and xr = csub(x, 4p):
-//   x' = xr + t = xs + T',  y' = xr + 4p - t = xs + (4p - 2(c+1)) - T',  xs = xr + (c+1)
-// so the (c+1) rides on the constant the conditional subtract selects anyway.
+// in: x,y < 8p ; out: x,y < 8p.  With t = y*w in [0, 3.42p) and xs = csub(x, 4p) < 4p:
+//   x' = xs + t < 8p,  y' = xs + 4p - t in (0, 8p).
 __device__ __forceinline__ void ct_bfly(uint64_t &x, uint64_t &y, uint64_t w, const PrimeK &k) {
   const uint64_t t = mulmod_raw_t<GPQ_PIN_CT>(y, w, k);
-  const uint64_t xs = x + (x >= k.p4 ? k.kx1 : k.kx0);
+  const uint64_t xs = csub4(x, k);
   x = xs + t;
-  y = xs + k.ky - t;
+  y = xs + k.p4 - t;
 }
 
 // Gentleman-Sande butterfly of src/ntt.c:63-68 in lazy form.
@@ -147,7 +161,7 @@ __device__ __forceinline__ void gs_bfly(uint64_t &x, uint64_t &y, uint64_t w, co
   const uint64_t v = x + y;
   const uint64_t d = x + k.p4 - y;  // (0, 8p)
   x = csub4(v, k);
-  y = mulmod_raw_t<GPQ_PIN_GS>(d, w, k) + k.c1;
+  y = mulmod_raw_t<GPQ_PIN_GS>(d, w, k);
 }
 
 // ---------------------------------------------------------------------------
@@ -156,13 +170,22 @@ __device__ __forceinline__ void gs_bfly(uint64_t &x, uint64_t &y, uint64_t w, co
 //   a*w == al*w + ah*w2  (mod p),   al < 2^31, ah <= 2^30 for a < 4p
 // is a 92-bit sum of two 32x60 products (4 mads, the column carries ride in the mad
 // addends) whose part above 2^59 fits 32 bits: ONE fold by c finishes.  5 v_mad_u64_u32
-// instead of 7 and no 128-bit shift.  Both constants are stored negated (p-w, p-w2), so
-//   a*w == -(tl + 2^59*th) == c*th - tl == c*th + (2^59-1-tl) + (c+1) - p
-// and the subtraction is again a complement.  Returns T' with a*w == T' + (c+1) (mod p).
-// For a multiplicand a < 6p:  ah <= 3*2^29,  th <= 3.5*2^30,  T' <= c*th + 2^59 - 1 < 3p - (c+1)   for c < GPQ_SPLIT_CMAX,
-// so t = T' + (c+1) < 3p and the ranges [0, 6p) forward / [0, 3p) inverse close with ONE conditional subtraction (of 3p) per
+// instead of 7 and no 128-bit shift.  Both constants are stored negated (X = p-w, Y = p-w2), and the sum carries a constant:
+//   t = al*X + ah*Y + K,   K = 2^64 + 31c - 1 == -(c+1) (mod p)      (2^64 = 32 * 2^59 == -32c),
+//   a*w + (c+1) == -t == -(tl + 2^59*th) == c*th - tl == c*th + (2^59-1-tl) + (c+1) - p
+// so the subtraction is again a complement and T' = c*th + (2^59-1-tl) == a*w (mod p) with no correction left over.  K costs no
+// instruction: 31c - 1 is the addend of the first mad of the low column (zero before), and the 2^64 is a 1 in the high dword of the
+// carry word handed to the high column (zero before), out of a VGPR that the whole kernel shares (PrimeK::one, pin_consts).
+// K raises th by at most 33.  For a multiplicand a < 6p:  ah <= 3*2^29,  th <= 3.5*2^30 + 33,  T' <= c*th + 2^59 - 1 < 3p   for
+// c < GPQ_SPLIT_CMAX, so t = T' < 3p and the ranges [0, 6p) forward / [0, 3p) inverse close with ONE conditional subtraction (of 3p) per
 // butterfly:  forward  xr = x - [x >= 3p] 3p < 3p,  x' = xr + t < 6p,  y' = xr + 3p - t in (0, 6p);
 //             inverse  v = x + y < 6p,  x' = v - [v >= 3p] 3p < 3p,  d = x + 3p - y in (0, 6p),  y' = t < 3p.
+// The wide class (below) runs multiplicands up to 8p - 1, where th < 2^32 is no longer implied by the class: al*X + ah*Y <=
+// (2^32 - 2) p < 2^91 - 2^60 leaves less room than K takes when BOTH X and Y are within ~2^33 of p, i.e. for the few w with
+// w + (w*2^31 mod p) < 2c + 15 * 2^29: w = q 2^28 + j with j = 1, 2, 3 and q (2^28 - c) < (15 - 4j) 2^29 + 2c, i.e. q from 0 up to 22..44, 14..28, 6..12
+// by c (w*2^31 = q p + j 2^31 - q c): some hundred values in 2^59, no root of unity of a real chain.  split_entry_fits_wide is the exact bound; the host checks every pair a
+// wide limb reads with it -- the twiddle tables and the last stage's constants (engine.hip: upload_tables), and the scaled copies of those
+// constants the bridge builds (bridge.hip: first_unfit_wide_limb) -- and a limb with a failing pair leaves the wide class.
 // (tests/test_lazy_ranges.py is the integer model; measured in tools/bfly_lab at the 4p / 2p ranges: +20 % CT, +27 % GS over the 7-mad form.)
 // ---------------------------------------------------------------------------
 typedef ulonglong2 TwS;   // .x = p - w, .y = p - (w*2^31 mod p)
@@ -174,12 +197,12 @@ template <typename W>
 __device__ __forceinline__ uint64_t mulmod_split(uint64_t a, const W &w, const PrimeK &k) {
   const uint32_t al = (uint32_t)a & 0x7fffffffu;
   const uint32_t ah = __builtin_amdgcn_alignbit((uint32_t)(a >> 32), (uint32_t)a, 31);
-  uint64_t t0 = mad_u64(al, (uint32_t)w.x, 0);
-  t0 = mad_u64(ah, (uint32_t)w.y, t0);                         // < 2^63 + 2^63 - ... : al < 2^31, ah < 2^31 (a < 8p), constants < 2^32
+  uint64_t t0 = mad_u64(al, (uint32_t)w.x, k.kinj);
+  t0 = mad_u64(ah, (uint32_t)w.y, t0);                         // <= 2^64 - 2^33 - 2^32 + 2 + (31c - 1): al < 2^31, ah <= 2^31 (a < 8p, and al <= 8c when ah = 2^31), constants < 2^32
   asm GPQ_PIN_VOLATILE("" : "+v"(t0));                                 // keep the carries inside the mads (see mulmod_raw_t)
-  uint64_t t1 = mad_u64(al, (uint32_t)(w.x >> 32), (uint32_t)(t0 >> 32));
+  uint64_t t1 = mad_u64(al, (uint32_t)(w.x >> 32), pack64((uint32_t)(t0 >> 32), k.one));   // + 2^32 here = + 2^64 in t
   asm GPQ_PIN_VOLATILE("" : "+v"(t1));
-  t1 = mad_u64(ah, (uint32_t)(w.y >> 32), t1);                 // sum >> 32, < 0.75p
+  t1 = mad_u64(ah, (uint32_t)(w.y >> 32), t1);                 // t >> 32, < 2^59: th = t >> 59 fits 32 bits (split class: by c; wide class: by the table check)
   const uint32_t t1lo = (uint32_t)t1, t1hi = (uint32_t)(t1 >> 32);
   const uint32_t th = __builtin_amdgcn_alignbit(t1hi, t1lo, 27);
   const uint64_t ntl = pack64(~(uint32_t)t0, not_low27(t1lo));  // 2^59 - 1 - tl
@@ -189,9 +212,9 @@ __device__ __forceinline__ uint64_t mulmod_split(uint64_t a, const W &w, const P
 // Cooley-Tukey, split twiddle.  in: x,y < 6p ; out: x,y < 6p.
 __device__ __forceinline__ void ct_bfly(uint64_t &x, uint64_t &y, const TwS &w, const PrimeK &k) {
   const uint64_t t = mulmod_split(y, w, k);
-  const uint64_t xs = x + (x >= k.p3 ? k.kx1x : k.kx0);
+  const uint64_t xs = csub3(x, k);
   x = xs + t;
-  y = xs + k.kyx - t;
+  y = xs + k.p3 - t;
 }
 // Gentleman-Sande, split twiddle.  in: x,y < 3p ; out: x,y < 3p.
 template <typename W>
@@ -199,13 +222,13 @@ __device__ __forceinline__ void gs_bfly_split(uint64_t &x, uint64_t &y, const W 
   const uint64_t v = x + y;
   const uint64_t d = x + k.p3 - y;  // (0, 6p)
   x = csub3(v, k);
-  y = mulmod_split(d, w, k) + k.c1;
+  y = mulmod_split(d, w, k);
 }
 __device__ __forceinline__ void gs_bfly(uint64_t &x, uint64_t &y, const TwS &w, const PrimeK &k) { gs_bfly_split(x, y, w, k); }
 
 // Gentleman-Sande for the wide class (c < GPQ_WIDE_CMAX): inverse data lives in [0, 4p) instead of [0, 2p).
 //   v = x + y < 8p;   d = x + 4p - y in (0, 8p): a legal multiplicand (8p - 1 = 2^62 + 8c - 1 <= 2^62 + 2^31 - 2 for c < 2^27),
-//   so the product leg y' = T' + (c+1) < 2p as in ct_bfly_wide;   sum leg x' = v - [v >= 4p] 4p < 4p.
+//   so the product leg y' = T' < 2p as in ct_bfly_wide;   sum leg x' = v - [v >= 4p] 4p < 4p.
 // What the wider range buys: a butterfly whose two inputs are BOTH product legs of the stage before (each < 2p) has
 // v < 4p already and needs no conditional subtraction (CSUB = false).  Inside a register group that is known at compile time
 // -- the pair (e, e + 2^B) of stage B shares bit B-1, and bit B-1 set means "product leg of the previous stage" -- so half
@@ -216,26 +239,36 @@ __device__ __forceinline__ void gs_bfly_wide(uint64_t &x, uint64_t &y, const TwW
   const uint64_t v = x + y;
   const uint64_t d = x + k.p4 - y;
   x = CSUB ? csub4(v, k) : v;
-  y = mulmod_split(d, w, k) + k.c1;
+  y = mulmod_split(d, w, k);
 }
 __device__ __forceinline__ void gs_bfly(uint64_t &x, uint64_t &y, const TwW &w, const PrimeK &k) { gs_bfly_wide<true>(x, y, w, k); }
 
 // Cooley-Tukey, split twiddle, one conditional subtraction per TWO stages (c < GPQ_WIDE_CMAX <= 2^27).
-// The split multiply only needs th < 2^32, i.e. al + ah <= 2^32 - 2, which holds for every multiplicand
-// a <= 2^62 + 2^31 - 2 (above 2^62 the low part al is what exceeds 2^62: small), and then
-//   t = T' + (c+1) <= c (2^32 - 2) + 2^59 + c < 2p          for c <= 2^27.
+// The split multiply only needs th < 2^32: al + ah <= 2^32 - 2 holds for every multiplicand a <= 2^62 + 2^31 - 2 (above 2^62 the
+// low part al is what exceeds 2^62: small), the table check (split_entry_fits_wide) covers the injected constant, and then
+//   t = T' <= c (2^32 - 1) + 2^59 - 1 < 2p          for c <= 2^27.
 // Stage kinds alternate by the position s of the index bit a stage works on (len = 2^s):
-//   s odd  "A": no subtraction.   in: x, y < 6p          out: x' = x + t < 8p,  y' = x + 2p - t <= 8p - c - 2
-//   s even "B": subtract 4p.      in: x, y < 8p          out: x' = xr + t < 6p, y' = xr + 2p - t < 6p     (xr = csub(x, 4p) < 4p)
-// 8p - c - 2 = 2^62 + 7c - 2 is a legal multiplicand (7c < 2^31).  Two A stages never follow each other; the
+//   s odd  "A": no subtraction.   in: x, y < 6p          out: x' = x + t < 8p,  y' = x + 2p - t in (0, 8p)
+//   s even "B": subtract 4p.      in: x, y < 8p          out: x' = xr + t < 6p, y' = xr + 2p - t in (0, 6p)     (xr = csub(x, 4p) < 4p)
+// 8p - 1 = 2^62 + 8c - 1 is a legal multiplicand (8c <= 2^30).  Two A stages never follow each other; the
 // last stage (s = 0) is B, so a finished forward transform is < 6p; canonical inputs may enter at either kind.
 // Measured (tools/bfly_lab): +8 % over a subtraction in every stage.
 template <bool CSUB>
 __device__ __forceinline__ void ct_bfly_wide(uint64_t &x, uint64_t &y, const TwW &w, const PrimeK &k) {
   const uint64_t t = mulmod_split(y, w, k);
-  const uint64_t xs = x + (CSUB ? (x >= k.p4 ? k.kx1 : k.kx0) : k.kx0);
+  const uint64_t xs = CSUB ? csub4(x, k) : x;
   x = xs + t;
-  y = xs + k.kys - t;
+  y = xs + k.p2 - t;
+}
+
+// Host side of the wide class's contract: does a table entry (X, Y) = (p - w, p - w*2^31 mod p) keep th = t >> 59 of mulmod_split in 32
+// bits for EVERY multiplicand the wide butterflies hand it (a <= 8p - 1: ct_bfly_wide, gs_bfly_wide, gs_last)?  Exact: with a = ah 2^31 + al
+// the sum al*X + ah*Y is largest either at the top multiplicand's ah (al <= its low part) or one below it with al = 2^31 - 1.
+inline bool split_entry_fits_wide(uint64_t p, uint64_t X, uint64_t Y) {
+  const uint64_t amax = 8 * p - 1, c = p - (1ull << 59);
+  const u128 ah = amax >> 31, al = amax & 0x7fffffffu, K = ((u128)1 << 64) + 31 * c - 1;
+  const u128 top = al * X + ah * Y, below = (u128)0x7fffffffu * X + (ah - 1) * Y;
+  return (top > below ? top : below) + K < ((u128)1 << 91);
 }
 
 // Exact a*b mod p for canonical a,b (poly_rns_mul, src/poly.c:77-82).

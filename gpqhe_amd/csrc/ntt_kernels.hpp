@@ -158,8 +158,8 @@ __device__ __forceinline__ void gs_last(uint64_t &x, uint64_t &y, const LastK<ui
 __device__ __forceinline__ void gs_last(uint64_t &x, uint64_t &y, const LastK<TwS> &t, const PrimeK &k) {   // in: x,y < 3p
   const uint64_t s = x + y;                 // < 6p
   const uint64_t d = x + k.p3 - y;          // (0, 6p)
-  x = canon4(mulmod_split(s, t.ninv, k) + k.c1, k);            // products < 3p
-  y = canon4(mulmod_split(d, t.winv1_ninv, k) + k.c1, k);
+  x = canon4(mulmod_split(s, t.ninv, k), k);            // products < 3p
+  y = canon4(mulmod_split(d, t.winv1_ninv, k), k);
 }
 
 // Per twiddle type: the table pointers of a launch and the lazy ranges the butterflies keep.
@@ -193,8 +193,8 @@ template <> struct LastK<TwW> : LastK<TwS> {      // the same two constants as t
 __device__ __forceinline__ void gs_last(uint64_t &x, uint64_t &y, const LastK<TwW> &t, const PrimeK &k) {   // in: x,y < 4p
   const uint64_t s = x + y;                 // < 8p: a legal multiplicand for the wide class (gs_bfly_wide)
   const uint64_t d = x + k.p4 - y;          // (0, 8p)
-  x = csub1(mulmod_split(s, t.ninv, k) + k.c1, k);
-  y = csub1(mulmod_split(d, t.winv1_ninv, k) + k.c1, k);
+  x = csub1(mulmod_split(s, t.ninv, k), k);                   // products < 2p
+  y = csub1(mulmod_split(d, t.winv1_ninv, k), k);
 }
 // Wide-split limbs: forward data < 6p after a finished transform (< 8p inside one), inverse data < 4p (gs_bfly_wide).
 template <> struct TwTraits<TwW> {
@@ -261,7 +261,7 @@ __global__ __launch_bounds__((StridedGeom<M1, EL>::T)) void strided_pass(PassArg
   }
   const unsigned limb = a.limb0 + bz;
   const LimbTab &tab = a.tabs[limb];
-  const PrimeK k = tab.k;
+  const PrimeK k = pin_consts(tab.k);
   const LastK<TW> last(tab);
   const TW *__restrict__ wt = TwTraits<TW>::table(a, INV) + ((size_t)limb << logn);
   const unsigned slab = by % a.nslab, poly = by / a.nslab;
@@ -440,7 +440,7 @@ __global__ __launch_bounds__(CONTIG_WAVES * 64, (sizeof(TW) == 8 ? 2 : GPQ_CONTI
   const unsigned wave0 = (blockIdx.x * CONTIG_WAVES + (threadIdx.x >> 6)) << 10;
   const unsigned limb = a.limb0 + blockIdx.z;
   const LimbTab &tab = a.tabs[limb];
-  const PrimeK k = tab.k;
+  const PrimeK k = pin_consts(tab.k);
   const unsigned p0 = blockIdx.y * CONTIG_POLYS;
   const unsigned cnt = polys - p0 < CONTIG_POLYS ? polys - p0 : CONTIG_POLYS;
   const size_t off = (size_t)p0 * a.poly_stride + ((size_t)blockIdx.z << a.logn) + wave0;
@@ -693,7 +693,7 @@ __global__ __launch_bounds__(CONTIG_WAVES * 64, GPQ_MID8_MINWAVES) void tensor_m
   __shared__ uint64_t lds[CONTIG_WAVES * LANE8_LDS_PER_WAVE];
   L8 ln(lds + (threadIdx.x >> 6) * LANE8_LDS_PER_WAVE);
   const Block8 cb(a);
-  const PrimeK k = a.tabs[cb.limb].k;
+  const PrimeK k = pin_consts(a.tabs[cb.limb].k);
   const TW *__restrict__ wf = TT::table(a, false) + cb.toff, *__restrict__ wi = TT::table(a, true) + cb.toff;
   uint64_t a0[8], a1[8], b0[8], b1[8];
   Tw8<TW, LOW> tw;
@@ -754,7 +754,7 @@ __global__ __launch_bounds__(CONTIG_WAVES * 64, GPQ_MID8_MINWAVES) void tensor_s
   __shared__ uint64_t lds[CONTIG_WAVES * LANE8_LDS_PER_WAVE];
   L8 ln(lds + (threadIdx.x >> 6) * LANE8_LDS_PER_WAVE);
   const Block8 cb(a);
-  const PrimeK k = a.tabs[cb.limb].k;
+  const PrimeK k = pin_consts(a.tabs[cb.limb].k);
   const TW *__restrict__ wf = TT::table(a, false) + cb.toff, *__restrict__ wi = TT::table(a, true) + cb.toff;
   uint64_t a0[8], a1[8];
   Tw8<TW, LOW> tw;
@@ -775,7 +775,7 @@ __global__ __launch_bounds__(CONTIG_WAVES * 64, GPQ_MID8_MINWAVES) void tensor_s
   for (int e = 0; e < 8; ++e) {                      // left operand < 2p or < 4p, right operand as it comes: the ranges of tensor_mid8
     const uint64_t u0 = TT::left(a0[e], k), u1 = TT::left(a1[e], k);
     const uint64_t v0 = TT::right(a0[e], k), v1 = TT::right(a1[e], k);
-    const uint64_t cross = mulmod_lazy(u0, v1, k);                                      // c0 c1, in (0, 4p)
+    const uint64_t cross = mulmod_lazy(u0, v1, k);                                      // c0 c1, in [0, 3.42p)
     a0[e] = TT::inv_from4(mulmod_lazy(u0, v0, k), k);                                   // d0
     d1[e] = TT::inv_from8(cross + cross, k);                                            // d1
     a1[e] = TT::inv_from4(mulmod_lazy(u1, v1, k), k);                                   // d2
@@ -806,7 +806,7 @@ __global__ __launch_bounds__(CONTIG_WAVES * 64, 4) void polymul_mid8(PassArgs a)
   __shared__ uint64_t lds[CONTIG_WAVES * LANE8_LDS_PER_WAVE];
   L8 ln(lds + (threadIdx.x >> 6) * LANE8_LDS_PER_WAVE);
   const Block8 cb(a);
-  const PrimeK k = a.tabs[cb.limb].k;
+  const PrimeK k = pin_consts(a.tabs[cb.limb].k);
   const TW *__restrict__ wf = TT::table(a, false) + cb.toff, *__restrict__ wi = TT::table(a, true) + cb.toff;
   uint64_t x[8], y[8];
   Tw8<TW, LOW> tw;
@@ -841,7 +841,7 @@ __global__ __launch_bounds__(CONTIG_WAVES * 64, 3) void mulpt_mid8(PassArgs a) {
   __shared__ uint64_t lds[CONTIG_WAVES * LANE8_LDS_PER_WAVE];
   L8 ln(lds + (threadIdx.x >> 6) * LANE8_LDS_PER_WAVE);
   const Block8 cb(a);
-  const PrimeK k = a.tabs[cb.limb].k;
+  const PrimeK k = pin_consts(a.tabs[cb.limb].k);
   const TW *__restrict__ wf = TT::table(a, false) + cb.toff, *__restrict__ wi = TT::table(a, true) + cb.toff;
   uint64_t m[8], x[8], y[8];
   Tw8<TW, LOW> tw;
@@ -883,8 +883,13 @@ __global__ __launch_bounds__(CONTIG_WAVES * 64, 3) void mulpt_mid8(PassArgs a) {
 // twiddle group are fetched once for both -- per polynomial the 16-per-lane kernel reads 960 B of twiddle pairs and 256 B
 // of key per lane against 384 B of its own data -- and the four products of a pair run like the tensor stage (2 forward
 // low-halves, 4 inverse ones).  blockIdx.y = pair of polynomials starting at `first`; an odd last polynomial runs alone in the TWO = false instantiation.
+// Register budget: the pair form is compiled for four waves per SIMD (<= 128 VGPRs).  At LOW = 8 its code object stood there anyway (126)
+// until the multiplies lost their trailing add; with the looser budget of three waves the scheduler then spreads to 168 registers and
+// spills 22 of them: 9 % slower with 7.7 % fewer instructions.  Stated, the budget gives 122 registers and no spill.  At LOW = 9 (135
+// before; 168 with 26 spilled on the wide limbs after) it gives 128 with 5 spilled, and the n = 2^17 key switch runs 3.4 % faster than
+// with three waves (profiles/r09/v1_n17_lib_ab.txt).
 template <typename TW, int LOW, bool TWO = true, bool NT = false>
-__global__ __launch_bounds__(CONTIG_WAVES * 64, 3) void keyswitch_mid8x2(KeyswitchArgs ka, unsigned first) {
+__global__ __launch_bounds__(CONTIG_WAVES * 64, TWO ? 4 : 3) void keyswitch_mid8x2(KeyswitchArgs ka, unsigned first) {
   using TT = TwTraits<TW>;
   using L8 = Lane8N<LOW, NT>;
   __shared__ uint64_t lds[CONTIG_WAVES * LANE8_LDS_PER_WAVE];
@@ -892,7 +897,7 @@ __global__ __launch_bounds__(CONTIG_WAVES * 64, 3) void keyswitch_mid8x2(Keyswit
   L8 ln(lds + (threadIdx.x >> 6) * LANE8_LDS_PER_WAVE);
   const unsigned wave0 = (blockIdx.x * CONTIG_WAVES + (threadIdx.x >> 6)) << 9;
   const unsigned limb = a.limb0 + blockIdx.z;
-  const PrimeK k = a.tabs[limb].k;
+  const PrimeK k = pin_consts(a.tabs[limb].k);
   const size_t toff = (size_t)limb << a.logn;
   const TW *__restrict__ wf = TT::table(a, false) + toff, *__restrict__ wi = TT::table(a, true) + toff;
   const unsigned p0 = first + 2 * blockIdx.y;  // TWO = false: the odd last polynomial of a batch (a single ciphertext is the reference's calling pattern) alone,
@@ -972,9 +977,11 @@ __device__ __forceinline__ unsigned automorphism_src(unsigned j, unsigned logn, 
 // keyswitch_mid8x2 for a rotated input that is already in the NTT domain: src[0] = the COMPLETE forward transform of the unrotated
 // decomposed c1 (shared by every rotation of a call); each wave reads the 512 words of its source tile (coalesced, H layout) into its LDS
 // region, takes its L-layout words through sigma from there, multiplies by the key and runs the inverse low stages.  dst[0..1] as in
-// keyswitch_mid8x2; the strided inverse pass follows.  Same pairing of polynomials, limb classes and cache policy.
+// keyswitch_mid8x2; the strided inverse pass follows.  Same pairing of polynomials, limb classes, cache policy and register budget (four waves
+// per SIMD for the pair form: at three, the split-class instantiation of LOW = 9 went from 148 VGPRs to 168 with 46 spilled once the
+// multiplies lost their trailing add; at four every instantiation holds 128 with 4-10 spilled).
 template <typename TW, int LOW, bool TWO = true, bool NT = false>
-__global__ __launch_bounds__(CONTIG_WAVES * 64, 3) void keyswitch_rot_mid8x2(KeyswitchArgs ka, unsigned first, unsigned g) {
+__global__ __launch_bounds__(CONTIG_WAVES * 64, TWO ? 4 : 3) void keyswitch_rot_mid8x2(KeyswitchArgs ka, unsigned first, unsigned g) {
   using TT = TwTraits<TW>;
   using L8 = Lane8N<LOW, NT>;
   __shared__ uint64_t lds[CONTIG_WAVES * LANE8_LDS_PER_WAVE];
@@ -982,7 +989,7 @@ __global__ __launch_bounds__(CONTIG_WAVES * 64, 3) void keyswitch_rot_mid8x2(Key
   L8 ln(lds + (threadIdx.x >> 6) * LANE8_LDS_PER_WAVE);
   const unsigned wave0 = (blockIdx.x * CONTIG_WAVES + (threadIdx.x >> 6)) << 9;
   const unsigned limb = a.limb0 + blockIdx.z;
-  const PrimeK k = a.tabs[limb].k;
+  const PrimeK k = pin_consts(a.tabs[limb].k);
   const size_t toff = (size_t)limb << a.logn;
   const TW *__restrict__ wi = TT::table(a, true) + toff;
   const unsigned p0 = first + 2 * blockIdx.y;
@@ -1067,7 +1074,7 @@ __global__ __launch_bounds__(256) void automorphism_gather(const uint64_t *__res
 // over the live terms of the step (terms[t] = (rotation slot in r0 / r1, diagonal of the plan): uniform, read with scalar loads).  r0 / r1 =
 // the complete forward transforms of the baby rotations, words in [0, p] (the reference's p-for-zero words included); diag = the plan's
 // diagonals, words in [0, p]; acc canonical.  The complete inverse transform follows (gpq_invntt).
-// Exactness, for ANY number of terms: a product is mulmod_lazy(u <= p, d <= p) in (0, 4p) (modarith.hpp: a < 8p, x = a w <= p^2 < 8p^2),
+// Exactness, for ANY number of terms: a product is mulmod_lazy(u <= p, d <= p) in [0, 3.42p) (modarith.hpp: a < 8p, x = a w <= p^2 < 8p^2),
 // the running sum enters a step below 4p, sum + product < 8p < 2^63 does not wrap, and one conditional subtraction of 4p brings it back
 // below 4p; canon4 at the end.  (tests/test_gemv_acc_dim.py is the integer model, at n1 = 511, the largest the reference can produce.)
 // Traffic: a workgroup keeps BT ciphertexts (2 BT polynomials, 16 bytes per lane each) in registers and reads every diagonal word ONCE for
@@ -1092,7 +1099,7 @@ __device__ __forceinline__ v2u64 gemv_ld16(const v2u64 *p) {
 }
 template <int BT, bool NT>
 __global__ __launch_bounds__(256) void gemv_mac(GemvMacArgs a) {
-  const PrimeK k = a.tabs[blockIdx.z].k;
+  const PrimeK k = pin_consts(a.tabs[blockIdx.z].k);
   const unsigned i2 = 2 * (blockIdx.y * 256 + threadIdx.x);
   if (i2 >= (1u << a.logn)) return;
   const unsigned b0 = blockIdx.x * BT, cnt = a.polys - b0 < (unsigned)BT ? a.polys - b0 : (unsigned)BT;   // b0 < polys by the grid
@@ -1134,7 +1141,7 @@ __global__ __launch_bounds__(CONTIG_WAVES * 64, 4) void contig_pass8(PassArgs a,
   L8 ln(lds + (threadIdx.x >> 6) * LANE8_LDS_PER_WAVE);
   const unsigned wave0 = (blockIdx.x * CONTIG_WAVES + (threadIdx.x >> 6)) << 9;
   const unsigned limb = a.limb0 + blockIdx.z;
-  const PrimeK k = a.tabs[limb].k;
+  const PrimeK k = pin_consts(a.tabs[limb].k);
   const unsigned p0 = blockIdx.y * CONTIG8_POLYS;
   const unsigned cnt = polys - p0 < CONTIG8_POLYS ? polys - p0 : CONTIG8_POLYS;
   const size_t off = (size_t)p0 * a.poly_stride + ((size_t)blockIdx.z << a.logn) + wave0;
@@ -1191,7 +1198,7 @@ __global__ __launch_bounds__(CONTIG_WAVES * 64, 4) void contig_pass8(PassArgs a,
 template <bool MUL>
 __global__ __launch_bounds__(256) void pointwise(PassArgs a) {
   const LimbTab &tab = a.tabs[a.limb0 + blockIdx.z];
-  const PrimeK k = tab.k;
+  const PrimeK k = pin_consts(tab.k);
   const unsigned i2 = 2 * (blockIdx.x * 256 + threadIdx.x);
   if (i2 >= (1u << a.logn)) return;
   const size_t off = (size_t)blockIdx.y * a.poly_stride + ((size_t)blockIdx.z << a.logn) + i2;
@@ -1215,7 +1222,7 @@ __global__ __launch_bounds__(256) void small_ntt(PassArgs a) {
   using TT = TwTraits<TW>;
   __shared__ uint64_t s[1 << SMALL_MAX_LOGN];
   const LimbTab &tab = a.tabs[a.limb0 + blockIdx.z];
-  const PrimeK k = tab.k;
+  const PrimeK k = pin_consts(tab.k);
   const LastK<TW> last(tab);
   const unsigned n = 1u << a.logn;
   const TW *__restrict__ wt = TT::table(a, INV) + ((size_t)(a.limb0 + blockIdx.z) << a.logn);
@@ -1279,7 +1286,7 @@ __device__ __forceinline__ uint64_t ref_fqmul(uint64_t a, uint64_t w, const Prim
 }
 template <bool INV>
 __device__ void ref_transform_limb(uint64_t *__restrict__ v, unsigned logn, const uint64_t *__restrict__ w, const LimbTab &tab) {
-  const PrimeK k = tab.k;
+  const PrimeK k = pin_consts(tab.k);
   const uint64_t q = k.p;
   const unsigned n = 1u << logn, half = n >> 1, T = blockDim.x;
   if (!INV) {

@@ -257,6 +257,11 @@ int gpq_set_lazy_decompose(gpq_ctx *ctx, int on);
 int gpq_set_nt_policy(gpq_ctx *ctx, int mode);
 /* Tests: the streaming kernels also flag every coefficient whose index is a multiple of `every` for the exact kernels behind them (0 = off). */
 int gpq_debug_force_redo(gpq_ctx *ctx, unsigned every);
+/* Tests (host only, no device needed): the check every split-twiddle pair (x, y) = (p - w, p - w 2^31 mod p) of a limb must pass before the limb
+ * may run the wide-split butterflies -- for every multiplicand up to 8p - 1 the 92-bit sum of the split multiply, with its injected constant
+ * 2^64 + 31c - 1, stays below 2^91.  1 = passes, 0 = fails (the limb and those after it take the split class), -1 = p is not a prime shape of
+ * the wide class (2^59 < p < 2^59 + GPQ_WIDE_CMAX) or x, y > p. */
+int gpq_debug_split_entry_fits_wide(uint64_t p, uint64_t x, uint64_t y);
 /* Tests: the zero watch of gpq_ntt (the reference stores p, not 0, at some positions of a forward transform, src/ntt.c:45-48; the forward
  * kernels flag every (polynomial, limb) whose output holds a residue 0 and a kernel that executes src/ntt.c as written redoes those limbs).
  * With the watch on, each launch group of gpq_ntt leaves a copy of its flag words as the forward kernels wrote them and a copy as the redo

@@ -1,0 +1,88 @@
+"""The butterflies with the (c+1) correction folded into mad addends (gpqhe_amd/csrc/modarith.hpp: mulmod_split, mulmod_raw_t)
+against the oracle, word for word: every butterfly class, the smallest two-pass ring and the nine-low-stage ring, an odd batch,
+and the inputs that sit on the edges of the lazy ranges -- all-zero, all p - 1, and polynomials whose transform holds
+residues 0 (a lazy value may now be 0 where it was p; canonical outputs, and the reference's stored p, must not move).
+The integer model of the same code is tests/test_inject_ranges.py."""
+import numpy as np
+import pytest
+
+import gpqhe_amd
+from gpqhe_amd import to_device, to_host
+from tests.zero_cases import limb_cases
+
+pytestmark = pytest.mark.gpu
+
+BATCH = 3      # odd: the key switch runs a pair of polynomials and then the single-polynomial instantiation
+# (logn, limbs, (wide, split)): logn 13 is the smallest two-pass ring, three limbs of each class inside one transform
+# (gpq_set_limb_classes as tests/test_ntt_gpu.py uses it: the first `wide` limbs wide-split, up to `split` split, the rest 7-mad);
+# logn 17 (nine low stages) with two limbs, both through each class in turn
+CASES = [(13, 9, (3, 6)), (17, 2, (2, 2)), (17, 2, (0, 2)), (17, 2, (0, 0))]
+
+_SHARED = {}
+
+
+def _inputs(o, logn, dim):
+    """Per ring, built once: slabs of BATCH polynomials.  `edge` = [zero residues in the transform, all-zero, all p - 1],
+    `mix` = [random, lower half of the transform zero, random]; `rnd` x 2; one key pair."""
+    if (logn, dim) in _SHARED:
+        return _SHARED[logn, dim]
+    n = o.n
+    rng = np.random.default_rng(1700 + logn)
+    cases = [dict(limb_cases(o, d, rng)) for d in range(dim)]
+    zeros = np.zeros(n, dtype=np.uint64)
+    scattered = np.concatenate([cases[d]["scattered zeros"] for d in range(dim)])
+    half = np.concatenate([cases[d]["lower half zero"] for d in range(dim)])
+    pmax = np.concatenate([np.full(n, o.p[d] - 1, dtype=np.uint64) for d in range(dim)])
+    edge = np.concatenate([scattered, np.tile(zeros, dim), pmax])
+    mix = np.concatenate([o.gen(31, dim), half, o.gen(32, dim)])
+    rnd = [np.concatenate([o.gen(40 + 10 * s + k, dim) for k in range(BATCH)]) for s in range(2)]
+    keys = [o.gen(7000, dim), o.gen(7001, dim)]
+    per = dim * n
+    exp = {"ntt": [o.ntt_slab(v, dim) for v in (edge, mix)], "invntt": [o.ntt_slab(v, dim, inverse=True) for v in (edge, mix)]}
+    quad = (edge, mix, rnd[0], rnd[1])
+    exp["tensor"] = [o.he_mul_tensor(*[v[k * per:(k + 1) * per].copy() for v in quad], dim) for k in range(BATCH)]
+    exp["square"] = [o.he_mul_tensor(*[v[k * per:(k + 1) * per].copy() for v in (edge, mix, edge, mix)], dim) for k in range(BATCH)]
+    exp["keyswitch"] = [[o.keyswitch(x[k * per:(k + 1) * per].copy(), keys[0], keys[1], dim) for k in range(BATCH)] for x in (edge, mix)]
+    _SHARED[logn, dim] = (edge, mix, rnd, keys, exp)
+    return _SHARED[logn, dim]
+
+
+@pytest.mark.parametrize("logn,dim,classes", CASES)
+def test_injected_butterflies_match_the_oracle(oracle_ctx, logn, dim, classes):
+    import torch
+    o = oracle_ctx(logn, dim)
+    edge, mix, rnd, keys, exp = _inputs(o, logn, dim)
+    g = gpqhe_amd.PolyContext(logn, dim)           # own context: the session-wide ones keep their classes
+    try:
+        assert g.p == o.p
+        g.set_limb_classes(*classes)
+        per = dim * o.n
+        for i, v in enumerate((edge, mix)):          # gpq_ntt, gpq_invntt
+            dev = to_device(v)
+            g.poly_ntt(dev, dim)
+            assert np.array_equal(to_host(dev), exp["ntt"][i]), "gpq_ntt, slab %d" % i
+            dev = to_device(v)
+            g.poly_invntt(dev, dim)
+            assert np.array_equal(to_host(dev), exp["invntt"][i]), "gpq_invntt, slab %d" % i
+        de, dm, r0, r1 = (to_device(v) for v in (edge, mix, rnd[0], rnd[1]))
+        outs = [torch.empty_like(de) for _ in range(3)]
+        g.he_mul_tensor(outs[0], outs[1], outs[2], de, dm, r0, r1, dim)          # gpq_he_mul_tensor: a general product
+        got = [to_host(t) for t in outs]
+        for k in range(BATCH):
+            for name, a, b in zip(("d0", "d1", "d2"), got, exp["tensor"][k]):
+                assert np.array_equal(a[k * per:(k + 1) * per], b), "tensor %s of ciphertext %d" % (name, k)
+        g.he_mul_tensor(outs[0], outs[1], outs[2], de, dm, de, dm, dim)          # ... and a squaring (aliased operands)
+        got = [to_host(t) for t in outs]
+        for k in range(BATCH):
+            for name, a, b in zip(("d0", "d1", "d2"), got, exp["square"][k]):
+                assert np.array_equal(a[k * per:(k + 1) * per], b), "squaring %s of ciphertext %d" % (name, k)
+        k0, k1 = to_device(keys[0]), to_device(keys[1])
+        for i, x in enumerate((de, dm)):             # gpq_keyswitch
+            c0, c1 = torch.empty_like(x), torch.empty_like(x)
+            g.he_keyswitch(c0, c1, x, k0, k1, dim)
+            h0, h1 = to_host(c0), to_host(c1)
+            for k in range(BATCH):
+                f0, f1 = exp["keyswitch"][i][k]
+                assert np.array_equal(h0[k * per:(k + 1) * per], f0) and np.array_equal(h1[k * per:(k + 1) * per], f1), "key switch, slab %d, polynomial %d" % (i, k)
+    finally:
+        g.close()

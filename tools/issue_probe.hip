@@ -25,7 +25,7 @@ constexpr int ITER = 512;
 template <int MIX>
 __global__ __launch_bounds__(1024) void probe(uint64_t *out, const LimbTab *tabs, const TwW *tw, unsigned long long *cycles) {
   extern __shared__ uint64_t pad[];                   // sized by the host: one workgroup per CU
-  const PrimeK k = tabs[0].k;
+  const PrimeK k = pin_consts(tabs[0].k);
   uint64_t x[8];
   TwW t[7];
 #pragma unroll
@@ -89,9 +89,8 @@ int main(int argc, char **argv) {
   LimbTab tab;
   memset((void *)&tab, 0, sizeof tab);
   tab.k.p = p; tab.k.p2 = 2 * p; tab.k.p4 = 4 * p; tab.k.c = (uint32_t)(p - (1ull << 59)); tab.k.c1 = tab.k.c + 1;
-  tab.k.kx0 = tab.k.c1; tab.k.kx1 = (uint64_t)tab.k.c1 - 4 * p; tab.k.ky = 4 * p - 2 * (uint64_t)tab.k.c1;
-  tab.k.kys = 2 * p - 2 * (uint64_t)tab.k.c1;
-  tab.k.p3 = 3 * p; tab.k.np3 = (uint64_t)0 - 3 * p; tab.k.kx1x = (uint64_t)tab.k.c1 - 3 * p; tab.k.kyx = 3 * p - 2 * (uint64_t)tab.k.c1;
+  tab.k.kinj = 31 * (uint64_t)tab.k.c - 1; tab.k.one = 1;
+  tab.k.p3 = 3 * p; tab.k.np3 = (uint64_t)0 - 3 * p;
   tab.k.np = (uint64_t)0 - p; tab.k.np2 = (uint64_t)0 - 2 * p; tab.k.np4 = (uint64_t)0 - 4 * p;
   tab.ninv = 281474976710656ull % p;
   TwW htw[64 * 7];

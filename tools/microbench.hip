@@ -25,7 +25,7 @@ __global__ __launch_bounds__(256) void probe(uint64_t *out, uint64_t seed, Prime
       if (OP == 2) v[i] = mad_u64((uint32_t)v[i], m, v[i]);                                 // v_mad_u64_u32
       if (OP == 3) v[i] = v[i] + k.p;                                                       // 64-bit add
       if (OP == 4) v[i] = mulmod_lazy(v[i] & 0x3fffffffffffffffull, k.p - 1 - i, k);        // 7 mads + fold
-      if (OP == 5) v[i] = csub(v[i], k.p4) + m;                                             // conditional subtract
+      if (OP == 5) v[i] = csub4(v[i], k) + m;                                             // conditional subtract
     }
     if (OP == 6) {  // 4 CT butterflies on the 8 values
 #pragma unroll
@@ -63,7 +63,7 @@ int run(const char *name, double ops_per_iter, uint64_t *d_out, PrimeK k) {
 int main() {
   uint64_t *d_out; CHECK(hipMalloc(&d_out, 256 * 8 * 256 * 8));
   PrimeK k; k.p = 576460752308273153ull; k.p2 = 2 * k.p; k.p4 = 4 * k.p; k.c = (uint32_t)(k.p - (1ull << 59)); k.c1 = k.c + 1;
-  k.kx0 = k.c1; k.kx1 = (uint64_t)k.c1 - k.p4; k.ky = k.p4 - 2 * (uint64_t)k.c1;
+  k.np4 = (uint64_t)0 - k.p4; k.kinj = 31 * (uint64_t)k.c - 1; k.one = 1;
   run<0>("v_add_u32", 8, d_out, k);
   run<1>("v_mul_lo_u32", 8, d_out, k);
   run<2>("v_mad_u64_u32", 8, d_out, k);
