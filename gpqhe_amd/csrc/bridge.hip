@@ -1347,6 +1347,35 @@ int relin_tail(gpq_ctx *c, Two<uint64_t> out, const uint64_t *chat, Two<const ui
 
 inline size_t align64(size_t b) { return (b + 63) & ~(size_t)63; }
 
+// Workspace layouts of gpq_he_mul and gpq_he_swk for launch groups of m ciphertexts: byte offsets of the regions in the order they lie in,
+// every size rounded to 64 bytes.  One definition for the *_workspace_bytes functions and for the entry points that carve the buffer.
+struct HeMulPlan { size_t sA, wsT, sB, wsK, dbig, tail, total; };
+int he_mul_plan(gpq_ctx *c, unsigned W, unsigned dimA, unsigned dimB, unsigned dimP, unsigned m, HeMulPlan *h) {
+  TailPlan tp;
+  int rc = tail_plan(c, W, dimP, dimB, 2 * m, &tp);                 // c0 and c1 of a launch group go through the tail together
+  if (rc) return rc;
+  const size_t n = c->n;
+  h->sA = 0;
+  h->wsT = h->sA + align64((size_t)m * 7 * dimA * n * 8);                  // sA: 4 decomposed inputs + d0hat,d1hat,d2hat
+  h->sB = h->wsT + align64(gpq_tensor_workspace_bytes(c, dimA, m));
+  h->wsK = h->sB + align64((size_t)m * 3 * dimB * n * 8);                  // sB: decomposed d2, c0hat, c1hat
+  h->dbig = h->wsK + align64(gpq_keyswitch_workspace_bytes(c, dimB, m));
+  h->tail = h->dbig + align64((size_t)m * 3 * W * n * 8);                  // dbig: d0, d1, d2
+  h->total = h->tail + align64(tp.bytes);
+  return GPQ_OK;
+}
+struct HeSwkPlan { size_t sB, wsK, tail, total; };
+int he_swk_plan(gpq_ctx *c, unsigned W, unsigned dimB, unsigned dimP, unsigned m, HeSwkPlan *h) {
+  TailPlan tp;
+  int rc = tail_plan(c, W, dimP, dimB, 2 * m, &tp);
+  if (rc) return rc;
+  h->sB = 0;
+  h->wsK = h->sB + align64((size_t)m * 3 * dimB * c->n * 8);               // sB: decomposed d1, c0hat, c1hat
+  h->tail = h->wsK + align64(gpq_keyswitch_workspace_bytes(c, dimB, m));
+  h->total = h->tail + align64(tp.bytes);
+  return GPQ_OK;
+}
+
 }  // namespace
 
 // dims the reference derives from the modulus chain: hectx.dim src/precomp.c:401, he_mul's
@@ -1367,18 +1396,8 @@ extern "C" int gpq_he_dims(gpq_ctx *c, unsigned logqL, unsigned logql, unsigned 
 }
 
 extern "C" size_t gpq_he_mul_workspace_bytes(gpq_ctx *c, unsigned W, unsigned dimA, unsigned dimB, unsigned dimP, unsigned batch) {
-  const unsigned m = batch < c->chunk ? batch : c->chunk;
-  TailPlan tp;
-  if (tail_plan(c, W, dimP, dimB, 2 * m, &tp) != GPQ_OK) return 0;      // c0 and c1 of a launch group go through the tail together
-  const size_t n = c->n;
-  size_t b = 0;
-  b += align64((size_t)m * 7 * dimA * n * 8);                       // 4 decomposed inputs + d0hat,d1hat,d2hat
-  b += align64(gpq_tensor_workspace_bytes(c, dimA, m));
-  b += align64((size_t)m * 3 * dimB * n * 8);                       // decomposed d2 (or d1), c0hat, c1hat
-  b += align64(gpq_keyswitch_workspace_bytes(c, dimB, m));
-  b += align64((size_t)m * 3 * W * n * 8);                          // d0, d1, d2
-  b += align64(tp.bytes);
-  return b;
+  HeMulPlan h;
+  return he_mul_plan(c, W, dimA, dimB, dimP, gpq_group_size(c, batch), &h) == GPQ_OK ? h.total : 0;
 }
 
 // he_mul, src/he-mult.c:88-156 (decl src/gpqhe.h:147), on big slabs of W words, q_l = 2^logql.
@@ -1410,28 +1429,21 @@ static int he_mul_impl(gpq_ctx *c, uint64_t *out_c0, uint64_t *out_c1, const uin
     return gpq_fail(GPQ_ERR_INVALID, "%s: bad arguments", who);
   hipStream_t s = (hipStream_t)stream;
   const size_t n = c->n, bigpoly = (size_t)W * n;
-  const unsigned m = batch < c->chunk ? batch : c->chunk;
-  TailPlan tp;
-  if ((rc = tail_plan(c, W, dimP, dimB, 2 * m, &tp))) return rc;
+  const unsigned m = gpq_group_size(c, batch);
+  HeMulPlan plan;
+  if ((rc = he_mul_plan(c, W, dimA, dimB, dimP, m, &plan))) return rc;
   char *w = (char *)workspace;
-  uint64_t *sA = (uint64_t *)w; w += align64((size_t)m * 7 * dimA * n * 8);
-  void *wsT = w; w += align64(gpq_tensor_workspace_bytes(c, dimA, m));
-  uint64_t *sB = (uint64_t *)w; w += align64((size_t)m * 3 * dimB * n * 8);
-  void *wsK = w; w += align64(gpq_keyswitch_workspace_bytes(c, dimB, m));
-  uint64_t *dbig = (uint64_t *)w; w += align64((size_t)m * 3 * W * n * 8);
-  void *wsTail = w;
+  uint64_t *sA = (uint64_t *)(w + plan.sA), *sB = (uint64_t *)(w + plan.sB), *dbig = (uint64_t *)(w + plan.dbig);
+  void *wsT = w + plan.wsT, *wsK = w + plan.wsK, *wsTail = w + plan.tail;
   gpq_bridge_basis *bA;
   if ((rc = get_basis(c, 0, dimA, &bA))) return rc;
-  PeerLane lane;
-  if (batch > m && (rc = gpq_peer_lane(c, s, gpq_lane_key(1, W, dimA, dimB, dimP, m ^ (logql << 8)), [&](gpq_ctx *q) { return gpq_he_mul_workspace_bytes(q, W, dimA, dimB, dimP, m); }, &lane))) return rc;
-  for (unsigned k0 = 0; k0 < batch; k0 += m) {
-    const unsigned polys = batch - k0 < m ? batch - k0 : m;
-    if (lane.c && ((k0 / m) & 1)) {                              // every other launch group: the same call on the peer, for this group's slice
-      const size_t o = k0 * bigpoly;
-      if ((rc = he_mul_impl(lane.c, out_c0 + o, out_c1 + o, ct1c0 + o, ct1c1 + o, ct2c0 + o, ct2c1 + o, rlk0, rlk1, W, logql, dimA, dimB, dimP,
-                            polys, lane.ws, lane.s, rs))) return rc;
-      continue;
-    }
+  auto peer = [&](const PeerLane &lane, unsigned k0, unsigned polys) {       // every other launch group: the same call on the peer, for this group's slice
+    const size_t o = k0 * bigpoly;
+    return he_mul_impl(lane.c, out_c0 + o, out_c1 + o, ct1c0 + o, ct1c1 + o, ct2c0 + o, ct2c1 + o, rlk0, rlk1, W, logql, dimA, dimB, dimP,
+                       polys, lane.ws, lane.s, rs);
+  };
+  auto own = [&](unsigned k0, unsigned polys) {
+    int rc;
     const size_t pa = (size_t)polys * dimA * n, pb = (size_t)polys * dimB * n;
     uint64_t *h[4] = {sA, sA + pa, sA + 2 * pa, sA + 3 * pa};
     uint64_t *d0h = sA + 4 * pa, *d1h = sA + 5 * pa, *d2h = sA + 6 * pa;
@@ -1490,10 +1502,10 @@ static int he_mul_impl(gpq_ctx *c, uint64_t *out_c0, uint64_t *out_c1, const uin
                     rs >= 1 && rs <= 63 ? rs : 0u, &rescaled);   // the tail kernel shifts inside one word; other Deltas take the rescale kernel below
     if (rc) return rc;
     if (rs && !rescaled && (rc = gpq_he_rs(c, out_c0 + k0 * bigpoly, out_c1 + k0 * bigpoly, W, rs, logql - rs, polys, stream))) return rc;   // src/he-rescale.c:33-54
-  }
-  const unsigned lanes_used = lane.c ? 2u : 1u;
-  if ((rc = gpq_peer_join(c, s, lane))) return rc;
-  c->last_lanes = lanes_used;   // (after the nested entry points of the groups, which record their own)
+    return (int)GPQ_OK;
+  };
+  if ((rc = gpq_launch_groups(c, s, batch, m, gpq_lane_key(1, W, dimA, dimB, dimP, m ^ (logql << 8)),
+                              [&](gpq_ctx *q) { return gpq_he_mul_workspace_bytes(q, W, dimA, dimB, dimP, m); }, own, peer))) return rc;
   return launched(who);
 }
 
@@ -1508,22 +1520,18 @@ extern "C" int gpq_he_swk(gpq_ctx *c, uint64_t *out_c0, uint64_t *out_c1, const 
     return gpq_fail(GPQ_ERR_INVALID, "gpq_he_swk: bad arguments");
   hipStream_t s = (hipStream_t)stream;
   const size_t n = c->n, bigpoly = (size_t)W * n;
-  const unsigned m = batch < c->chunk ? batch : c->chunk;
-  TailPlan tp;
-  if ((rc = tail_plan(c, W, dimP, dimB, 2 * m, &tp))) return rc;
+  const unsigned m = gpq_group_size(c, batch);
+  HeSwkPlan plan;
+  if ((rc = he_swk_plan(c, W, dimB, dimP, m, &plan))) return rc;
   char *w = (char *)workspace;
-  uint64_t *sB = (uint64_t *)w; w += align64((size_t)m * 3 * dimB * n * 8);
-  void *wsK = w; w += align64(gpq_keyswitch_workspace_bytes(c, dimB, m));
-  void *wsTail = w;
-  PeerLane lane;
-  if (batch > m && (rc = gpq_peer_lane(c, s, gpq_lane_key(2, W, 0, dimB, dimP, m ^ (logql << 8)), [&](gpq_ctx *q) { return gpq_he_swk_workspace_bytes(q, W, dimB, dimP, m); }, &lane))) return rc;
-  for (unsigned k0 = 0; k0 < batch; k0 += m) {
-    const unsigned polys = batch - k0 < m ? batch - k0 : m;
-    if (lane.c && ((k0 / m) & 1)) {                              // (as in gpq_he_mul)
-      const size_t o = k0 * bigpoly;
-      if ((rc = gpq_he_swk(lane.c, out_c0 + o, out_c1 + o, d0 + o, d1 + o, swk0, swk1, W, logql, dimB, dimP, polys, lane.ws, lane.s))) return rc;
-      continue;
-    }
+  uint64_t *sB = (uint64_t *)(w + plan.sB);
+  void *wsK = w + plan.wsK, *wsTail = w + plan.tail;
+  auto peer = [&](const PeerLane &lane, unsigned k0, unsigned polys) {       // (as in gpq_he_mul)
+    const size_t o = k0 * bigpoly;
+    return gpq_he_swk(lane.c, out_c0 + o, out_c1 + o, d0 + o, d1 + o, swk0, swk1, W, logql, dimB, dimP, polys, lane.ws, lane.s);
+  };
+  auto own = [&](unsigned k0, unsigned polys) {
+    int rc;
     const size_t pb = (size_t)polys * dimB * n;
     uint64_t *d1hat = sB, *c0hat = sB + pb, *c1hat = sB + 2 * pb;
     if ((rc = launch_decompose(c, d1hat, d1 + k0 * bigpoly, W, 0, dimB, polys, s, c->lazy_decompose && c->logn > 12))) return rc;   // :60
@@ -1537,17 +1545,15 @@ extern "C" int gpq_he_swk(gpq_ctx *c, uint64_t *out_c0, uint64_t *out_c1, const 
     // c0 (+ d0) and c1 (no addend) as one batch of 2 x polys polynomials                                           // :68-75
     if ((rc = relin_tail(c, Two<uint64_t>{out_c0 + k0 * bigpoly, out_c1 + k0 * bigpoly, polys}, c0hat, Two<const uint64_t>{d0 + k0 * bigpoly, nullptr, polys},
                          W, dimP, dimB, logql, 2 * polys, wsTail, s, tail_mode))) return rc;
-  }
-  const unsigned lanes_used = lane.c ? 2u : 1u;
-  if ((rc = gpq_peer_join(c, s, lane))) return rc;
-  c->last_lanes = lanes_used;   // (after the nested entry points of the groups, which record their own)
+    return (int)GPQ_OK;
+  };
+  if ((rc = gpq_launch_groups(c, s, batch, m, gpq_lane_key(2, W, 0, dimB, dimP, m ^ (logql << 8)),
+                              [&](gpq_ctx *q) { return gpq_he_swk_workspace_bytes(q, W, dimB, dimP, m); }, own, peer))) return rc;
   return launched("gpq_he_swk");
 }
 extern "C" size_t gpq_he_swk_workspace_bytes(gpq_ctx *c, unsigned W, unsigned dimB, unsigned dimP, unsigned batch) {
-  const unsigned m = batch < c->chunk ? batch : c->chunk;
-  TailPlan tp;
-  if (tail_plan(c, W, dimP, dimB, 2 * m, &tp) != GPQ_OK) return 0;
-  return align64((size_t)m * 3 * dimB * c->n * 8) + align64(gpq_keyswitch_workspace_bytes(c, dimB, m)) + align64(tp.bytes);
+  HeSwkPlan h;
+  return he_swk_plan(c, W, dimB, dimP, gpq_group_size(c, batch), &h) == GPQ_OK ? h.total : 0;
 }
 
 // ---------------------------------------------------------------------------

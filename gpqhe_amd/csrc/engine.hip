@@ -528,6 +528,43 @@ static inline void with_nt(unsigned nt, F f) {
   else f(std::false_type{});
 }
 
+// The fused middles (ntt_kernels.hpp: *_mid8*), launched once per class of limbs present under one ProfScope: launch(instantiation, args of
+// the class's limbs, their number = the grid's z extent), with the instantiation of the class, of the ring (LOW = 9 at n = 2^17) and of the
+// group's cache policy.  The grid's x extent and the block are the same for all of them.
+template <typename TW_, int LOW_, bool NT_>
+struct Mid8Inst { using TW = TW_; static constexpr int LOW = LOW_; static constexpr bool NT = NT_; };
+template <typename F>
+static int launch_mid8(const gpq_ctx *c, const PassArgs &m, unsigned limbs, const uint64_t **evk0, const uint64_t **evk1, int slot, hipStream_t s, F launch) {
+  return for_limb_ranges<true>(c, m, limbs, evk0, evk1, [&](auto tag, const PassArgs &a, unsigned nl) {
+    using TW = decltype(tag);
+    ProfScope prof(c, slot, s);
+    with_nt(a.nt, [&](auto nt) {
+      constexpr bool NT = decltype(nt)::value;
+      if (c->low9) launch(Mid8Inst<TW, 9, NT>{}, a, nl);
+      else launch(Mid8Inst<TW, 8, NT>{}, a, nl);
+    });
+    return (int)GPQ_OK;
+  });
+}
+// ... a PassArgs kernel over `polys` polynomials: kernel(instantiation) = the __global__ function
+template <typename K>
+static int launch_mid8(const gpq_ctx *c, const PassArgs &m, unsigned limbs, unsigned polys, int slot, hipStream_t s, K kernel) {
+  return launch_mid8(c, m, limbs, nullptr, nullptr, slot, s, [&](auto inst, const PassArgs &a, unsigned nl) {
+    hipLaunchKernelGGL(kernel(inst), dim3(c->n >> 11, polys, nl), dim3(CONTIG_WAVES * 64), 0, s, a);
+  });
+}
+// ... a key-switch middle: the polynomials of a group in pairs, an odd last one alone (half the arithmetic of a pair that would be stored
+// once).  kernel(instantiation, pair form?) = the __global__ function; tail = what it takes after `first`.
+template <typename K, typename... Tail>
+static int launch_keyswitch_mid8(const gpq_ctx *c, KeyswitchArgs m, unsigned limbs, unsigned polys, int slot, hipStream_t s, K kernel, Tail... tail) {
+  return launch_mid8(c, m.p, limbs, &m.evk0, &m.evk1, slot, s, [&](auto inst, const PassArgs &a, unsigned nl) {
+    KeyswitchArgs ka{a, m.evk0, m.evk1};
+    const dim3 block(CONTIG_WAVES * 64);
+    if (polys / 2) hipLaunchKernelGGL(kernel(inst, std::true_type{}), dim3(c->n >> 11, polys / 2, nl), block, 0, s, ka, 0u, tail...);
+    if (polys & 1) hipLaunchKernelGGL(kernel(inst, std::false_type{}), dim3(c->n >> 11, 1, nl), block, 0, s, ka, polys - 1, tail...);
+  });
+}
+
 template <int M1, int EL, bool INV, bool CANON, typename TW, int CW = 8>
 int launch_strided_t(const PassArgs &a, unsigned gy, unsigned gz, hipStream_t s) {
   using G = StridedGeom<M1, EL>;
@@ -775,16 +812,7 @@ extern "C" int gpq_poly_mul_rns(gpq_ctx *c, uint64_t *r, uint64_t *a, uint64_t *
     if ((rc = launch_strided<false>(c, f, dim, polys, s))) return rc;
     PassArgs m = make_args(c, dim, 1, nt);
     m.src[0] = f.dst[0]; m.src[1] = f.dst[1]; m.dst[0] = r + k0 * poly;
-    if ((rc = for_limb_ranges<true>(c, m, dim, nullptr, nullptr, [&](auto tag, const PassArgs &p, unsigned limbs) {
-          using TW = decltype(tag);
-          ProfScope prof(c, GPQ_K_CONTIG_FWD, s);
-          with_nt(p.nt, [&](auto nt) {
-            constexpr bool NT = decltype(nt)::value;
-            if (c->low9) hipLaunchKernelGGL((polymul_mid8<TW, 9, NT>), dim3(c->n >> 11, polys, limbs), dim3(CONTIG_WAVES * 64), 0, s, p);
-            else hipLaunchKernelGGL((polymul_mid8<TW, 8, NT>), dim3(c->n >> 11, polys, limbs), dim3(CONTIG_WAVES * 64), 0, s, p);
-          });
-          return (int)GPQ_OK;
-        }))) return rc;
+    if ((rc = launch_mid8(c, m, dim, polys, GPQ_K_CONTIG_FWD, s, [](auto i) { using I = decltype(i); return polymul_mid8<typename I::TW, I::LOW, I::NT>; }))) return rc;
     PassArgs b2 = make_args(c, dim, 1, nt);
     b2.src[0] = b2.dst[0] = m.dst[0];
     if ((rc = launch_strided<true>(c, b2, dim, polys, s))) return rc;
@@ -816,16 +844,7 @@ extern "C" int gpq_mulpt_rns(gpq_ctx *c, uint64_t *r0, uint64_t *r1, uint64_t *m
     PassArgs p = make_args(c, dim, 1, nt);
     for (int i = 0; i < 3; ++i) p.src[i] = f.dst[i];
     p.dst[0] = r0 + k0 * poly; p.dst[1] = r1 + k0 * poly;
-    if ((rc = for_limb_ranges<true>(c, p, dim, nullptr, nullptr, [&](auto tag, const PassArgs &q, unsigned limbs) {
-          using TW = decltype(tag);
-          ProfScope prof(c, GPQ_K_CONTIG_FWD, s);
-          with_nt(q.nt, [&](auto nt) {
-            constexpr bool NT = decltype(nt)::value;
-            if (c->low9) hipLaunchKernelGGL((mulpt_mid8<TW, 9, NT>), dim3(c->n >> 11, polys, limbs), dim3(CONTIG_WAVES * 64), 0, s, q);
-            else hipLaunchKernelGGL((mulpt_mid8<TW, 8, NT>), dim3(c->n >> 11, polys, limbs), dim3(CONTIG_WAVES * 64), 0, s, q);
-          });
-          return (int)GPQ_OK;
-        }))) return rc;
+    if ((rc = launch_mid8(c, p, dim, polys, GPQ_K_CONTIG_FWD, s, [](auto i) { using I = decltype(i); return mulpt_mid8<typename I::TW, I::LOW, I::NT>; }))) return rc;
     PassArgs b2 = make_args(c, dim, 2, nt);
     b2.src[0] = b2.dst[0] = p.dst[0]; b2.src[1] = b2.dst[1] = p.dst[1];
     if ((rc = launch_strided<true>(c, b2, dim, polys, s))) return rc;
@@ -836,20 +855,17 @@ extern "C" int gpq_mulpt_rns(gpq_ctx *c, uint64_t *r0, uint64_t *r1, uint64_t *m
 // ---------------------------------------------------------------------------
 // fused he_mul RNS core
 // ---------------------------------------------------------------------------
-static unsigned tensor_chunk(const gpq_ctx *c, unsigned batch) {
-  return batch < c->chunk ? batch : c->chunk;
-}
 static unsigned limb_block(const gpq_ctx *c, unsigned dim) {
   return (c->limb_block && c->limb_block < dim) ? c->limb_block : dim;
 }
 
 extern "C" size_t gpq_tensor_workspace_bytes(const gpq_ctx *c, unsigned dim, unsigned batch) {
   if (!two_pass(c)) return 4ull * batch * ((size_t)dim << c->logn) * 8;
-  return 4ull * tensor_chunk(c, batch) * ((size_t)dim << c->logn) * 8;
+  return 4ull * gpq_group_size(c, batch) * ((size_t)dim << c->logn) * 8;
 }
 extern "C" size_t gpq_keyswitch_workspace_bytes(const gpq_ctx *c, unsigned dim, unsigned batch) {
   if (!two_pass(c)) return 1ull * batch * ((size_t)dim << c->logn) * 8;
-  return 1ull * tensor_chunk(c, batch) * ((size_t)dim << c->logn) * 8;
+  return 1ull * gpq_group_size(c, batch) * ((size_t)dim << c->logn) * 8;
 }
 
 extern "C" int gpq_he_mul_tensor(gpq_ctx *c, uint64_t *d0, uint64_t *d1, uint64_t *d2,
@@ -885,17 +901,14 @@ extern "C" int gpq_he_mul_tensor(gpq_ctx *c, uint64_t *d0, uint64_t *d1, uint64_
   // Both operands the same ciphertext (he_mul(&ct, &ct, &ct, rlk), src/he-algo.c:151): two forward transforms instead of four
   const bool square = a0 == b0 && a1 == b1;
   const unsigned nin = square ? 2 : 4;
-  const unsigned chunk = tensor_chunk(c, batch);
+  const unsigned chunk = gpq_group_size(c, batch);
   const unsigned lblock = limb_block(c, dim);
-  PeerLane lane;                                             // two launch groups in flight (engine_internal.hpp: gpq_peer_lane)
-  if (batch > chunk && (rc = gpq_peer_lane(c, s, gpq_lane_key(3, dim, chunk, 0, 0, 0), [&](gpq_ctx *q) { return gpq_tensor_workspace_bytes(q, dim, chunk); }, &lane))) return rc;
-  for (unsigned k0 = 0; k0 < batch; k0 += chunk) {
-    const unsigned polys = (batch - k0 < chunk) ? batch - k0 : chunk;
-    if (lane.c && ((k0 / chunk) & 1)) {
-      const size_t o = k0 * poly;
-      if ((rc = gpq_he_mul_tensor(lane.c, d0 + o, d1 + o, d2 + o, a0 + o, a1 + o, b0 + o, b1 + o, dim, polys, lane.ws, lane.s))) return rc;
-      continue;
-    }
+  auto peer = [&](const PeerLane &lane, unsigned k0, unsigned polys) {
+    const size_t o = k0 * poly;
+    return gpq_he_mul_tensor(lane.c, d0 + o, d1 + o, d2 + o, a0 + o, a1 + o, b0 + o, b1 + o, dim, polys, lane.ws, lane.s);
+  };
+  auto own = [&](unsigned k0, unsigned polys) {
+    int rc;
     // A launch group = `polys` polynomials x `limbs` limbs of every slab: its three kernels run back to back so that
     // what one writes the next one reads while it is still in the Infinity Cache (gpq_set_limb_block).
     for (unsigned l0 = 0; l0 < dim; l0 += lblock) {
@@ -913,17 +926,9 @@ extern "C" int gpq_he_mul_tensor(gpq_ctx *c, uint64_t *d0, uint64_t *d1, uint64_
       m.limb0 = l0;
       for (unsigned i = 0; i < nin; ++i) m.src[i] = f.dst[i];
       m.dst[0] = d0 + k0 * poly + loff; m.dst[1] = d1 + k0 * poly + loff; m.dst[2] = d2 + k0 * poly + loff;
-      if ((rc = for_limb_ranges<true>(c, m, limbs, nullptr, nullptr, [&](auto tag, const PassArgs &a, unsigned nl) {
-            using TW = decltype(tag);
-            ProfScope prof(c, GPQ_K_TENSOR_MID, s);
-            with_nt(a.nt, [&](auto nt) {
-              constexpr bool NT = decltype(nt)::value;
-              if (square && c->low9) hipLaunchKernelGGL((tensor_sq_mid8<TW, 9, NT>), dim3(c->n >> 11, polys, nl), dim3(CONTIG_WAVES * 64), 0, s, a);
-              else if (square) hipLaunchKernelGGL((tensor_sq_mid8<TW, 8, NT>), dim3(c->n >> 11, polys, nl), dim3(CONTIG_WAVES * 64), 0, s, a);
-              else if (c->low9) hipLaunchKernelGGL((tensor_mid8<TW, 9, NT>), dim3(c->n >> 11, polys, nl), dim3(CONTIG_WAVES * 64), 0, s, a);
-              else hipLaunchKernelGGL((tensor_mid8<TW, 8, NT>), dim3(c->n >> 11, polys, nl), dim3(CONTIG_WAVES * 64), 0, s, a);
-            });
-            return (int)GPQ_OK;
+      if ((rc = launch_mid8(c, m, limbs, polys, GPQ_K_TENSOR_MID, s, [&](auto i) {
+            using I = decltype(i);
+            return square ? tensor_sq_mid8<typename I::TW, I::LOW, I::NT> : tensor_mid8<typename I::TW, I::LOW, I::NT>;
           }))) return rc;
       // 3. strided inverse pass in place on the three outputs
       PassArgs b = make_args(c, dim, 3, nt);
@@ -932,10 +937,10 @@ extern "C" int gpq_he_mul_tensor(gpq_ctx *c, uint64_t *d0, uint64_t *d1, uint64_
       for (int i = 0; i < 3; ++i) { b.src[i] = m.dst[i]; b.dst[i] = m.dst[i]; }
       if ((rc = launch_strided<true>(c, b, limbs, polys, s))) return rc;
     }
-  }
-  const unsigned lanes_used = lane.c ? 2u : 1u;
-  if ((rc = gpq_peer_join(c, s, lane))) return rc;
-  c->last_lanes = lanes_used;   // (after the nested entry points of the groups, which record their own)
+    return (int)GPQ_OK;
+  };
+  // two launch groups in flight (engine_internal.hpp: gpq_launch_groups)
+  if ((rc = gpq_launch_groups(c, s, batch, chunk, gpq_lane_key(3, dim, chunk, 0, 0, 0), [&](gpq_ctx *q) { return gpq_tensor_workspace_bytes(q, dim, chunk); }, own, peer))) return rc;
   return after_launch("gpq_he_mul_tensor");
 }
 
@@ -960,17 +965,14 @@ extern "C" int gpq_keyswitch(gpq_ctx *c, uint64_t *c0, uint64_t *c1, const uint6
     return gpq_invntt(c, c1, dim, batch, stream);
   }
 
-  const unsigned chunk = tensor_chunk(c, batch);
+  const unsigned chunk = gpq_group_size(c, batch);
   const unsigned lblock = limb_block(c, dim);
-  PeerLane lane;
-  if (batch > chunk && (rc = gpq_peer_lane(c, s, gpq_lane_key(4, dim, chunk, 0, 0, 0), [&](gpq_ctx *q) { return gpq_keyswitch_workspace_bytes(q, dim, chunk); }, &lane))) return rc;
-  for (unsigned k0 = 0; k0 < batch; k0 += chunk) {
-    const unsigned polys = (batch - k0 < chunk) ? batch - k0 : chunk;
-    if (lane.c && ((k0 / chunk) & 1)) {
-      const size_t o = k0 * poly;
-      if ((rc = gpq_keyswitch(lane.c, c0 + o, c1 + o, x + o, evk0, evk1, dim, polys, lane.ws, lane.s))) return rc;
-      continue;
-    }
+  auto peer = [&](const PeerLane &lane, unsigned k0, unsigned polys) {
+    const size_t o = k0 * poly;
+    return gpq_keyswitch(lane.c, c0 + o, c1 + o, x + o, evk0, evk1, dim, polys, lane.ws, lane.s);
+  };
+  auto own = [&](unsigned k0, unsigned polys) {
+    int rc;
     for (unsigned l0 = 0; l0 < dim; l0 += lblock) {       // launch groups as in gpq_he_mul_tensor
       const unsigned limbs = dim - l0 < lblock ? dim - l0 : lblock;
       const size_t loff = (size_t)l0 << c->logn;
@@ -985,23 +987,9 @@ extern "C" int gpq_keyswitch(gpq_ctx *c, uint64_t *c0, uint64_t *c1, const uint6
       m.p.limb0 = l0;
       m.p.src[0] = f.dst[0]; m.p.dst[0] = c0 + k0 * poly + loff; m.p.dst[1] = c1 + k0 * poly + loff;
       m.evk0 = evk0 + loff; m.evk1 = evk1 + loff;
-      if ((rc = for_limb_ranges<true>(c, m.p, limbs, &m.evk0, &m.evk1, [&](auto tag, const PassArgs &a, unsigned nl) {
-            using TW = decltype(tag);
-            KeyswitchArgs ka{a, m.evk0, m.evk1};
-            ProfScope prof(c, GPQ_K_KEYSWITCH_MID, s);
-            const dim3 block(CONTIG_WAVES * 64);
-            with_nt(a.nt, [&](auto nt) {
-              constexpr bool NT = decltype(nt)::value;
-              if (polys / 2) {
-                if (c->low9) hipLaunchKernelGGL((keyswitch_mid8x2<TW, 9, true, NT>), dim3(c->n >> 11, polys / 2, nl), block, 0, s, ka, 0u);
-                else hipLaunchKernelGGL((keyswitch_mid8x2<TW, 8, true, NT>), dim3(c->n >> 11, polys / 2, nl), block, 0, s, ka, 0u);
-              }
-              if (polys & 1) {           // the odd last polynomial alone (half the arithmetic of a pair that would be stored once)
-                if (c->low9) hipLaunchKernelGGL((keyswitch_mid8x2<TW, 9, false, NT>), dim3(c->n >> 11, 1, nl), block, 0, s, ka, polys - 1);
-                else hipLaunchKernelGGL((keyswitch_mid8x2<TW, 8, false, NT>), dim3(c->n >> 11, 1, nl), block, 0, s, ka, polys - 1);
-              }
-            });
-            return (int)GPQ_OK;
+      if ((rc = launch_keyswitch_mid8(c, m, limbs, polys, GPQ_K_KEYSWITCH_MID, s, [](auto i, auto two) {
+            using I = decltype(i);
+            return keyswitch_mid8x2<typename I::TW, I::LOW, decltype(two)::value, I::NT>;
           }))) return rc;
       PassArgs b = make_args(c, dim, 2, nt);
       b.limb0 = l0;
@@ -1009,10 +997,9 @@ extern "C" int gpq_keyswitch(gpq_ctx *c, uint64_t *c0, uint64_t *c1, const uint6
       for (int i = 0; i < 2; ++i) { b.src[i] = m.p.dst[i]; b.dst[i] = m.p.dst[i]; }
       if ((rc = launch_strided<true>(c, b, limbs, polys, s))) return rc;
     }
-  }
-  const unsigned lanes_used = lane.c ? 2u : 1u;
-  if ((rc = gpq_peer_join(c, s, lane))) return rc;
-  c->last_lanes = lanes_used;   // (after the nested entry points of the groups, which record their own)
+    return (int)GPQ_OK;
+  };
+  if ((rc = gpq_launch_groups(c, s, batch, chunk, gpq_lane_key(4, dim, chunk, 0, 0, 0), [&](gpq_ctx *q) { return gpq_keyswitch_workspace_bytes(q, dim, chunk); }, own, peer))) return rc;
   return after_launch("gpq_keyswitch");
 }
 
@@ -1068,24 +1055,10 @@ int gpq_keyswitch_rotated(gpq_ctx *c, uint64_t *c0, uint64_t *c1, const uint64_t
   m.p = make_args(c, dim, 1, nt);
   m.p.src[0] = X; m.p.dst[0] = c0; m.p.dst[1] = c1;
   m.evk0 = evk0; m.evk1 = evk1;
-  if ((rc = for_limb_ranges<true>(c, m.p, dim, &m.evk0, &m.evk1, [&](auto tag, const PassArgs &a, unsigned nl) {
-        using TW = decltype(tag);
-        KeyswitchArgs ka{a, m.evk0, m.evk1};
-        ProfScope prof(c, GPQ_K_KEYSWITCH_ROT_MID, s);
-        const dim3 block(CONTIG_WAVES * 64);
-        with_nt(a.nt, [&](auto ntv) {
-          constexpr bool NT = decltype(ntv)::value;
-          if (polys / 2) {
-            if (c->low9) hipLaunchKernelGGL((keyswitch_rot_mid8x2<TW, 9, true, NT>), dim3(c->n >> 11, polys / 2, nl), block, 0, s, ka, 0u, g);
-            else hipLaunchKernelGGL((keyswitch_rot_mid8x2<TW, 8, true, NT>), dim3(c->n >> 11, polys / 2, nl), block, 0, s, ka, 0u, g);
-          }
-          if (polys & 1) {
-            if (c->low9) hipLaunchKernelGGL((keyswitch_rot_mid8x2<TW, 9, false, NT>), dim3(c->n >> 11, 1, nl), block, 0, s, ka, polys - 1, g);
-            else hipLaunchKernelGGL((keyswitch_rot_mid8x2<TW, 8, false, NT>), dim3(c->n >> 11, 1, nl), block, 0, s, ka, polys - 1, g);
-          }
-        });
-        return (int)GPQ_OK;
-      }))) return rc;
+  if ((rc = launch_keyswitch_mid8(c, m, dim, polys, GPQ_K_KEYSWITCH_ROT_MID, s, [](auto i, auto two) {
+        using I = decltype(i);
+        return keyswitch_rot_mid8x2<typename I::TW, I::LOW, decltype(two)::value, I::NT>;
+      }, g))) return rc;
   PassArgs b = make_args(c, dim, 2, nt);
   if (c->inv_tabs_override) b.tabs = c->inv_tabs_override;
   b.src[0] = b.dst[0] = c0; b.src[1] = b.dst[1] = c1;

@@ -309,7 +309,27 @@ inline int PeerLane::join() {
   c = nullptr; owner = nullptr;
   return e == hipSuccess ? (int)GPQ_OK : gpq_fail(GPQ_ERR_HIP, "joining the peer stream: %s", hipGetErrorString(e));
 }
-inline int gpq_peer_join(gpq_ctx *, hipStream_t, PeerLane &lane) { return lane.join(); }
+// Polynomials (ciphertexts) per launch group of the multi-group entry points
+inline unsigned gpq_group_size(const gpq_ctx *c, unsigned batch) { return batch < c->chunk ? batch : c->chunk; }
+// The launch groups of a two-lane entry point: `batch` items in groups of `chunk` (gpq_group_size), every other group on the peer when the
+// call gets a lane (gpq_peer_lane with the call's `key` and `bytes`).  own(k0, count) runs a group on the caller's context and stream;
+// peer(lane, k0, count) is the SAME entry point on lane.c with lane.ws and lane.s for that group's slice of the batch -- with that entry's
+// own checks and its last_lanes bookkeeping, which is why the call's own is recorded after the groups.  A body's error ends the call; the
+// lane is joined on that path too (PeerLane's destructor).
+template <typename Bytes, typename Own, typename Peer>
+int gpq_launch_groups(gpq_ctx *c, hipStream_t s, unsigned batch, unsigned chunk, unsigned long long key, Bytes bytes, Own own, Peer peer) {
+  int rc;
+  PeerLane lane;
+  if (batch > chunk && (rc = gpq_peer_lane(c, s, key, bytes, &lane))) return rc;
+  for (unsigned k0 = 0; k0 < batch; k0 += chunk) {
+    const unsigned count = batch - k0 < chunk ? batch - k0 : chunk;
+    if ((rc = lane.c && ((k0 / chunk) & 1) ? peer(lane, k0, count) : own(k0, count))) return rc;
+  }
+  const unsigned lanes_used = lane.c ? 2u : 1u;
+  if ((rc = lane.join())) return rc;
+  c->last_lanes = lanes_used;
+  return GPQ_OK;
+}
 inline unsigned long long gpq_lane_key(unsigned entry, unsigned a, unsigned b, unsigned c3, unsigned d, unsigned e) {
   unsigned long long h = 0xcbf29ce484222325ull;
   for (unsigned v : {entry, a, b, c3, d, e}) { h ^= v; h *= 0x100000001b3ull; }

@@ -672,51 +672,72 @@ struct Tw8 {
   }
 };
 
-struct Block8 {             // per-workgroup addressing: 4 waves x 512 coefficients
-  unsigned wave0, limb;
-  size_t off, toff;
-  __device__ __forceinline__ Block8(const PassArgs &a) {
-    wave0 = (blockIdx.x * CONTIG_WAVES + (threadIdx.x >> 6)) << 9;
-    limb = a.limb0 + blockIdx.z;
-    off = (size_t)blockIdx.y * a.poly_stride + ((size_t)blockIdx.z << a.logn) + wave0;
-    toff = (size_t)limb << a.logn;
-  }
-};
-
 #ifndef GPQ_MID8_MINWAVES
 #define GPQ_MID8_MINWAVES 3
 #endif
+// The schedule every fused middle below shares.  A wave's 512 coefficients of each array go through the forward low stages H -> M -> L
+// (two exchanges through the wave's LDS region per array), the kernel's own products, and the inverse low stages L -> M -> H.  ONE twiddle
+// group (Tw8: 7 values or pairs, 6 or 7 for L) is live at a time and serves every array; each group is requested before the work of the
+// previous one, so it arrives under that work.  The statement order is the kernels' register budget: an array, or a second twiddle group,
+// that is live earlier than here costs a wave per SIMD.  Arrays come as parameter packs (no array of arrays): they stay in registers.
+// The code objects are compared with the hand-written kernels this replaced, instantiation by instantiation (tools/codeobj_ab.py,
+// profiles/r10/v1_codeobj_ab.txt); three things below are as they are because another form changed one of them:
+//   - toff is formed before the limb constants are read (the other order: one VALU instruction in the plain-twiddle LOW = 9 forms of
+//     polymul_mid8 and tensor_sq_mid8, which spill);
+//   - a kernel stores with ln.store_h itself after finish() (the store nested in finish(): the spills of keyswitch_rot_mid8x2's pair
+//     forms on split limbs go from 4 to 2 and to 8);
+//   - the products of the key switch are a macro and keyswitch_rot_mid8x2 writes its offset out (see there).
+template <typename TW, int LOW, bool NT>
+struct Mid8 {
+  using TT = TwTraits<TW>;
+  using L8 = Lane8N<LOW, NT>;
+  L8 ln;
+  const unsigned wave0, logn, limb;   // wave0 = limb-relative index of the wave's first coefficient
+  const size_t toff;                  // offset of the limb inside the twiddle tables
+  const PrimeK k;
+  const TW *__restrict__ wf, *__restrict__ wi;
+  Tw8<TW, LOW> tw;
+  // per-workgroup addressing: 4 waves x 512 coefficients of limb a.limb0 + blockIdx.z; lds = the workgroup's CONTIG_WAVES * LANE8_LDS_PER_WAVE words
+  __device__ __forceinline__ Mid8(uint64_t *lds, const PassArgs &a)
+      : ln(lds + (threadIdx.x >> 6) * LANE8_LDS_PER_WAVE), wave0((blockIdx.x * CONTIG_WAVES + (threadIdx.x >> 6)) << 9), logn(a.logn), limb(a.limb0 + blockIdx.z),
+        toff((size_t)limb << a.logn), k(pin_consts(a.tabs[limb].k)), wf(TT::table(a, false) + toff), wi(TT::table(a, true) + toff) {}
+  // offset of the wave's coefficients of polynomial `poly`, this limb, in a slab
+  __device__ __forceinline__ size_t off(const PassArgs &a, unsigned poly) const { return (size_t)poly * a.poly_stride + ((size_t)blockIdx.z << a.logn) + wave0; }
+  // the first array of a kernel, with the first forward twiddle group behind it; every other array
+  __device__ __forceinline__ void load_first(uint64_t (&x)[8], const uint64_t *__restrict__ p) { ln.load_h(x, p); tw.load_h(ln, wave0, logn, wf); }
+  __device__ __forceinline__ void load(uint64_t (&x)[8], const uint64_t *__restrict__ p) const { ln.load_h(x, p); }
+  template <typename... X> __device__ __forceinline__ void forward(X &...x) {
+    (L8::ct_h(x, tw.t, k), ...);
+    tw.load_m(ln, wave0, logn, wf);
+    ((ln.h_to_m(x), L8::ct_m(x, tw.t, k)), ...);
+    tw.load_l(ln, wave0, logn, wf);
+    ((ln.m_to_l(x), L8::ct_l(x, tw.u, k)), ...);
+  }
+  __device__ __forceinline__ void load_inverse_l() { tw.load_l(ln, wave0, logn, wi); }   // in front of the products: the inverse twiddles arrive under them
+  template <typename... X> __device__ __forceinline__ void inverse(X &...x) {
+    ((L8::gs_l(x, tw.u, k), ln.l_to_m(x)), ...);
+    tw.load_m(ln, wave0, logn, wi);
+    ((L8::gs_hm(x, tw.t, k), ln.m_to_h(x)), ...);
+    tw.load_h(ln, wave0, logn, wi);
+  }
+  // the last inverse group of an array; ln.store_h follows, in the kernel
+  __device__ __forceinline__ void finish(uint64_t (&x)[8]) const { L8::gs_hm(x, tw.t, k); }
+};
+
 template <typename TW, int LOW, bool NT = false>
 __global__ __launch_bounds__(CONTIG_WAVES * 64, GPQ_MID8_MINWAVES) void tensor_mid8(PassArgs a) {
   using TT = TwTraits<TW>;
-  using L8 = Lane8N<LOW, NT>;
   __shared__ uint64_t lds[CONTIG_WAVES * LANE8_LDS_PER_WAVE];
-  L8 ln(lds + (threadIdx.x >> 6) * LANE8_LDS_PER_WAVE);
-  const Block8 cb(a);
-  const PrimeK k = pin_consts(a.tabs[cb.limb].k);
-  const TW *__restrict__ wf = TT::table(a, false) + cb.toff, *__restrict__ wi = TT::table(a, true) + cb.toff;
   uint64_t a0[8], a1[8], b0[8], b1[8];
-  Tw8<TW, LOW> tw;
-  ln.load_h(a0, a.src[0] + cb.off);
-  tw.load_h(ln, cb.wave0, a.logn, wf);
-  ln.load_h(b0, a.src[2] + cb.off);
-  ln.load_h(a1, a.src[1] + cb.off);
-  ln.load_h(b1, a.src[3] + cb.off);
-  L8::ct_h(a0, tw.t, k);
-  L8::ct_h(b0, tw.t, k);
-  L8::ct_h(a1, tw.t, k);
-  L8::ct_h(b1, tw.t, k);
-  tw.load_m(ln, cb.wave0, a.logn, wf);
-  ln.h_to_m(a0); L8::ct_m(a0, tw.t, k);
-  ln.h_to_m(b0); L8::ct_m(b0, tw.t, k);
-  ln.h_to_m(a1); L8::ct_m(a1, tw.t, k);
-  ln.h_to_m(b1); L8::ct_m(b1, tw.t, k);
-  tw.load_l(ln, cb.wave0, a.logn, wf);
-  ln.m_to_l(a0); L8::ct_l(a0, tw.u, k);
-  ln.m_to_l(b0); L8::ct_l(b0, tw.u, k);
-  ln.m_to_l(a1); L8::ct_l(a1, tw.u, k);
-  ln.m_to_l(b1); L8::ct_l(b1, tw.u, k);
-  tw.load_l(ln, cb.wave0, a.logn, wi);               // inverse twiddles arrive under the products
+  Mid8<TW, LOW, NT> s(lds, a);
+  const size_t off = s.off(a, blockIdx.y);
+  const PrimeK &k = s.k;
+  s.load_first(a0, a.src[0] + off);
+  s.load(b0, a.src[2] + off);
+  s.load(a1, a.src[1] + off);
+  s.load(b1, a.src[3] + off);
+  s.forward(a0, b0, a1, b1);
+  s.load_inverse_l();
   uint64_t d1[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) {                      // products: TwTraits::left / right put the operands where mulmod_lazy's second fold fits 32 bits and the product leaves
@@ -727,20 +748,10 @@ __global__ __launch_bounds__(CONTIG_WAVES * 64, GPQ_MID8_MINWAVES) void tensor_m
     d1[e] = TT::inv_from8(mulmod_lazy(u0, v1, k) + mulmod_lazy(u1, v0, k), k);          // d1
     a1[e] = TT::inv_from4(mulmod_lazy(u1, v1, k), k);                                   // d2
   }
-  L8::gs_l(a0, tw.u, k); ln.l_to_m(a0);
-  L8::gs_l(d1, tw.u, k); ln.l_to_m(d1);
-  L8::gs_l(a1, tw.u, k); ln.l_to_m(a1);
-  tw.load_m(ln, cb.wave0, a.logn, wi);
-  L8::gs_hm(a0, tw.t, k); ln.m_to_h(a0);
-  L8::gs_hm(d1, tw.t, k); ln.m_to_h(d1);
-  L8::gs_hm(a1, tw.t, k); ln.m_to_h(a1);
-  tw.load_h(ln, cb.wave0, a.logn, wi);
-  L8::gs_hm(a0, tw.t, k);
-  ln.store_h(a.dst[0] + cb.off, a0);
-  L8::gs_hm(d1, tw.t, k);
-  ln.store_h(a.dst[1] + cb.off, d1);
-  L8::gs_hm(a1, tw.t, k);
-  ln.store_h(a.dst[2] + cb.off, a1);
+  s.inverse(a0, d1, a1);
+  s.finish(a0); s.ln.store_h(a.dst[0] + off, a0);
+  s.finish(d1); s.ln.store_h(a.dst[1] + off, d1);
+  s.finish(a1); s.ln.store_h(a.dst[2] + off, a1);
 }
 
 // The tensor stage of a SQUARING, he_mul(&ct, &ct, &ct, rlk) (src/he-algo.c:151 and the repeated squarings of he_exp / he_inv call
@@ -750,26 +761,15 @@ __global__ __launch_bounds__(CONTIG_WAVES * 64, GPQ_MID8_MINWAVES) void tensor_m
 template <typename TW, int LOW, bool NT = false>
 __global__ __launch_bounds__(CONTIG_WAVES * 64, GPQ_MID8_MINWAVES) void tensor_sq_mid8(PassArgs a) {
   using TT = TwTraits<TW>;
-  using L8 = Lane8N<LOW, NT>;
   __shared__ uint64_t lds[CONTIG_WAVES * LANE8_LDS_PER_WAVE];
-  L8 ln(lds + (threadIdx.x >> 6) * LANE8_LDS_PER_WAVE);
-  const Block8 cb(a);
-  const PrimeK k = pin_consts(a.tabs[cb.limb].k);
-  const TW *__restrict__ wf = TT::table(a, false) + cb.toff, *__restrict__ wi = TT::table(a, true) + cb.toff;
   uint64_t a0[8], a1[8];
-  Tw8<TW, LOW> tw;
-  ln.load_h(a0, a.src[0] + cb.off);
-  tw.load_h(ln, cb.wave0, a.logn, wf);
-  ln.load_h(a1, a.src[1] + cb.off);
-  L8::ct_h(a0, tw.t, k);
-  L8::ct_h(a1, tw.t, k);
-  tw.load_m(ln, cb.wave0, a.logn, wf);
-  ln.h_to_m(a0); L8::ct_m(a0, tw.t, k);
-  ln.h_to_m(a1); L8::ct_m(a1, tw.t, k);
-  tw.load_l(ln, cb.wave0, a.logn, wf);
-  ln.m_to_l(a0); L8::ct_l(a0, tw.u, k);
-  ln.m_to_l(a1); L8::ct_l(a1, tw.u, k);
-  tw.load_l(ln, cb.wave0, a.logn, wi);
+  Mid8<TW, LOW, NT> s(lds, a);
+  const size_t off = s.off(a, blockIdx.y);
+  const PrimeK &k = s.k;
+  s.load_first(a0, a.src[0] + off);
+  s.load(a1, a.src[1] + off);
+  s.forward(a0, a1);
+  s.load_inverse_l();
   uint64_t d1[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) {                      // left operand < 2p or < 4p, right operand as it comes: the ranges of tensor_mid8
@@ -780,20 +780,10 @@ __global__ __launch_bounds__(CONTIG_WAVES * 64, GPQ_MID8_MINWAVES) void tensor_s
     d1[e] = TT::inv_from8(cross + cross, k);                                            // d1
     a1[e] = TT::inv_from4(mulmod_lazy(u1, v1, k), k);                                   // d2
   }
-  L8::gs_l(a0, tw.u, k); ln.l_to_m(a0);
-  L8::gs_l(d1, tw.u, k); ln.l_to_m(d1);
-  L8::gs_l(a1, tw.u, k); ln.l_to_m(a1);
-  tw.load_m(ln, cb.wave0, a.logn, wi);
-  L8::gs_hm(a0, tw.t, k); ln.m_to_h(a0);
-  L8::gs_hm(d1, tw.t, k); ln.m_to_h(d1);
-  L8::gs_hm(a1, tw.t, k); ln.m_to_h(a1);
-  tw.load_h(ln, cb.wave0, a.logn, wi);
-  L8::gs_hm(a0, tw.t, k);
-  ln.store_h(a.dst[0] + cb.off, a0);
-  L8::gs_hm(d1, tw.t, k);
-  ln.store_h(a.dst[1] + cb.off, d1);
-  L8::gs_hm(a1, tw.t, k);
-  ln.store_h(a.dst[2] + cb.off, a1);
+  s.inverse(a0, d1, a1);
+  s.finish(a0); s.ln.store_h(a.dst[0] + off, a0);
+  s.finish(d1); s.ln.store_h(a.dst[1] + off, d1);
+  s.finish(a1); s.ln.store_h(a.dst[2] + off, a1);
 }
 
 // Middle of poly_mul's limb loop (src/poly.c:96-103): low forward stages of a and b, a (*) b, low inverse stages.
@@ -802,34 +792,19 @@ __global__ __launch_bounds__(CONTIG_WAVES * 64, GPQ_MID8_MINWAVES) void tensor_s
 template <typename TW, int LOW, bool NT = false>
 __global__ __launch_bounds__(CONTIG_WAVES * 64, 4) void polymul_mid8(PassArgs a) {
   using TT = TwTraits<TW>;
-  using L8 = Lane8N<LOW, NT>;
   __shared__ uint64_t lds[CONTIG_WAVES * LANE8_LDS_PER_WAVE];
-  L8 ln(lds + (threadIdx.x >> 6) * LANE8_LDS_PER_WAVE);
-  const Block8 cb(a);
-  const PrimeK k = pin_consts(a.tabs[cb.limb].k);
-  const TW *__restrict__ wf = TT::table(a, false) + cb.toff, *__restrict__ wi = TT::table(a, true) + cb.toff;
   uint64_t x[8], y[8];
-  Tw8<TW, LOW> tw;
-  ln.load_h(x, a.src[0] + cb.off);
-  tw.load_h(ln, cb.wave0, a.logn, wf);
-  ln.load_h(y, a.src[1] + cb.off);
-  L8::ct_h(x, tw.t, k);
-  L8::ct_h(y, tw.t, k);
-  tw.load_m(ln, cb.wave0, a.logn, wf);
-  ln.h_to_m(x); L8::ct_m(x, tw.t, k);
-  ln.h_to_m(y); L8::ct_m(y, tw.t, k);
-  tw.load_l(ln, cb.wave0, a.logn, wf);
-  ln.m_to_l(x); L8::ct_l(x, tw.u, k);
-  ln.m_to_l(y); L8::ct_l(y, tw.u, k);
-  tw.load_l(ln, cb.wave0, a.logn, wi);
+  Mid8<TW, LOW, NT> s(lds, a);
+  const size_t off = s.off(a, blockIdx.y);
+  const PrimeK &k = s.k;
+  s.load_first(x, a.src[0] + off);
+  s.load(y, a.src[1] + off);
+  s.forward(x, y);
+  s.load_inverse_l();
 #pragma unroll
   for (int e = 0; e < 8; ++e) x[e] = TT::inv_from4(mulmod_lazy(TT::left(x[e], k), TT::right(y[e], k), k), k);
-  L8::gs_l(x, tw.u, k); ln.l_to_m(x);
-  tw.load_m(ln, cb.wave0, a.logn, wi);
-  L8::gs_hm(x, tw.t, k); ln.m_to_h(x);
-  tw.load_h(ln, cb.wave0, a.logn, wi);
-  L8::gs_hm(x, tw.t, k);
-  ln.store_h(a.dst[0] + cb.off, x);
+  s.inverse(x);
+  s.finish(x); s.ln.store_h(a.dst[0] + off, x);
 }
 
 // Middle of he_mulpt's limb loop (src/he-mult.c:179-185): low forward stages of m, c0, c1, then m (*) c0 and m (*) c1,
@@ -837,52 +812,66 @@ __global__ __launch_bounds__(CONTIG_WAVES * 64, 4) void polymul_mid8(PassArgs a)
 template <typename TW, int LOW, bool NT = false>
 __global__ __launch_bounds__(CONTIG_WAVES * 64, 3) void mulpt_mid8(PassArgs a) {
   using TT = TwTraits<TW>;
-  using L8 = Lane8N<LOW, NT>;
   __shared__ uint64_t lds[CONTIG_WAVES * LANE8_LDS_PER_WAVE];
-  L8 ln(lds + (threadIdx.x >> 6) * LANE8_LDS_PER_WAVE);
-  const Block8 cb(a);
-  const PrimeK k = pin_consts(a.tabs[cb.limb].k);
-  const TW *__restrict__ wf = TT::table(a, false) + cb.toff, *__restrict__ wi = TT::table(a, true) + cb.toff;
   uint64_t m[8], x[8], y[8];
-  Tw8<TW, LOW> tw;
-  ln.load_h(m, a.src[0] + cb.off);
-  tw.load_h(ln, cb.wave0, a.logn, wf);
-  ln.load_h(x, a.src[1] + cb.off);
-  ln.load_h(y, a.src[2] + cb.off);
-  L8::ct_h(m, tw.t, k);
-  L8::ct_h(x, tw.t, k);
-  L8::ct_h(y, tw.t, k);
-  tw.load_m(ln, cb.wave0, a.logn, wf);
-  ln.h_to_m(m); L8::ct_m(m, tw.t, k);
-  ln.h_to_m(x); L8::ct_m(x, tw.t, k);
-  ln.h_to_m(y); L8::ct_m(y, tw.t, k);
-  tw.load_l(ln, cb.wave0, a.logn, wf);
-  ln.m_to_l(m); L8::ct_l(m, tw.u, k);
-  ln.m_to_l(x); L8::ct_l(x, tw.u, k);
-  ln.m_to_l(y); L8::ct_l(y, tw.u, k);
-  tw.load_l(ln, cb.wave0, a.logn, wi);
+  Mid8<TW, LOW, NT> s(lds, a);
+  const size_t off = s.off(a, blockIdx.y);
+  const PrimeK &k = s.k;
+  s.load_first(m, a.src[0] + off);
+  s.load(x, a.src[1] + off);
+  s.load(y, a.src[2] + off);
+  s.forward(m, x, y);
+  s.load_inverse_l();
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
     const uint64_t u = TT::left(m[e], k);
     x[e] = TT::inv_from4(mulmod_lazy(u, TT::right(x[e], k), k), k);
     y[e] = TT::inv_from4(mulmod_lazy(u, TT::right(y[e], k), k), k);
   }
-  L8::gs_l(x, tw.u, k); ln.l_to_m(x);
-  L8::gs_l(y, tw.u, k); ln.l_to_m(y);
-  tw.load_m(ln, cb.wave0, a.logn, wi);
-  L8::gs_hm(x, tw.t, k); ln.m_to_h(x);
-  L8::gs_hm(y, tw.t, k); ln.m_to_h(y);
-  tw.load_h(ln, cb.wave0, a.logn, wi);
-  L8::gs_hm(x, tw.t, k);
-  ln.store_h(a.dst[0] + cb.off, x);
-  L8::gs_hm(y, tw.t, k);
-  ln.store_h(a.dst[1] + cb.off, y);
+  s.inverse(x, y);
+  s.finish(x); s.ln.store_h(a.dst[0] + off, x);
+  s.finish(y); s.ln.store_h(a.dst[1] + off, y);
+}
+
+// The key limbs and the products of the two key-switch middles, from x0 (and x1) in the L layout and the NTT domain, in the right-operand range
+// of their class (canonical words are inside every class's): x0, x1 become x0 * evk0, x1 * evk0; y0, y1 = x0 * evk1, x1 * evk1.  A macro over
+// the kernel's own names: with the key arrays and the loops in a function, or the loop behind a lambda, keyswitch_rot_mid8x2 compiles to
+// other code (29 fewer VALU instructions and 12 more registers in its single form on wide limbs at LOW = 9, for one).
+#define GPQ_KEYSWITCH_PRODUCTS()                                  \
+  s.ln.load_l(e0, ka.evk0 + koff);                                \
+  s.ln.load_l(e1, ka.evk1 + koff);                                \
+  s.load_inverse_l();                                             \
+  uint64_t y0[8], y1[8];                                          \
+  _Pragma("unroll") for (int e = 0; e < 8; ++e) {                 \
+    const uint64_t u0 = TT::right(x0[e], k);                      \
+    x0[e] = TT::inv_from4(mulmod_lazy(u0, e0[e], k), k);          \
+    y0[e] = TT::inv_from4(mulmod_lazy(u0, e1[e], k), k);          \
+  }                                                               \
+  if constexpr (TWO) {                                            \
+    _Pragma("unroll") for (int e = 0; e < 8; ++e) {               \
+      const uint64_t u1 = TT::right(x1[e], k);                    \
+      x1[e] = TT::inv_from4(mulmod_lazy(u1, e0[e], k), k);        \
+      y1[e] = TT::inv_from4(mulmod_lazy(u1, e1[e], k), k);        \
+    }                                                             \
+  }
+// ... and their common end: the inverse low stages of the two or four products, dst[0..1] at off0 (and off1).
+template <bool TWO, typename S>
+__device__ __forceinline__ void keyswitch_back(S &s, const PassArgs &a, uint64_t (&x0)[8], uint64_t (&y0)[8], uint64_t (&x1)[8], uint64_t (&y1)[8], size_t off0, size_t off1) {
+  if constexpr (TWO) s.inverse(x0, y0, x1, y1);
+  else s.inverse(x0, y0);
+  s.finish(x0); s.ln.store_h(a.dst[0] + off0, x0);
+  s.finish(y0); s.ln.store_h(a.dst[1] + off0, y0);
+  if constexpr (TWO) {
+    s.finish(x1); s.ln.store_h(a.dst[0] + off1, x1);
+    s.finish(y1); s.ln.store_h(a.dst[1] + off1, y1);
+  }
 }
 
 // Key switch with TWO polynomials of the same limb and tile per workgroup: the key limbs (shared by the batch) and every
 // twiddle group are fetched once for both -- per polynomial the 16-per-lane kernel reads 960 B of twiddle pairs and 256 B
 // of key per lane against 384 B of its own data -- and the four products of a pair run like the tensor stage (2 forward
-// low-halves, 4 inverse ones).  blockIdx.y = pair of polynomials starting at `first`; an odd last polynomial runs alone in the TWO = false instantiation.
+// low-halves, 4 inverse ones).  An odd last polynomial of a batch (a single ciphertext is the reference's calling pattern) runs alone
+// in the TWO = false instantiation -- under a run-time branch the pair form needs 168 registers instead of 116.
 // Register budget: the pair form is compiled for four waves per SIMD (<= 128 VGPRs).  At LOW = 8 its code object stood there anyway (126)
 // until the multiplies lost their trailing add; with the looser budget of three waves the scheduler then spreads to 168 registers and
 // spills 22 of them: 9 % slower with 7.7 % fewer instructions.  Stated, the budget gives 122 registers and no spill.  At LOW = 9 (135
@@ -891,75 +880,21 @@ __global__ __launch_bounds__(CONTIG_WAVES * 64, 3) void mulpt_mid8(PassArgs a) {
 template <typename TW, int LOW, bool TWO = true, bool NT = false>
 __global__ __launch_bounds__(CONTIG_WAVES * 64, TWO ? 4 : 3) void keyswitch_mid8x2(KeyswitchArgs ka, unsigned first) {
   using TT = TwTraits<TW>;
-  using L8 = Lane8N<LOW, NT>;
   __shared__ uint64_t lds[CONTIG_WAVES * LANE8_LDS_PER_WAVE];
   const PassArgs &a = ka.p;
-  L8 ln(lds + (threadIdx.x >> 6) * LANE8_LDS_PER_WAVE);
-  const unsigned wave0 = (blockIdx.x * CONTIG_WAVES + (threadIdx.x >> 6)) << 9;
-  const unsigned limb = a.limb0 + blockIdx.z;
-  const PrimeK k = pin_consts(a.tabs[limb].k);
-  const size_t toff = (size_t)limb << a.logn;
-  const TW *__restrict__ wf = TT::table(a, false) + toff, *__restrict__ wi = TT::table(a, true) + toff;
-  const unsigned p0 = first + 2 * blockIdx.y;  // TWO = false: the odd last polynomial of a batch (a single ciphertext is the reference's calling pattern) alone,
-  constexpr bool two = TWO;                    // in its own instantiation -- under a run-time branch the pair form needs 168 registers instead of 116
-  const size_t off0 = (size_t)p0 * a.poly_stride + ((size_t)blockIdx.z << a.logn) + wave0;
-  const size_t off1 = two ? off0 + a.poly_stride : off0;
-  const size_t koff = ((size_t)blockIdx.z << a.logn) + wave0;
+  Mid8<TW, LOW, NT> s(lds, a);
+  const unsigned wave0 = s.wave0;
+  const PrimeK &k = s.k;
+  const unsigned p0 = first + 2 * blockIdx.y;   // blockIdx.y = pair of polynomials starting at `first`
+  const size_t off0 = s.off(a, p0);
+  const size_t off1 = TWO ? off0 + a.poly_stride : off0;
+  const size_t koff = ((size_t)blockIdx.z << a.logn) + wave0;       // the key limbs have no poly stride
   uint64_t x0[8], x1[8], e0[8], e1[8];
-  Tw8<TW, LOW> tw;
-  ln.load_h(x0, a.src[0] + off0);
-  tw.load_h(ln, wave0, a.logn, wf);
-  if constexpr (two) ln.load_h(x1, a.src[0] + off1);
-  L8::ct_h(x0, tw.t, k);
-  if constexpr (two) L8::ct_h(x1, tw.t, k);
-  tw.load_m(ln, wave0, a.logn, wf);
-  ln.h_to_m(x0); L8::ct_m(x0, tw.t, k);
-  if constexpr (two) { ln.h_to_m(x1); L8::ct_m(x1, tw.t, k); }
-  tw.load_l(ln, wave0, a.logn, wf);
-  ln.m_to_l(x0); L8::ct_l(x0, tw.u, k);
-  if constexpr (two) { ln.m_to_l(x1); L8::ct_l(x1, tw.u, k); }
-  ln.load_l(e0, ka.evk0 + koff);
-  ln.load_l(e1, ka.evk1 + koff);
-  tw.load_l(ln, wave0, a.logn, wi);
-  uint64_t y0[8], y1[8];                        // x0 * evk1, x1 * evk1;  x0, x1 become x0 * evk0, x1 * evk0
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const uint64_t u0 = TT::right(x0[e], k);
-    x0[e] = TT::inv_from4(mulmod_lazy(u0, e0[e], k), k);
-    y0[e] = TT::inv_from4(mulmod_lazy(u0, e1[e], k), k);
-  }
-  if constexpr (two) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const uint64_t u1 = TT::right(x1[e], k);
-      x1[e] = TT::inv_from4(mulmod_lazy(u1, e0[e], k), k);
-      y1[e] = TT::inv_from4(mulmod_lazy(u1, e1[e], k), k);
-    }
-  }
-  L8::gs_l(x0, tw.u, k); ln.l_to_m(x0);
-  L8::gs_l(y0, tw.u, k); ln.l_to_m(y0);
-  if constexpr (two) {
-    L8::gs_l(x1, tw.u, k); ln.l_to_m(x1);
-    L8::gs_l(y1, tw.u, k); ln.l_to_m(y1);
-  }
-  tw.load_m(ln, wave0, a.logn, wi);
-  L8::gs_hm(x0, tw.t, k); ln.m_to_h(x0);
-  L8::gs_hm(y0, tw.t, k); ln.m_to_h(y0);
-  if constexpr (two) {
-    L8::gs_hm(x1, tw.t, k); ln.m_to_h(x1);
-    L8::gs_hm(y1, tw.t, k); ln.m_to_h(y1);
-  }
-  tw.load_h(ln, wave0, a.logn, wi);
-  L8::gs_hm(x0, tw.t, k);
-  ln.store_h(a.dst[0] + off0, x0);
-  L8::gs_hm(y0, tw.t, k);
-  ln.store_h(a.dst[1] + off0, y0);
-  if constexpr (two) {
-    L8::gs_hm(x1, tw.t, k);
-    ln.store_h(a.dst[0] + off1, x1);
-    L8::gs_hm(y1, tw.t, k);
-    ln.store_h(a.dst[1] + off1, y1);
-  }
+  s.load_first(x0, a.src[0] + off0);
+  if constexpr (TWO) { s.load(x1, a.src[0] + off1); s.forward(x0, x1); }
+  else s.forward(x0);
+  GPQ_KEYSWITCH_PRODUCTS();
+  keyswitch_back<TWO>(s, a, x0, y0, x1, y1, off0, off1);
 }
 
 // ---------------------------------------------------------------------------
@@ -986,20 +921,17 @@ __global__ __launch_bounds__(CONTIG_WAVES * 64, TWO ? 4 : 3) void keyswitch_rot_
   using L8 = Lane8N<LOW, NT>;
   __shared__ uint64_t lds[CONTIG_WAVES * LANE8_LDS_PER_WAVE];
   const PassArgs &a = ka.p;
-  L8 ln(lds + (threadIdx.x >> 6) * LANE8_LDS_PER_WAVE);
-  const unsigned wave0 = (blockIdx.x * CONTIG_WAVES + (threadIdx.x >> 6)) << 9;
-  const unsigned limb = a.limb0 + blockIdx.z;
-  const PrimeK k = pin_consts(a.tabs[limb].k);
-  const size_t toff = (size_t)limb << a.logn;
-  const TW *__restrict__ wi = TT::table(a, true) + toff;
-  const unsigned p0 = first + 2 * blockIdx.y;
-  constexpr bool two = TWO;
-  const size_t off0 = (size_t)p0 * a.poly_stride + ((size_t)blockIdx.z << a.logn) + wave0;
-  const size_t off1 = two ? off0 + a.poly_stride : off0;
-  const size_t koff = ((size_t)blockIdx.z << a.logn) + wave0;
+  Mid8<TW, LOW, NT> s(lds, a);
+  const unsigned wave0 = s.wave0;
+  const PrimeK &k = s.k;
+  const unsigned p0 = first + 2 * blockIdx.y;   // blockIdx.y = pair of polynomials starting at `first`
+  const size_t off0 = (size_t)p0 * a.poly_stride + ((size_t)blockIdx.z << a.logn) + wave0;    // s.off(a, p0), written out: the compiler folds the wave0 of soff0 / soff1 below away only here (one v_mad_u64_u32)
+  const size_t off1 = TWO ? off0 + a.poly_stride : off0;
+  const size_t koff = ((size_t)blockIdx.z << a.logn) + wave0;       // the key limbs have no poly stride
+  const L8 &ln = s.ln;
   const unsigned src0 = automorphism_src(wave0, a.logn, g) & ~511u;    // the source tile (one per wave, see above)
   const size_t soff0 = off0 - wave0 + src0, soff1 = off1 - wave0 + src0;
-  unsigned sl[8];                                                       // in-tile source of the lane's L-layout words
+  unsigned sl[8];                                                          // in-tile source of the lane's L-layout words
 #pragma unroll
   for (int e = 0; e < 8; ++e) sl[e] = automorphism_src(wave0 + ln.lk + e, a.logn, g) & 511u;
   auto gather = [&](uint64_t (&x)[8], size_t soff) {
@@ -1012,52 +944,12 @@ __global__ __launch_bounds__(CONTIG_WAVES * 64, TWO ? 4 : 3) void keyswitch_rot_
     wave_lds_sync();
   };
   uint64_t x0[8], x1[8], e0[8], e1[8];
-  Tw8<TW, LOW> tw;
   gather(x0, soff0);
-  if constexpr (two) gather(x1, soff1);
-  ln.load_l(e0, ka.evk0 + koff);
-  ln.load_l(e1, ka.evk1 + koff);
-  tw.load_l(ln, wave0, a.logn, wi);
-  uint64_t y0[8], y1[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const uint64_t u0 = TT::right(x0[e], k);          // canonical words: inside every class's right-operand range
-    x0[e] = TT::inv_from4(mulmod_lazy(u0, e0[e], k), k);
-    y0[e] = TT::inv_from4(mulmod_lazy(u0, e1[e], k), k);
-  }
-  if constexpr (two) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const uint64_t u1 = TT::right(x1[e], k);
-      x1[e] = TT::inv_from4(mulmod_lazy(u1, e0[e], k), k);
-      y1[e] = TT::inv_from4(mulmod_lazy(u1, e1[e], k), k);
-    }
-  }
-  L8::gs_l(x0, tw.u, k); ln.l_to_m(x0);
-  L8::gs_l(y0, tw.u, k); ln.l_to_m(y0);
-  if constexpr (two) {
-    L8::gs_l(x1, tw.u, k); ln.l_to_m(x1);
-    L8::gs_l(y1, tw.u, k); ln.l_to_m(y1);
-  }
-  tw.load_m(ln, wave0, a.logn, wi);
-  L8::gs_hm(x0, tw.t, k); ln.m_to_h(x0);
-  L8::gs_hm(y0, tw.t, k); ln.m_to_h(y0);
-  if constexpr (two) {
-    L8::gs_hm(x1, tw.t, k); ln.m_to_h(x1);
-    L8::gs_hm(y1, tw.t, k); ln.m_to_h(y1);
-  }
-  tw.load_h(ln, wave0, a.logn, wi);
-  L8::gs_hm(x0, tw.t, k);
-  ln.store_h(a.dst[0] + off0, x0);
-  L8::gs_hm(y0, tw.t, k);
-  ln.store_h(a.dst[1] + off0, y0);
-  if constexpr (two) {
-    L8::gs_hm(x1, tw.t, k);
-    ln.store_h(a.dst[0] + off1, x1);
-    L8::gs_hm(y1, tw.t, k);
-    ln.store_h(a.dst[1] + off1, y1);
-  }
+  if constexpr (TWO) gather(x1, soff1);
+  GPQ_KEYSWITCH_PRODUCTS();
+  keyswitch_back<TWO>(s, a, x0, y0, x1, y1, off0, off1);
 }
+#undef GPQ_KEYSWITCH_PRODUCTS
 
 // The same permutation on single-pass rings (n <= 2^12), as a plain gather: dst[row][j] = src[row][sigma(j)] over rows of n words
 // (polynomial x limb), one thread per word.  gpq_rns_mul and gpq_invntt follow.

@@ -1,5 +1,6 @@
 """The butterflies with the (c+1) correction folded into mad addends (gpqhe_amd/csrc/modarith.hpp: mulmod_split, mulmod_raw_t)
 against the oracle, word for word: every butterfly class, the smallest two-pass ring and the nine-low-stage ring, an odd batch,
+every fused middle (tensor, squaring, key switch in its pair and single forms, poly_mul, he_mulpt) under both cache policies,
 and the inputs that sit on the edges of the lazy ranges -- all-zero, all p - 1, and polynomials whose transform holds
 residues 0 (a lazy value may now be 0 where it was p; canonical outputs, and the reference's stored p, must not move).
 The integer model of the same code is tests/test_inject_ranges.py."""
@@ -43,12 +44,16 @@ def _inputs(o, logn, dim):
     exp["tensor"] = [o.he_mul_tensor(*[v[k * per:(k + 1) * per].copy() for v in quad], dim) for k in range(BATCH)]
     exp["square"] = [o.he_mul_tensor(*[v[k * per:(k + 1) * per].copy() for v in (edge, mix, edge, mix)], dim) for k in range(BATCH)]
     exp["keyswitch"] = [[o.keyswitch(x[k * per:(k + 1) * per].copy(), keys[0], keys[1], dim) for k in range(BATCH)] for x in (edge, mix)]
+    one = lambda v, k: v[k * per:(k + 1) * per].copy()
+    exp["polymul"] = [o.poly_mul_rns(one(edge, k), one(mix, k), dim) for k in range(BATCH)]
+    exp["mulpt"] = [[o.poly_mul_rns(one(rnd[0], k), one(x, k), dim) for k in range(BATCH)] for x in (edge, mix)]     # m x0, m x1
     _SHARED[logn, dim] = (edge, mix, rnd, keys, exp)
     return _SHARED[logn, dim]
 
 
+@pytest.mark.parametrize("nt", [0, 1])          # both cache-policy instantiations of every kernel (the expectations are cached per ring)
 @pytest.mark.parametrize("logn,dim,classes", CASES)
-def test_injected_butterflies_match_the_oracle(oracle_ctx, logn, dim, classes):
+def test_injected_butterflies_match_the_oracle(oracle_ctx, logn, dim, classes, nt):
     import torch
     o = oracle_ctx(logn, dim)
     edge, mix, rnd, keys, exp = _inputs(o, logn, dim)
@@ -56,6 +61,7 @@ def test_injected_butterflies_match_the_oracle(oracle_ctx, logn, dim, classes):
     try:
         assert g.p == o.p
         g.set_limb_classes(*classes)
+        g.set_nt_policy(nt)
         per = dim * o.n
         for i, v in enumerate((edge, mix)):          # gpq_ntt, gpq_invntt
             dev = to_device(v)
@@ -84,5 +90,12 @@ def test_injected_butterflies_match_the_oracle(oracle_ctx, logn, dim, classes):
             for k in range(BATCH):
                 f0, f1 = exp["keyswitch"][i][k]
                 assert np.array_equal(h0[k * per:(k + 1) * per], f0) and np.array_equal(h1[k * per:(k + 1) * per], f1), "key switch, slab %d, polynomial %d" % (i, k)
+        r = torch.empty_like(de)                     # gpq_poly_mul_rns (it overwrites its inputs: clones)
+        g.poly_mul_rns(r, de.clone(), dm.clone(), dim)
+        assert np.array_equal(to_host(r), np.concatenate(exp["polymul"])), "gpq_poly_mul_rns"
+        p0, p1 = torch.empty_like(de), torch.empty_like(de)   # gpq_mulpt_rns: m x0, m x1 (clones again)
+        g.mulpt_rns(p0, p1, r0.clone(), de.clone(), dm.clone(), dim)
+        assert np.array_equal(to_host(p0), np.concatenate(exp["mulpt"][0])), "gpq_mulpt_rns, m x0"
+        assert np.array_equal(to_host(p1), np.concatenate(exp["mulpt"][1])), "gpq_mulpt_rns, m x1"
     finally:
         g.close()
