@@ -134,6 +134,13 @@ SIGNATURES = {
     "gpq_gemv_plan_destroy": (None, [vp]),
     "gpq_gemv_plan_info": (C.c_int, [vp, C.POINTER(C.c_uint), C.POINTER(C.c_size_t), C.POINTER(C.c_uint), C.POINTER(C.c_int)]),
     "gpq_gemv_plan_rotations": (C.c_int, [vp, vp]),
+    "gpq_gemv_plan_diag_bits": (C.c_uint, [vp]),
+    "gpq_ecd_roots": (C.c_int, [vp, C.c_uint]),
+    "gpq_ecd_plan_create": (C.c_int, [vp, C.POINTER(vp), C.c_uint, vp, C.c_uint]),
+    "gpq_ecd_plan_destroy": (None, [vp]),
+    "gpq_he_ecd": (C.c_int, [vp, vp, vp, vp, C.c_uint, C.c_uint, C.c_uint, vp, vp]),
+    "gpq_he_ecd_diagonals": (C.c_int, [vp, vp, vp, vp, C.c_uint, C.c_uint, vp, vp]),
+    "gpq_gemv_plan_create_from_matrix": (C.c_int, [vp, C.POINTER(vp), vp, vp, C.c_uint, C.c_uint, C.c_uint, vp]),
     "gpq_shim_gemv_plan_cache": (None, [C.c_uint]),
     "gpq_gemv_inner_workspace_bytes": (C.c_size_t, [vp, vp, C.c_uint]),
     "gpq_gemv_inner": (C.c_int, [vp] * 6 + [C.c_uint] * 3 + [vp, vp]),
@@ -174,6 +181,7 @@ SIGNATURES = {
     "gpq_mpi_shim_poly_bypass": (None, [C.c_int]),
     "gpq_mpi_shim_set_direct_mpi": (C.c_int, [C.c_int]),
     "gpq_mpi_shim_last_timing": (None, [C.POINTER(C.c_double)]),
+    "gpq_mpi_shim_set_device_ecd": (None, [C.c_int]),
     "gpq_fill_rns_chain": (C.c_int, [vp, C.c_uint, vp, C.c_int]),
     "gpq_release_rns_chain": (None, [vp]),
 }

@@ -1,0 +1,165 @@
+// ecd.hip -- the encoder on the device (include/gpqhe_hip.h, "he_ecd"): the root table, the per-slot-count plan, gpq_he_ecd /
+// gpq_he_ecd_diagonals (kernel: ecd_kernels.hpp) and gpq_gemv_plan_create_from_matrix, which encodes a matrix's diagonals into a one-word
+// slab and hands it to gpq_gemv_plan_create.
+#include <hip/hip_runtime.h>
+#include "../../include/gpqhe_hip.h"
+#include "engine_internal.hpp"
+#include "ecd_kernels.hpp"
+
+#include <cmath>
+#include <memory>
+#include <new>
+#include <vector>
+
+using namespace gpq;
+
+#define HIP_TRY(expr)                                                                      \
+  do {                                                                                     \
+    hipError_t e_ = (expr);                                                                \
+    if (e_ != hipSuccess) return gpq_fail(GPQ_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
+  } while (0)
+
+struct gpq_ecd_plan {
+  gpq_ctx *ctx = nullptr;
+  unsigned slots = 0, logslots = 0;
+  double2 *d_roots = nullptr;      // T[0 .. 4 slots]
+  uint32_t *d_pow5 = nullptr;      // 5^j mod 4 slots
+  uint32_t *d_bad = nullptr;       // gpq_gemv_plan_create_from_matrix's own counter ...
+  uint32_t *h_bad = nullptr;       // ... and the page-locked word it is read through
+};
+
+namespace {
+bool pow2(unsigned v) { return v && !(v & (v - 1)); }
+unsigned log2u(unsigned v) { unsigned b = 0; while ((1u << b) < v) ++b; return b; }
+void gemv_split(unsigned slots, unsigned *n1) {               // src/he-algo.c:51-54
+  unsigned a = (unsigned)std::sqrt((double)slots);
+  if (slots != a * a) a = (unsigned)std::sqrt((double)(2 * slots));
+  *n1 = a;
+}
+
+int encode(gpq_ctx *c, const gpq_ecd_plan *p, uint64_t *out, const double *src, unsigned logDelta, unsigned W, unsigned count, unsigned n1,
+           uint32_t *bad, void *stream, const char *who) {
+  if (!c) return gpq_fail(GPQ_ERR_INVALID, "%s: null context", who);
+  if (!p || p->ctx != c) return gpq_fail(GPQ_ERR_INVALID, "%s: no plan, or a plan of another context", who);
+  if (!out || !src || !count) return gpq_fail(GPQ_ERR_INVALID, "%s: null argument or empty batch", who);
+  if (W < 1 || W > 32) return gpq_fail(GPQ_ERR_INVALID, "%s: W = %u outside 1..32", who, W);
+  if (logDelta > 63) return gpq_fail(GPQ_ERR_INVALID, "%s: Delta = 2^%u is not a 64-bit Delta (src/gpqhe.h:100)", who, logDelta);
+  int dev = -1;
+  if (hipGetDevice(&dev) == hipSuccess && dev != c->device)
+    return gpq_fail(GPQ_ERR_INVALID, "%s: the context lives on device %d but the calling thread's current device is %d (gpq_set_device(gpq_ctx_device(ctx)) first)", who, c->device, dev);
+  static bool raised[64] = {};
+  const size_t lds = (size_t)p->slots * 16;
+  if (lds > 65536 && !(dev >= 0 && dev < 64 && raised[dev])) {            // dynamic LDS above 64 KB needs the attribute, once per device
+    HIP_TRY(hipFuncSetAttribute((const void *)he_ecd_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kEcdMaxSlots * 16)));
+    if (dev >= 0 && dev < 64) raised[dev] = true;
+  }
+  EcdArgs a{src, out, p->d_roots, p->d_pow5, bad, std::ldexp(1.0, (int)logDelta), 1.0 / p->slots, p->slots, p->logslots, c->logn, W, n1};
+  const unsigned threads = (p->slots / 2 >= kEcdMaxThreads || ((size_t)W << c->logn) >= 8192) ? kEcdMaxThreads : 256u;
+  hipStream_t s = (hipStream_t)stream;
+  {
+    ProfScope prof(c, GPQ_K_ECD, s);
+    hipLaunchKernelGGL(he_ecd_lds, dim3(count), dim3(threads), lds, s, a);
+  }
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? GPQ_OK : gpq_fail(GPQ_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(e));
+}
+}  // namespace
+
+extern "C" int gpq_ecd_roots(double *table, unsigned slots) {
+  if (!table || !pow2(slots) || slots > (1u << 28)) return gpq_fail(GPQ_ERR_INVALID, "gpq_ecd_roots: slots = %u must be a power of two", slots);
+  const unsigned m4 = 4 * slots;
+  for (unsigned t = 0; t < m4; ++t) {
+    const double theta = 2 * 3.141592653589793238462643383279502884 * t / m4;     // src/precomp.c:307, src/params.h:52
+    double sn, cs;
+    sincos(theta, &sn, &cs);                                                       // what gcc -O2 makes of :308
+    table[2 * t] = cs; table[2 * t + 1] = sn;
+  }
+  table[2 * m4] = table[0]; table[2 * m4 + 1] = table[1];                           // :310
+  return GPQ_OK;
+}
+
+extern "C" void gpq_ecd_plan_destroy(gpq_ecd_plan *p) {
+  if (!p) return;
+  DeviceScope on_device(p->ctx->device);
+  if (p->d_roots) (void)hipFree(p->d_roots);
+  if (p->d_pow5) (void)hipFree(p->d_pow5);
+  if (p->d_bad) (void)hipFree(p->d_bad);
+  if (p->h_bad) (void)hipHostFree(p->h_bad);
+  delete p;
+}
+
+extern "C" int gpq_ecd_plan_create(gpq_ctx *c, gpq_ecd_plan **out, unsigned slots, const double *roots, unsigned roots_slots) {
+  if (!c || !out) return gpq_fail(GPQ_ERR_INVALID, "gpq_ecd_plan_create: null argument");
+  if (!pow2(slots) || slots > c->n / 2)
+    return gpq_fail(GPQ_ERR_INVALID, "gpq_ecd_plan_create: slots = %u must be a power of two up to n/2 = %u", slots, c->n / 2);
+  if (slots > kEcdMaxSlots)
+    return gpq_fail(GPQ_ERR_INVALID, "gpq_ecd_plan_create: %u slots exceed the %u one workgroup holds in LDS", slots, kEcdMaxSlots);
+  if (roots && (!pow2(roots_slots) || roots_slots < slots))
+    return gpq_fail(GPQ_ERR_INVALID, "gpq_ecd_plan_create: the root table is for %u slots: a power of two >= %u is needed", roots_slots, slots);
+  const unsigned m4 = 4 * slots;
+  std::vector<double> T(2 * (size_t)(m4 + 1));
+  if (roots) {
+    const size_t stride = roots_slots / slots;
+    for (unsigned t = 0; t <= m4; ++t) { T[2 * t] = roots[2 * t * stride]; T[2 * t + 1] = roots[2 * t * stride + 1]; }
+  } else {
+    int rc = gpq_ecd_roots(T.data(), slots);
+    if (rc) return rc;
+  }
+  std::vector<uint32_t> pow5(slots / 2 ? slots / 2 : 1);
+  uint32_t g = 1;
+  for (uint32_t &v : pow5) { v = g; g = (uint32_t)((5ull * g) % m4); }
+  std::unique_ptr<gpq_ecd_plan, void (*)(gpq_ecd_plan *)> p(new (std::nothrow) gpq_ecd_plan(), gpq_ecd_plan_destroy);
+  if (!p) return gpq_fail(GPQ_ERR_NOMEM, "out of host memory");
+  p->ctx = c; p->slots = slots; p->logslots = log2u(slots);
+  DeviceScope on_device(c->device);
+  HIP_TRY(hipMalloc((void **)&p->d_roots, T.size() * sizeof(double)));
+  HIP_TRY(hipMalloc((void **)&p->d_pow5, pow5.size() * sizeof(uint32_t)));
+  HIP_TRY(hipMalloc((void **)&p->d_bad, sizeof(uint32_t)));
+  HIP_TRY(hipHostMalloc((void **)&p->h_bad, sizeof(uint32_t), hipHostMallocDefault));
+  HIP_TRY(hipMemcpy(p->d_roots, T.data(), T.size() * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(p->d_pow5, pow5.data(), pow5.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  *out = p.release();
+  return GPQ_OK;
+}
+
+extern "C" int gpq_he_ecd(gpq_ctx *c, const gpq_ecd_plan *p, uint64_t *out, const double *z_dev, unsigned logDelta, unsigned W, unsigned count,
+                          uint32_t *bad_dev, void *stream) {
+  return encode(c, p, out, z_dev, logDelta, W, count, 0, bad_dev, stream, "gpq_he_ecd");
+}
+
+extern "C" int gpq_he_ecd_diagonals(gpq_ctx *c, const gpq_ecd_plan *p, uint64_t *out, const double *A_dev, unsigned logDelta, unsigned W,
+                                    uint32_t *bad_dev, void *stream) {
+  unsigned n1 = 1;
+  if (p) gemv_split(p->slots, &n1);
+  return encode(c, p, out, A_dev, logDelta, W, p ? p->slots : 1, n1, bad_dev, stream, "gpq_he_ecd_diagonals");
+}
+
+extern "C" int gpq_gemv_plan_create_from_matrix(gpq_ctx *c, gpq_gemv_plan **out, const gpq_ecd_plan *p, const double *A_dev, unsigned logDelta,
+                                                unsigned logql, unsigned dimpt, void *stream) {
+  if (!c || !out || !p || p->ctx != c || !A_dev) return gpq_fail(GPQ_ERR_INVALID, "gpq_gemv_plan_create_from_matrix: null argument, or a plan of another context");
+  hipStream_t s = (hipStream_t)stream;
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
+    return gpq_fail(GPQ_ERR_INVALID, "gpq_gemv_plan_create_from_matrix allocates and waits for the stream: not inside a stream capture");
+  // one word per coefficient: every encodable value fits (|v| < 2^63), 8 n bytes per diagonal
+  uint64_t *slab = nullptr;
+  const size_t bytes = (size_t)p->slots * c->n * 8;
+  if (hipMalloc((void **)&slab, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    return gpq_fail(GPQ_ERR_NOMEM, "gpq_gemv_plan_create_from_matrix: no room for %zu bytes of encoded diagonals", bytes);
+  }
+  struct Release { uint64_t *q; ~Release() { (void)hipFree(q); } } release{slab};   // (hipFree waits for the transforms that read it)
+  *p->h_bad = 0;
+  HIP_TRY(hipMemsetAsync(p->d_bad, 0, sizeof(uint32_t), s));
+  int rc = gpq_he_ecd_diagonals(c, p, slab, A_dev, logDelta, 1, p->d_bad, stream);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(p->h_bad, p->d_bad, sizeof(uint32_t), hipMemcpyDeviceToHost, s));   // arrives with gpq_gemv_plan_create's own wait
+  gpq_gemv_plan *made = nullptr;
+  if ((rc = gpq_gemv_plan_create(c, &made, slab, p->slots, 1, logql, dimpt, stream))) return rc;
+  if (*p->h_bad) {
+    gpq_gemv_plan_destroy(made);
+    return gpq_fail(GPQ_ERR_INVALID, "gpq_gemv_plan_create_from_matrix: %u coefficients of the encoded diagonals are not finite or reach 2^63", *p->h_bad);
+  }
+  *out = made;
+  return GPQ_OK;
+}

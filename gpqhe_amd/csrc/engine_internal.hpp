@@ -21,7 +21,9 @@ enum { GPQ_K_STRIDED_FWD = 0, GPQ_K_STRIDED_INV, GPQ_K_CONTIG_FWD, GPQ_K_CONTIG_
        // permutation of that input on single-pass rings (automorphism_gather)
        GPQ_K_KEYSWITCH_ROT_MID, GPQ_K_AUTOMORPHISM_GATHER,
        // planned he_gemv: the inner sum of one giant step in the NTT domain (gemv_mac)
-       GPQ_K_GEMV_MAC, GPQ_K_COUNT };
+       GPQ_K_GEMV_MAC,
+       // he_ecd on the device: one workgroup per slot vector (he_ecd_lds, ecd_kernels.hpp)
+       GPQ_K_ECD, GPQ_K_COUNT };
 
 // Constant matrix of the matrix-core CRT fast path for one basis and result width WL (bridge_mfma.hpp)
 struct gpq_recon_mfma {

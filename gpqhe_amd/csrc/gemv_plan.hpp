@@ -70,6 +70,8 @@ extern "C" int gpq_gemv_plan_info(const gpq_gemv_plan *p, unsigned *dim, size_t 
   return GPQ_OK;
 }
 
+extern "C" unsigned gpq_gemv_plan_diag_bits(const gpq_gemv_plan *p) { return p ? p->diag_bits : 0; }
+
 extern "C" int gpq_gemv_plan_rotations(const gpq_gemv_plan *p, unsigned char *needed) {
   if (!p || !needed) return gpq_fail(GPQ_ERR_INVALID, "gpq_gemv_plan_rotations: null argument");
   memset(needed, 0, p->slots);

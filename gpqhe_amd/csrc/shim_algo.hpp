@@ -40,6 +40,7 @@ static void free_poly(poly_mpi_t *p, unsigned n) {
 
 // The reference's loop, call by call (:62-88), over this library's he_copy_ct / he_rot / he_mulpt / he_add / he_rs.
 static void gemv_loop(he_ct_t *ct_dest, const GemvMatrix &A, const he_ct_t *ct, const he_evk_t *rk) {
+  if (!he_ecd) die("he_gemv: the host program provides no he_ecd (src/he-encode.c)");
   const unsigned slots = hectx.slots, n = polyctx.n;
   unsigned n1, n2;
   gemv_split(slots, &n1, &n2);
@@ -69,12 +70,46 @@ static void gemv_loop(he_ct_t *ct_dest, const GemvMatrix &A, const he_ct_t *ct, 
   for (he_ct_t *t : {&inner, &outer, &ct_rot}) { free_poly(&t->c0, n); free_poly(&t->c1, n); }
 }
 
+// gpq_mpi_shim_set_device_ecd(1): the plan of a matrix not seen before, with the diagonals encoded ON THE DEVICE from the slots^2 entries
+// (gpq_gemv_plan_create_from_matrix) instead of slots he_ecd calls, slots n conversions and an upload of slots W n words.  The roots are the
+// host's own polyctx.ring.zetas, read by stride, so the words are those of an encoder that reads that table (src/he-encode.c does), under any
+// libm; pt.nu is hectx.Delta as src/he-encode.c:109 sets it.  nullptr -- and the caller goes on as if the switch were off -- when a
+// coefficient has no image (bad != 0), the plan is not exact, or the slot count exceeds what one workgroup holds.  `key` is consumed on success only.
+static GemvPlanEntry *gemv_plan_on_device(gpq_ctx *c, GemvPlanKey &key, const GemvMatrix &A, const gpq_zc *raw, unsigned slots, unsigned logql, unsigned logDelta) {
+  if (!polyctx.ring.zetas || slots > 8192 || slots > polyctx.n / 2) return nullptr;
+  gpq_ecd_plan *ep = nullptr;
+  if (gpq_ecd_plan_create(c, &ep, slots, (const double *)polyctx.ring.zetas, polyctx.m / 4) != GPQ_OK) die("he_gemv: cannot build the encoder's tables");
+  std::vector<gpq_zc> built;
+  if (!raw) {                                                      // he_sum / he_idx: the matrix they describe, slots^2 x 16 bytes
+    built.resize((size_t)slots * slots);
+    for (unsigned r = 0; r < slots; ++r)
+      for (unsigned col = 0; col < slots; ++col) built[(size_t)r * slots + col] = A(r, col);
+    raw = built.data();
+  }
+  const size_t bytes = (size_t)slots * slots * sizeof(gpq_zc);
+  DevBuf dA(bytes);
+  if (gpq_upload(dA.p, raw, bytes, nullptr) != GPQ_OK) die("upload failed");
+  const unsigned dimpt = (logql + 1 + logDelta + polyctx.logn) / 59u + 1;                                          // src/he-mult.c:169 with nu = Delta
+  gpq_gemv_plan *made = nullptr;
+  const int rc = gpq_gemv_plan_create_from_matrix(c, &made, ep, (const double *)dA.p, logDelta, logql, dimpt, nullptr);
+  gpq_ecd_plan_destroy(ep);
+  if (rc == GPQ_ERR_INVALID) return nullptr;                       // a coefficient at or beyond 2^63: the host's encoder decides what that means
+  if (rc != GPQ_OK) die("he_gemv: cannot build the plan");
+  int exact = 0;
+  (void)gpq_gemv_plan_info(made, nullptr, nullptr, nullptr, &exact);
+  if (!exact) { gpq_gemv_plan_destroy(made); return nullptr; }
+  const unsigned dbits = gpq_gemv_plan_diag_bits(made);
+  GemvPlanEntry e;
+  e.key = std::move(key); e.plan = made; e.nu = hectx.Delta; e.bits = dbits > logql + 1 ? dbits : logql + 1;
+  return gemv_plan_insert(std::move(e));
+}
+
 // kind 0: he_gemv (raw = the caller's slots x slots matrix), 1: he_sum, 2: he_idx (idx): what the plan cache keys on (shim_gemv_plans.hpp)
 static void gemv_impl(he_ct_t *ct_dest, const GemvMatrix &A, const he_ct_t *ct, const he_evk_t *rk, unsigned kind, unsigned idx, const gpq_zc *raw) {
   SHIM_CALL();
   need_gcrypt();
   if (&hectx == nullptr || !hectx.q) die("`hectx` is not initialised (hectx_init first)");
-  if (!he_ecd) die("he_gemv: the host program provides no he_ecd (src/he-encode.c)");
+  if (!he_ecd && !g_device_ecd) die("he_gemv: the host program provides no he_ecd (src/he-encode.c)");
   gpq_ctx *c = engine();
   const unsigned n = polyctx.n, l = ct->l, slots = hectx.slots;
   if (!slots || l < 1) die("he_gemv: needs slots > 0 and a level to rescale to");
@@ -96,7 +131,9 @@ static void gemv_impl(he_ct_t *ct_dest, const GemvMatrix &A, const he_ct_t *ct, 
     if (kind == 0) key.A.assign((const unsigned char *)raw, (const unsigned char *)raw + (size_t)slots * slots * sizeof(gpq_zc));
     hit = gemv_plan_find(key);
   }
+  if (!hit && g_device_ecd && g_gemv_plan_slots) hit = gemv_plan_on_device(c, key, A, raw, slots, logql, logql - logql1);
   // otherwise the diagonals, encoded by the host program's he_ecd on the reference's vectors in the reference's order (:70-72)
+  if (!hit && !he_ecd) die("he_gemv: the host program provides no he_ecd (src/he-encode.c)");
   std::vector<he_pt_t> pts(hit ? 0 : slots);
   std::vector<gpq_zc> rd;
   unsigned bits = logql + 1;
@@ -205,6 +242,12 @@ void he_sum(he_ct_t *ct_sum, const he_ct_t *ct, const he_evk_t *rk) {
 // he_idx, :105-113: A[idx][idx] = 1
 void he_idx(he_ct_t *ct_idx, const he_ct_t *ct, const unsigned int idx, const he_evk_t *rk) {
   gemv_impl(ct_idx, [idx](unsigned r, unsigned col) { return r == idx && col == idx ? (gpq_zc)1.0 : (gpq_zc)0.0; }, ct, rk, 2, idx, nullptr);
+}
+// 1: he_gemv / he_sum / he_idx encode the diagonals of a matrix they have no plan for on the device (gemv_plan_on_device); 0 (default): the
+// host program's he_ecd does, as ever
+void gpq_mpi_shim_set_device_ecd(int on) {
+  SHIM_CALL();
+  g_device_ecd = on != 0;
 }
 // Entries of he_gemv's plan cache (default 4, least recently used out); 0 frees every plan and makes every call encode, convert and upload
 // its diagonals and run gpq_he_gemv, as before the cache existed.

@@ -25,6 +25,7 @@ struct GemvPlanEntry {
 };
 std::vector<GemvPlanEntry> g_gemv_plans;
 unsigned g_gemv_plan_slots = 4;
+bool g_device_ecd = false;      // gpq_mpi_shim_set_device_ecd: a missing plan is built from the matrix on the device (shim_algo.hpp)
 unsigned long long g_gemv_plan_tick = 0;
 
 void gemv_plans_drop(size_t keep) {        // least recently used first

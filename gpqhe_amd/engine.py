@@ -377,6 +377,36 @@ class PolyContext:
         """A plan for he_gemv with a fixed matrix: diag = slots plaintext big slabs (index i*n1 + j) as he_gemv takes them."""
         return GemvPlan(self, diag, slots, W, logql, dimpt)
 
+    # --- he_ecd on the device (include/gpqhe_hip.h, "he_ecd on the device") ---
+    def ecd_plan(self, slots, roots=None, roots_slots=None):
+        """The encoder's tables for `slots` slots: roots = a (4 S + 1) x 2 float64 table for S >= slots slots (None: ecd_roots(slots))."""
+        return EcdPlan(self, slots, roots, roots_slots)
+
+    def he_ecd(self, plan, out, z, logDelta=None, W=1, bad=None, Delta=None):
+        """he_ecd (src/he-encode.c:107-111) of every vector of z = [count][slots] complex128 (or (re, im) float64 pairs) on the device into
+        out = [count][W][n]; `bad` = an int32 device word that counts coefficients without an image (stored as 0), or None."""
+        logDelta = log_delta(logDelta, Delta)
+        count = z.numel() * (2 if z.is_complex() else 1) // (2 * plan.slots)
+        if out.numel() != count * W * self.n:
+            raise ValueError("out holds %d words, %d vectors need %d" % (out.numel(), count, count * W * self.n))
+        _native.check(self.lib.gpq_he_ecd(self.h, plan.h, self._ptr(out), self._ptr(z), logDelta, W, count,
+                                          None if bad is None else self._ptr(bad), self._stream()), "gpq_he_ecd")
+        return out
+
+    def he_ecd_diagonals(self, plan, out, A, logDelta=None, W=1, bad=None, Delta=None):
+        """out[i n1 + j] = he_ecd(zrotdiag(A, i n1 + j, -i n1)) for the slots x slots row-major complex128 matrix A on the device: the `diag`
+        of he_gemv and gemv_plan."""
+        logDelta = log_delta(logDelta, Delta)
+        if out.numel() != plan.slots * W * self.n:
+            raise ValueError("out holds %d words, %d diagonals need %d" % (out.numel(), plan.slots, plan.slots * W * self.n))
+        _native.check(self.lib.gpq_he_ecd_diagonals(self.h, plan.h, self._ptr(out), self._ptr(A), logDelta, W,
+                                                    None if bad is None else self._ptr(bad), self._stream()), "gpq_he_ecd_diagonals")
+        return out
+
+    def gemv_plan_from_matrix(self, ecd, A, logDelta=None, logql=None, dimpt=None, Delta=None):
+        """A plan for he_gemv straight from the slots x slots complex128 matrix A on the device: the diagonals are encoded there."""
+        return GemvPlan.from_matrix(self, ecd, A, log_delta(logDelta, Delta), logql, dimpt)
+
     def gemv_inner(self, out_c0, out_c1, R0, R1, plan, giant, W):
         """One giant step's inner sum smod(sum_j R_j * diag[giant n1 + j], 2^logql); R0 / R1 = n1 x batch big slabs, rotation-major."""
         torch = _torch()
@@ -499,10 +529,30 @@ class GemvPlan:
     def __init__(self, ctx, diag, slots, W, logql, dimpt):
         self.lib, self.h = ctx.lib, C.c_void_p()
         _native.check(self.lib.gpq_gemv_plan_create(ctx.h, C.byref(self.h), ctx._ptr(diag), slots, W, logql, dimpt, ctx._stream()), "gpq_gemv_plan_create")
+        self._describe(slots, logql, dimpt)
+
+    @classmethod
+    def from_matrix(cls, ctx, ecd, A, logDelta, logql, dimpt):
+        """gpq_gemv_plan_create_from_matrix: the diagonals of the device matrix A, encoded on the device with the EcdPlan `ecd`"""
+        self = cls.__new__(cls)
+        self.lib, self.h = ctx.lib, C.c_void_p()
+        _native.check(self.lib.gpq_gemv_plan_create_from_matrix(ctx.h, C.byref(self.h), ecd.h, ctx._ptr(A), logDelta, logql, dimpt, ctx._stream()),
+                      "gpq_gemv_plan_create_from_matrix")
+        self._describe(ecd.slots, logql, dimpt)
+        return self
+
+    def _describe(self, slots, logql, dimpt):
         dim, nbytes, live, exact = C.c_uint(), C.c_size_t(), C.c_uint(), C.c_int()
         _native.check(self.lib.gpq_gemv_plan_info(self.h, C.byref(dim), C.byref(nbytes), C.byref(live), C.byref(exact)), "gpq_gemv_plan_info")
         self.dim, self.bytes, self.live, self.exact = dim.value, nbytes.value, live.value, bool(exact.value)
+        self.diag_bits = int(self.lib.gpq_gemv_plan_diag_bits(self.h))
         self.slots, self.logql, self.dimpt = slots, logql, dimpt
+
+    def rotations(self):
+        """needed[r] for every rotation r < slots whose key he_gemv_planned reads"""
+        needed = (C.c_ubyte * self.slots)()
+        _native.check(self.lib.gpq_gemv_plan_rotations(self.h, needed), "gpq_gemv_plan_rotations")
+        return [int(v) for v in needed]
 
     def close(self):
         if getattr(self, "h", None):
@@ -516,6 +566,53 @@ class GemvPlan:
 
     def __exit__(self, *exc):
         self.close()
+
+
+class EcdPlan:
+    """gpq_ecd_plan: the root table and the powers of 5 the encoder reads for `slots` slots, on the device.  `roots` = a (4 S + 1) x 2
+    float64 array for S = roots_slots >= slots slots (S is taken from the array's length when not given); None = ecd_roots(slots)."""
+
+    def __init__(self, ctx, slots, roots=None, roots_slots=None):
+        self.lib, self.h, self.slots = ctx.lib, C.c_void_p(), slots
+        if roots is not None:
+            roots = np.ascontiguousarray(roots, dtype=np.float64).reshape(-1, 2)
+            roots_slots = roots_slots or (roots.shape[0] - 1) // 4
+            if roots.shape[0] != 4 * roots_slots + 1:
+                raise ValueError("a root table for %d slots has %d rows, not %d" % (roots_slots, 4 * roots_slots + 1, roots.shape[0]))
+        _native.check(self.lib.gpq_ecd_plan_create(ctx.h, C.byref(self.h), slots, None if roots is None else roots.ctypes.data_as(C.c_void_p),
+                                                   roots_slots or 0), "gpq_ecd_plan_create")
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.gpq_ecd_plan_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def ecd_roots(slots):
+    """(4 slots + 1) x 2 float64: T[t] = (cos, sin)(2 PI t / (4 slots)) by the C library's sincos (include/gpqhe_hip.h: gpq_ecd_roots).  No device."""
+    table = np.empty((4 * slots + 1, 2), dtype=np.float64)
+    _native.check(_native.load().gpq_ecd_roots(table.ctypes.data_as(C.c_void_p), slots), "gpq_ecd_roots")
+    return table
+
+
+def log_delta(logDelta=None, Delta=None):
+    """the logDelta the device encoder takes: Delta must be a power of two >= 2 (any other needs the reference's x87 product and is refused)"""
+    if Delta is None:
+        if logDelta is None:
+            raise ValueError("logDelta or Delta")
+        return int(logDelta)
+    m, e = np.frexp(float(Delta))
+    if m != 0.5 or e < 2 or (logDelta is not None and int(logDelta) != e - 1):
+        raise _native.GpqError("he_ecd on the device: Delta = %r is not a power of two (GPQ_ERR_INVALID)" % (Delta,))
+    return int(e) - 1
 
 
 def gemv_acc_dim(logql, diag_bits, logn, n1):

@@ -425,6 +425,42 @@ int gpq_he_gemv_planned(gpq_ctx *ctx, uint64_t *out_c0, uint64_t *out_c1, const 
                         const uint64_t *const *rk0, const uint64_t *const *rk1, unsigned W, unsigned logDelta, unsigned dimB, unsigned dimP,
                         unsigned batch, void *workspace, void *stream);
 
+/* ---- he_ecd on the device ("Encoding on the device") ----------------------------------------------------------------------
+ * he_ecd, src/he-encode.c:53-64 and :107-111 with invcanemb, src/canemb.c:62-81: `slots` complex doubles -> the plaintext polynomial as a
+ * big slab, one workgroup per vector (he_ecd_lds).  The butterflies are the reference's, every double operation rounded on its own (no
+ * fused multiply-add), so the words are those of the reference compiled for x86-64 -- GIVEN THE SAME ROOT TABLE: the kernel holds no
+ * trigonometry of its own.  All the encoder reads of polyctx.ring.zetas for `slots` slots are the 4 slots + 1 entries
+ * T[t] = zetas[t m / (4 slots)] = (cos, sin)(2 PI t / (4 slots)); a table for S slots serves every power of two below S by stride.
+ *   Range: Delta = 2^logDelta, logDelta <= 63 (any other Delta needs the x87 product of src/he-encode.c:61 and has no entry point here).
+ *   A rounded coefficient must satisfy |v| < 2^63; one that does not, or that is not finite, is stored as 0 and counted in *bad_dev
+ *   (a device word the caller zeroes; NULL: not counted).  The other coefficients and vectors of the call are unaffected.
+ * gpq_ecd_roots: host only, no device.  table = 2 (4 slots + 1) doubles, (re, im) pairs, from the C library's sincos on
+ *   2 PI t / (4 slots) with the reference's PI (src/params.h:52) -- what gcc -O2 makes of src/precomp.c:306-309 -- and T[4 slots] = T[0].
+ * gpq_ecd_plan_create: slots = a power of two, <= n/2 and <= 8192 (16 bytes per slot in LDS; more: GPQ_ERR_INVALID).  roots = the caller's
+ *   table for roots_slots >= slots (a power of two), read by stride -- a host that has polyctx.ring.zetas passes it with roots_slots = m/4
+ *   and gets the words of its own encoder under any libm; NULL = gpq_ecd_roots.  A plan belongs to its context and is destroyed before it.
+ * gpq_he_ecd: z_dev = [count][slots] (re, im) pairs on the device; out = [count][W][n], W <= 32: slot i as W sign-extended words at
+ *   coefficient i gap (real part) and i gap + n/2 (imaginary part), gap = n / (2 slots), zero everywhere else.  The call writes every word
+ *   of `out`: the caller does not clear it.  Asynchronous on `stream`.
+ * gpq_he_ecd_diagonals: A_dev = a slots x slots row-major matrix of (re, im) pairs; out[i n1 + j] = he_ecd(zrotdiag(A, i n1 + j, -i n1))
+ *   (src/he-algo.c:29-43, :63-72; n1 as :51-54): the `diag` of gpq_he_gemv and gpq_gemv_plan_create, gathered by the kernel's load.
+ * gpq_gemv_plan_create_from_matrix: gpq_gemv_plan_create on the diagonals of A_dev encoded into a W = 1 slab (8 n bytes per diagonal: every
+ *   encodable value fits), which is released before the call returns.  A coefficient out of range fails the call with GPQ_ERR_INVALID
+ *   and leaves no plan.  Waits for `stream` as gpq_gemv_plan_create does (the bad count arrives with its measurement), and for the
+ *   device when it releases the slab. */
+typedef struct gpq_ecd_plan gpq_ecd_plan;
+int gpq_ecd_roots(double *table, unsigned slots);
+int gpq_ecd_plan_create(gpq_ctx *ctx, gpq_ecd_plan **plan, unsigned slots, const double *roots, unsigned roots_slots);
+void gpq_ecd_plan_destroy(gpq_ecd_plan *plan);
+int gpq_he_ecd(gpq_ctx *ctx, const gpq_ecd_plan *plan, uint64_t *out, const double *z_dev, unsigned logDelta, unsigned W, unsigned count,
+               uint32_t *bad_dev, void *stream);
+int gpq_he_ecd_diagonals(gpq_ctx *ctx, const gpq_ecd_plan *plan, uint64_t *out, const double *A_dev, unsigned logDelta, unsigned W,
+                         uint32_t *bad_dev, void *stream);
+int gpq_gemv_plan_create_from_matrix(gpq_ctx *ctx, gpq_gemv_plan **plan, const gpq_ecd_plan *ecd, const double *A_dev, unsigned logDelta,
+                                     unsigned logql, unsigned dimpt, void *stream);
+/* the largest coefficient of the plan's diagonals in bits, as gpq_gemv_plan_create measured it (the `diag_bits` of the bound above) */
+unsigned gpq_gemv_plan_diag_bits(const gpq_gemv_plan *plan);
+
 /* ---- general moduli: any q_l (little-endian words ql_words[0..Lq)) and any Delta (uint64_t, as hectx_init takes it,
  * src/gpqhe.h:100).  Same reference semantics, through the multiword Barrett kernel: slow-path quality, meant for parameter
  * sets outside the powers of two that the fast entry points above cover. */

@@ -187,6 +187,13 @@ void gpq_mpi_shim_set_key_slots(unsigned slots);
  * repeat call neither encodes (no he_ecd call), converts nor uploads diagonals.  `entries` plans are kept (default 4, least recently used
  * out; each holds slots x limbs x n words on the device); 0 frees them and restores the per-call path.  Same results either way. */
 void gpq_shim_gemv_plan_cache(unsigned entries);
+/* he_ecd is by contract the host program's own (src/he-encode.c; the library calls it through a weak reference).  on != 0 lets he_gemv / he_sum /
+ * he_idx encode the diagonals of a matrix they hold no plan for ON THE DEVICE instead (gpqhe_hip.h: gpq_gemv_plan_create_from_matrix): the
+ * slots^2 entries go up, not slots W n words, and he_ecd is not called at all.  The roots are the host's polyctx.ring.zetas, so the words are
+ * those of the reference's encoder on that table.  Taken when q_l, q_(l-1) and Delta are powers of two and the plan cache is on; a matrix with
+ * a coefficient at or beyond 2^63, a plan that is not exact, or more than 8192 slots goes the usual way through he_ecd, without an error.
+ * OPT-IN (default 0 = he_ecd encodes, exactly as before): a host whose he_ecd is not the reference's would get other plaintexts. */
+void gpq_mpi_shim_set_device_ecd(int on);
 /* How a resident key is recognised: by the caller's two pointers and a fingerprint of EVERY word, limb by limb (full != 0, the
  * default: a key edited in place multiplies as edited, like the reference, which reads its key on every call), computed by the
  * conversion threads while the device works; a call at a lower level, which reads fewer limbs of the same key (src/he-mult.c:51),
