@@ -140,6 +140,9 @@ SIGNATURES = {
     "gpq_ecd_plan_destroy": (None, [vp]),
     "gpq_he_ecd": (C.c_int, [vp, vp, vp, vp, C.c_uint, C.c_uint, C.c_uint, vp, vp]),
     "gpq_he_ecd_diagonals": (C.c_int, [vp, vp, vp, vp, C.c_uint, C.c_uint, vp, vp]),
+    "gpq_he_dcd": (C.c_int, [vp, vp, vp, vp, C.c_double, C.c_uint, C.c_uint, vp]),
+    "gpq_he_dec_workspace_bytes": (C.c_size_t, [vp, C.c_uint, C.c_uint]),
+    "gpq_he_dec": (C.c_int, [vp] * 5 + [C.c_uint] * 4 + [vp, vp]),
     "gpq_gemv_plan_create_from_matrix": (C.c_int, [vp, C.POINTER(vp), vp, vp, C.c_uint, C.c_uint, C.c_uint, vp]),
     "gpq_shim_gemv_plan_cache": (None, [C.c_uint]),
     "gpq_gemv_inner_workspace_bytes": (C.c_size_t, [vp, vp, C.c_uint]),
@@ -182,6 +185,7 @@ SIGNATURES = {
     "gpq_mpi_shim_set_direct_mpi": (C.c_int, [C.c_int]),
     "gpq_mpi_shim_last_timing": (None, [C.POINTER(C.c_double)]),
     "gpq_mpi_shim_set_device_ecd": (None, [C.c_int]),
+    "gpq_shim_he_dec_dcd": (C.c_int, [vp, vp, vp]),
     "gpq_fill_rns_chain": (C.c_int, [vp, C.c_uint, vp, C.c_int]),
     "gpq_release_rns_chain": (None, [vp]),
 }

@@ -1978,6 +1978,34 @@ extern "C" int gpq_he_mulpt(gpq_ctx *c, uint64_t *out_c0, uint64_t *out_c1, cons
   return gpq_rns_reconstruct(c, out_c1, W, s1, dim, batch, logql, stream);                                                // :189
 }
 
+// he_dec, src/he-encrypt.c:105-125, for q_l = 2^logql: m = smod(poly_mul(c1, sk, dim, q_l) + c0, q_l) for `batch` ciphertexts and ONE key.
+// sk_ntt = the secret key as he_genswk would store it (gpq_evk_pack of its big slab): uint64_t[dim][n], read by every ciphertext of the
+// batch through the pointwise kernel's shared operand -- the key exists once and the launches do not grow with the batch.  dim is the
+// caller's (:113).  The words are the reference's also when c1 * sk wraps the dim-limb basis: the same residues, the same CRT.
+extern "C" size_t gpq_he_dec_workspace_bytes(const gpq_ctx *c, unsigned dim, unsigned batch) {
+  return c ? (size_t)batch * ((size_t)dim << c->logn) * 8 : 0;
+}
+
+extern "C" int gpq_he_dec(gpq_ctx *c, uint64_t *m, const uint64_t *c0, const uint64_t *c1, const uint64_t *sk_ntt, unsigned W, unsigned logql,
+                          unsigned dim, unsigned batch, void *workspace, void *stream) {
+  int rc = check(c, dim, batch, "gpq_he_dec");
+  if (rc) return rc;
+  if (!m || !c0 || !c1 || !sk_ntt || !workspace || !logql) return gpq_fail(GPQ_ERR_INVALID, "gpq_he_dec: bad arguments (q_l must be 2^logql, logql > 0)");
+  if (W < 1 || 64ull * W <= logql) return gpq_fail(GPQ_ERR_INVALID, "gpq_he_dec: %u words cannot hold a centred coefficient mod 2^%u (64 W > logql)", W, logql);
+  const size_t big = (size_t)batch * W * c->n, key = (size_t)dim << c->logn;
+  auto overlap = [](const uint64_t *a, size_t na, const uint64_t *b, size_t nb) { return a < b + nb && b < a + na; };
+  if (overlap(m, big, c0, big) || overlap(m, big, c1, big) || overlap(m, big, sk_ntt, key))
+    return gpq_fail(GPQ_ERR_INVALID, "gpq_he_dec: the output aliases an input");
+  StageRange stage("gpq_he_dec");
+  uint64_t *x = (uint64_t *)workspace;
+  if ((rc = gpq_rns_decompose(c, x, c1, W, dim, batch, stream))) return rc;              // src/poly.c:96-103 with the key's limbs already transformed
+  if ((rc = gpq_ntt(c, x, dim, batch, stream))) return rc;
+  if ((rc = gpq_rns_mul_shared(c, x, x, sk_ntt, dim, batch, (hipStream_t)stream))) return rc;
+  if ((rc = gpq_invntt(c, x, dim, batch, stream))) return rc;
+  if ((rc = gpq_rns_reconstruct(c, m, W, x, dim, batch, logql, stream))) return rc;       // poly_rns2mpi, :104
+  return gpq_big_add(c, m, m, c0, W, logql, batch, stream);                                // src/he-encrypt.c:117-118
+}
+
 static int permute(gpq_ctx *c, uint64_t *r, const uint64_t *a, unsigned W, unsigned batch, unsigned long long power, int conj, void *stream) {
   if (!c || !r || !a || r == a || W < 1 || batch < 1) return gpq_fail(GPQ_ERR_INVALID, "poly_rot/poly_conj: bad arguments (not in place)");
   PermuteArgs p{a, r, W, c->logn, power, conj};

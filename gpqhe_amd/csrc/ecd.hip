@@ -1,10 +1,11 @@
 // ecd.hip -- the encoder on the device (include/gpqhe_hip.h, "he_ecd"): the root table, the per-slot-count plan, gpq_he_ecd /
 // gpq_he_ecd_diagonals (kernel: ecd_kernels.hpp) and gpq_gemv_plan_create_from_matrix, which encodes a matrix's diagonals into a one-word
-// slab and hands it to gpq_gemv_plan_create.
+// slab and hands it to gpq_gemv_plan_create; and the decoder, gpq_he_dcd (kernel: dcd_kernels.hpp), on the same plan.
 #include <hip/hip_runtime.h>
 #include "../../include/gpqhe_hip.h"
 #include "engine_internal.hpp"
 #include "ecd_kernels.hpp"
+#include "dcd_kernels.hpp"
 
 #include <cmath>
 #include <memory>
@@ -132,6 +133,34 @@ extern "C" int gpq_he_ecd_diagonals(gpq_ctx *c, const gpq_ecd_plan *p, uint64_t 
   unsigned n1 = 1;
   if (p) gemv_split(p->slots, &n1);
   return encode(c, p, out, A_dev, logDelta, W, p ? p->slots : 1, n1, bad_dev, stream, "gpq_he_ecd_diagonals");
+}
+
+// he_dcd, src/he-encode.c:66-74 and :114-117: `count` plaintext big slabs -> [count][slots] (re, im) pairs
+extern "C" int gpq_he_dcd(gpq_ctx *c, const gpq_ecd_plan *p, double *z_dev, const uint64_t *in, double nu, unsigned W, unsigned count, void *stream) {
+  const char *who = "gpq_he_dcd";
+  if (!c) return gpq_fail(GPQ_ERR_INVALID, "%s: null context", who);
+  if (!p || p->ctx != c) return gpq_fail(GPQ_ERR_INVALID, "%s: no plan, or a plan of another context", who);
+  if (!z_dev || !in || !count) return gpq_fail(GPQ_ERR_INVALID, "%s: null argument or empty batch", who);
+  if (W < 1 || W > 32) return gpq_fail(GPQ_ERR_INVALID, "%s: W = %u outside 1..32", who, W);
+  if (!std::isfinite(nu) || !(nu > 0)) return gpq_fail(GPQ_ERR_INVALID, "%s: nu = %g must be a finite double above 0", who, nu);
+  int dev = -1;
+  if (hipGetDevice(&dev) == hipSuccess && dev != c->device)
+    return gpq_fail(GPQ_ERR_INVALID, "%s: the context lives on device %d but the calling thread's current device is %d (gpq_set_device(gpq_ctx_device(ctx)) first)", who, c->device, dev);
+  static bool raised[64] = {};
+  const size_t lds = (size_t)p->slots * 16;
+  if (lds > 65536 && !(dev >= 0 && dev < 64 && raised[dev])) {            // the attribute is per kernel function: he_ecd_lds having it does not serve
+    HIP_TRY(hipFuncSetAttribute((const void *)he_dcd_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kEcdMaxSlots * 16)));
+    if (dev >= 0 && dev < 64) raised[dev] = true;
+  }
+  DcdArgs a{in, z_dev, p->d_roots, p->d_pow5, nu, p->slots, p->logslots, c->logn, W};
+  const unsigned threads = p->slots >= kEcdMaxThreads ? kEcdMaxThreads : 256u;     // 2 slots conversions, slots / 2 butterflies per stage
+  hipStream_t s = (hipStream_t)stream;
+  {
+    ProfScope prof(c, GPQ_K_DCD, s);
+    hipLaunchKernelGGL(he_dcd_lds, dim3(count), dim3(threads), lds, s, a);
+  }
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? GPQ_OK : gpq_fail(GPQ_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(e));
 }
 
 extern "C" int gpq_gemv_plan_create_from_matrix(gpq_ctx *c, gpq_gemv_plan **out, const gpq_ecd_plan *p, const double *A_dev, unsigned logDelta,

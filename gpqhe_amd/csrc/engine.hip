@@ -457,7 +457,7 @@ static const char *const kKernelNames[GPQ_K_COUNT] = {"strided_fwd", "strided_in
                                                       "tensor_mid", "keyswitch_mid", "pointwise", "small_ntt", "reference_redo",
                                                       "bridge_decompose", "bridge_reconstruct", "bridge_relin_front", "bridge_relin_tail_fused", "bridge_exact_paths", "bridge_rescale",
                                                       "bridge_relin_tail_direct", "bridge_crt_decompose", "bridge_tail_stream",
-                                                      "keyswitch_rot_mid", "automorphism_gather", "gemv_mac", "he_ecd_lds"};
+                                                      "keyswitch_rot_mid", "automorphism_gather", "gemv_mac", "he_ecd_lds", "he_dcd_lds"};
 
 int check_shape(const gpq_ctx *c, unsigned dim, unsigned batch, const char *who) {
   if (!c) return gpq_fail(GPQ_ERR_INVALID, "%s: null context", who);
@@ -766,7 +766,7 @@ extern "C" int gpq_invntt(gpq_ctx *c, uint64_t *slab, unsigned dim, unsigned bat
   return after_launch("gpq_invntt");
 }
 
-template <bool MUL>
+template <bool MUL, bool SHARED = false>
 static int pointwise_api(gpq_ctx *c, uint64_t *r, const uint64_t *x, const uint64_t *y, unsigned dim, unsigned batch,
                          void *stream, const char *who) {
   int rc = check_shape(c, dim, batch, who);
@@ -777,9 +777,9 @@ static int pointwise_api(gpq_ctx *c, uint64_t *r, const uint64_t *x, const uint6
     const unsigned polys = batch - k0 < kMaxPolysPerLaunch ? batch - k0 : kMaxPolysPerLaunch;
     const size_t off = (size_t)k0 * ((size_t)dim << c->logn);
     PassArgs a = make_args(c, dim, 1);
-    a.src[0] = x + off; a.src[1] = y + off; a.dst[0] = r + off;
+    a.src[0] = x + off; a.src[1] = SHARED ? y : y + off; a.dst[0] = r + off;
     ProfScope prof(c, GPQ_K_POINTWISE, (hipStream_t)stream);
-    hipLaunchKernelGGL((pointwise<MUL>), dim3(bx, polys, dim), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL((pointwise<MUL, SHARED>), dim3(bx, polys, dim), dim3(256), 0, (hipStream_t)stream, a);
   }
   return after_launch(who);
 }
@@ -789,6 +789,10 @@ extern "C" int gpq_rns_mul(gpq_ctx *c, uint64_t *r, const uint64_t *a, const uin
 }
 extern "C" int gpq_rns_add(gpq_ctx *c, uint64_t *r, const uint64_t *a, const uint64_t *b, unsigned dim, unsigned batch, void *stream) {
   return pointwise_api<false>(c, r, a, b, dim, batch, stream, "gpq_rns_add");
+}
+
+int gpq_rns_mul_shared(gpq_ctx *c, uint64_t *r, const uint64_t *x, const uint64_t *key, unsigned dim, unsigned polys, hipStream_t s) {
+  return pointwise_api<true, true>(c, r, x, key, dim, polys, (void *)s, "gpq_rns_mul_shared");
 }
 
 extern "C" int gpq_poly_mul_rns(gpq_ctx *c, uint64_t *r, uint64_t *a, uint64_t *b, unsigned dim, unsigned batch, void *stream) {

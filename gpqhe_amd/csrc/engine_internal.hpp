@@ -23,7 +23,9 @@ enum { GPQ_K_STRIDED_FWD = 0, GPQ_K_STRIDED_INV, GPQ_K_CONTIG_FWD, GPQ_K_CONTIG_
        // planned he_gemv: the inner sum of one giant step in the NTT domain (gemv_mac)
        GPQ_K_GEMV_MAC,
        // he_ecd on the device: one workgroup per slot vector (he_ecd_lds, ecd_kernels.hpp)
-       GPQ_K_ECD, GPQ_K_COUNT };
+       GPQ_K_ECD,
+       // he_dcd on the device: one workgroup per plaintext (he_dcd_lds, dcd_kernels.hpp)
+       GPQ_K_DCD, GPQ_K_COUNT };
 
 // Constant matrix of the matrix-core CRT fast path for one basis and result width WL (bridge_mfma.hpp)
 struct gpq_recon_mfma {
@@ -211,6 +213,9 @@ int gpq_keyswitch_rotated(gpq_ctx *c, uint64_t *c0, uint64_t *c1, const uint64_t
 // pairs (device array) of r0 / r1[slot][polys][dim][n] (*) diag[diagonal][dim][n], all in the NTT domain; canonical output, ONE launch.
 int gpq_gemv_mac(gpq_ctx *c, uint64_t *acc0, uint64_t *acc1, const uint64_t *r0, const uint64_t *r1, const uint64_t *diag,
                  const void *terms, unsigned nterms, unsigned dim, unsigned polys, hipStream_t s);
+// gpq_he_dec (bridge.hip): r[k] = x[k] (*) key for `polys` polynomials of `dim` limbs and ONE key slab uint64_t[dim][n] shared by all of them
+// (pointwise<true, true>: the second operand is read without the polynomial's offset); r may alias x.
+int gpq_rns_mul_shared(gpq_ctx *c, uint64_t *r, const uint64_t *x, const uint64_t *key, unsigned dim, unsigned polys, hipStream_t s);
 // hipMalloc of a read-only table, accounted in the context's table cache (gpq_debug_table_bytes)
 inline hipError_t gpq_table_malloc(gpq_ctx *c, void **p, size_t bytes) {
   hipError_t e = hipMalloc(p, bytes);

@@ -1086,8 +1086,9 @@ __global__ __launch_bounds__(CONTIG_WAVES * 64, 4) void contig_pass8(PassArgs a,
 // ---------------------------------------------------------------------------
 // Pointwise limb ops on whole slabs: poly_rns_mul / poly_rns_add,
 // src/poly.c:71-82.  16 bytes per lane, grid-stride free (exact grid).
+// SHARED: src[1] is ONE polynomial's limbs [dim][n], the second operand of every polynomial of the launch (gpq_he_dec's key).
 // ---------------------------------------------------------------------------
-template <bool MUL>
+template <bool MUL, bool SHARED = false>
 __global__ __launch_bounds__(256) void pointwise(PassArgs a) {
   const LimbTab &tab = a.tabs[a.limb0 + blockIdx.z];
   const PrimeK k = pin_consts(tab.k);
@@ -1095,7 +1096,7 @@ __global__ __launch_bounds__(256) void pointwise(PassArgs a) {
   if (i2 >= (1u << a.logn)) return;
   const size_t off = (size_t)blockIdx.y * a.poly_stride + ((size_t)blockIdx.z << a.logn) + i2;
   const ulonglong2 u = *reinterpret_cast<const ulonglong2 *>(a.src[0] + off);
-  const ulonglong2 v = *reinterpret_cast<const ulonglong2 *>(a.src[1] + off);
+  const ulonglong2 v = *reinterpret_cast<const ulonglong2 *>(a.src[1] + (SHARED ? ((size_t)blockIdx.z << a.logn) + i2 : off));
   ulonglong2 r;
   if (MUL) { r.x = mulmod_canon(u.x, v.x, k); r.y = mulmod_canon(u.y, v.y, k); }
   else     { r.x = addmod_canon(u.x, v.x, k); r.y = addmod_canon(u.y, v.y, k); }

@@ -28,7 +28,16 @@ unsigned g_gemv_plan_slots = 4;
 bool g_device_ecd = false;      // gpq_mpi_shim_set_device_ecd: a missing plan is built from the matrix on the device (shim_algo.hpp)
 unsigned long long g_gemv_plan_tick = 0;
 
+// gpq_shim_he_dec_dcd's decoder tables (a gpq_ecd_plan on the host's polyctx.ring.zetas), kept between calls; they belong to the engine
+// context like the plans above and go with them
+struct DcdPlan { gpq_ecd_plan *plan = nullptr; unsigned slots = 0, m = 0; const void *zetas = nullptr; } g_dcd_plan;
+
 void gemv_plans_drop(size_t keep) {        // least recently used first
+  if (!keep && g_dcd_plan.plan) {
+    (void)gpq_stream_sync(nullptr);
+    gpq_ecd_plan_destroy(g_dcd_plan.plan);
+    g_dcd_plan = DcdPlan();
+  }
   while (g_gemv_plans.size() > keep) {
     size_t old = 0;
     for (size_t i = 1; i < g_gemv_plans.size(); ++i) if (g_gemv_plans[i].used < g_gemv_plans[old].used) old = i;

@@ -403,6 +403,27 @@ class PolyContext:
                                                     None if bad is None else self._ptr(bad), self._stream()), "gpq_he_ecd_diagonals")
         return out
 
+    # --- he_dec and he_dcd on the device (include/gpqhe_hip.h, "he_dec and he_dcd on the device") ---
+    def he_dcd(self, plan, z_out, big, nu, W):
+        """he_dcd (src/he-encode.c:114-117) of every plaintext of big = [count][W][n] on the device into z_out = [count][slots] complex128
+        (or (re, im) float64 pairs); nu = pt->nu, any finite double > 0.  The plan is the encoder's (ecd_plan)."""
+        count = big.numel() // (W * self.n)
+        have = z_out.numel() * (2 if z_out.is_complex() else 1)
+        if have != count * 2 * plan.slots:
+            raise ValueError("z_out holds %d doubles, %d plaintexts need %d" % (have, count, count * 2 * plan.slots))
+        _native.check(self.lib.gpq_he_dcd(self.h, plan.h, self._ptr(z_out), self._ptr(big), float(nu), W, count, self._stream()), "gpq_he_dcd")
+        return z_out
+
+    def he_dec(self, m, c0, c1, sk_ntt, W, logql, dim):
+        """he_dec (src/he-encrypt.c:105-125) with q_l = 2^logql on big slabs: m = smod(c1 * sk + c0, q_l) for every ciphertext of the batch;
+        sk_ntt = the key as ONE NTT-domain slab [dim][n] (evk_pack of its big slab), shared by the batch."""
+        torch = _torch()
+        batch = c1.numel() // (W * self.n)
+        ws = torch.empty(self.lib.gpq_he_dec_workspace_bytes(self.h, dim, batch) // 8 + 8, dtype=torch.int64, device=self._dev)
+        _native.check(self.lib.gpq_he_dec(self.h, self._ptr(m), self._ptr(c0), self._ptr(c1), self._ptr(sk_ntt), W, logql, dim, batch,
+                                          self._ptr(ws), self._stream()), "gpq_he_dec")
+        return m
+
     def gemv_plan_from_matrix(self, ecd, A, logDelta=None, logql=None, dimpt=None, Delta=None):
         """A plan for he_gemv straight from the slots x slots complex128 matrix A on the device: the diagonals are encoded there."""
         return GemvPlan.from_matrix(self, ecd, A, log_delta(logDelta, Delta), logql, dimpt)

@@ -461,6 +461,29 @@ int gpq_gemv_plan_create_from_matrix(gpq_ctx *ctx, gpq_gemv_plan **plan, const g
 /* the largest coefficient of the plan's diagonals in bits, as gpq_gemv_plan_create measured it (the `diag_bits` of the bound above) */
 unsigned gpq_gemv_plan_diag_bits(const gpq_gemv_plan *plan);
 
+/* ---- he_dec and he_dcd on the device ("Decoding on the device") ------------------------------------------------------------
+ * he_dcd, src/he-encode.c:66-74 and :114-117 with canemb, src/canemb.c:43-60: a plaintext big slab -> `slots` complex doubles, one
+ * workgroup per plaintext (he_dcd_lds), on the SAME gpq_ecd_plan as the encoder (its root table and powers of 5; no plan type of its own).
+ * The doubles are the reference's bit for bit, given the same root table:
+ *   - mpi_to_double (src/types.c:77-106) is `num = num * 2 + bit` in double arithmetic, neither correctly rounded nor truncating: a
+ *     magnitude of more than 53 bits becomes M' 2^(L - 53) with M its top 53 bits, b the 54th and M' = M + (b & M & 1); every lower bit is
+ *     ignored; +-inf from 2^1024 (a 32-word slab can reach it).  The kernel computes exactly that, sign last;
+ *   - the division by nu is the IEEE-rounded one, real and imaginary part on their own: nu is ANY finite double > 0 (after he_mul / he_rs
+ *     it is no power of two);
+ *   - the butterflies are the reference's, every double operation rounded on its own (no fused multiply-add).
+ * gpq_he_dcd: in = [count][W][n] big slabs (two's complement, -2^(64 W - 1) included), W in 1..32; only the 2 slots W words of the
+ *   coefficients i gap and i gap + n/2 (gap = n / (2 slots)) of each are read.  z_dev = [count][slots] (re, im) pairs on the device, written
+ *   completely: 16 slots bytes per plaintext are what a host downloads.  Asynchronous on `stream`.  GPQ_ERR_INVALID before anything is
+ *   launched for a null argument, a plan of another context, W outside 1..32, count = 0, nu not finite or <= 0, or the wrong current device.
+ * gpq_he_dec: he_dec, src/he-encrypt.c:105-125, for q_l = 2^logql on big slabs of W words (64 W > logql):
+ *   m = smod(poly_mul(c1, sk, dim, q_l) + c0, q_l) for `batch` ciphertexts; sk_ntt = the secret key as ONE NTT-domain slab uint64_t[dim][n]
+ *   (gpq_evk_pack of its big slab, batch 1), shared by the batch: the key is never replicated.  dim = (logql + 1) / 59 + 1 is the caller's
+ *   (:113).  The words are the reference's also when c1 * sk wraps the dim-limb basis.  Outputs may not alias inputs. */
+int gpq_he_dcd(gpq_ctx *ctx, const gpq_ecd_plan *plan, double *z_dev, const uint64_t *in, double nu, unsigned W, unsigned count, void *stream);
+size_t gpq_he_dec_workspace_bytes(const gpq_ctx *ctx, unsigned dim, unsigned batch);
+int gpq_he_dec(gpq_ctx *ctx, uint64_t *m, const uint64_t *c0, const uint64_t *c1, const uint64_t *sk_ntt, unsigned W, unsigned logql,
+               unsigned dim, unsigned batch, void *workspace, void *stream);
+
 /* ---- general moduli: any q_l (little-endian words ql_words[0..Lq)) and any Delta (uint64_t, as hectx_init takes it,
  * src/gpqhe.h:100).  Same reference semantics, through the multiword Barrett kernel: slow-path quality, meant for parameter
  * sets outside the powers of two that the fast entry points above cover. */

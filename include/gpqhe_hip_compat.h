@@ -194,6 +194,12 @@ void gpq_shim_gemv_plan_cache(unsigned entries);
  * a coefficient at or beyond 2^63, a plan that is not exact, or more than 8192 slots goes the usual way through he_ecd, without an error.
  * OPT-IN (default 0 = he_ecd encodes, exactly as before): a host whose he_ecd is not the reference's would get other plaintexts. */
 void gpq_mpi_shim_set_device_ecd(int on);
+/* he_dec followed by he_dcd without the plaintext ever becoming libgcrypt integers: 16 * hectx.slots bytes come down.  (he_dcd itself is by
+ * contract the host program's own, like he_ecd; this is a name of its own.)  The operands, their residency and the recheck are he_dec's;
+ * the decoder is gpqhe_hip.h's gpq_he_dcd with the host's polyctx.ring.zetas as roots (as gpq_mpi_shim_set_device_ecd) and nu = ct->nu, so
+ * the doubles are those of the reference's he_dec + he_dcd on that table, bit for bit.  Returns 1 when done; 0 -- and m untouched -- when q_l
+ * is no power of two, slots > 8192 or there is no ring table: the caller then runs he_dec + he_dcd. */
+int gpq_shim_he_dec_dcd(_Complex double *m, const struct he_ct *ct, const poly_mpi_t *sk);
 /* How a resident key is recognised: by the caller's two pointers and a fingerprint of EVERY word, limb by limb (full != 0, the
  * default: a key edited in place multiplies as edited, like the reference, which reads its key on every call), computed by the
  * conversion threads while the device works; a call at a lower level, which reads fewer limbs of the same key (src/he-mult.c:51),
