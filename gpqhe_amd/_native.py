@@ -143,6 +143,14 @@ SIGNATURES = {
     "gpq_he_dcd": (C.c_int, [vp, vp, vp, vp, C.c_double, C.c_uint, C.c_uint, vp]),
     "gpq_he_dec_workspace_bytes": (C.c_size_t, [vp, C.c_uint, C.c_uint]),
     "gpq_he_dec": (C.c_int, [vp] * 5 + [C.c_uint] * 4 + [vp, vp]),
+    "gpq_sample_error_table": (C.c_int, [vp]),
+    "gpq_sample_zo": (C.c_int, [vp, vp, vp, C.c_uint, vp]),
+    "gpq_sample_error": (C.c_int, [vp, vp, vp, C.c_uint, vp]),
+    "gpq_sample_uniform": (C.c_int, [vp, vp, vp, C.c_uint, C.c_uint, C.c_uint, vp]),
+    "gpq_small_to_big": (C.c_int, [vp, vp, vp, C.c_uint, C.c_uint, vp]),
+    "gpq_he_enc_workspace_bytes": (C.c_size_t, [vp, C.c_uint, C.c_uint, C.c_int]),
+    "gpq_he_enc_pk": (C.c_int, [vp] * 9 + [C.c_uint] * 4 + [vp, vp]),
+    "gpq_he_enc_sk": (C.c_int, [vp] * 7 + [C.c_uint] * 4 + [vp, vp]),
     "gpq_gemv_plan_create_from_matrix": (C.c_int, [vp, C.POINTER(vp), vp, vp, C.c_uint, C.c_uint, C.c_uint, vp]),
     "gpq_shim_gemv_plan_cache": (None, [C.c_uint]),
     "gpq_gemv_inner_workspace_bytes": (C.c_size_t, [vp, vp, C.c_uint]),
@@ -185,6 +193,7 @@ SIGNATURES = {
     "gpq_mpi_shim_set_direct_mpi": (C.c_int, [C.c_int]),
     "gpq_mpi_shim_last_timing": (None, [C.POINTER(C.c_double)]),
     "gpq_mpi_shim_set_device_ecd": (None, [C.c_int]),
+    "gpq_mpi_shim_set_device_samplers": (None, [C.c_int]),
     "gpq_shim_he_dec_dcd": (C.c_int, [vp, vp, vp]),
     "gpq_fill_rns_chain": (C.c_int, [vp, C.c_uint, vp, C.c_int]),
     "gpq_release_rns_chain": (None, [vp]),
@@ -193,7 +202,7 @@ SIGNATURES = {
 # exercised from C (tests/c/dropin_host.c)
 EXPORTED_ONLY = ["montgomery_reduce", "barrett_reduce",
                  # MPI-typed surface: driven from C with real libgcrypt MPIs (tests/c/mpi_host.c)
-                 "rns_decompose", "rns_reconstruct", "poly_rns2mpi", "poly_mul", "he_mul", "he_rs", "he_rescale", "he_moddown", "he_mulpt", "he_add", "he_sub", "he_addpt", "he_subpt", "he_neg", "he_copy_ct", "he_dec", "he_conj", "he_rot", "he_genrlk", "he_genck", "he_genrk",
+                 "rns_decompose", "rns_reconstruct", "poly_rns2mpi", "poly_mul", "he_mul", "he_rs", "he_rescale", "he_moddown", "he_mulpt", "he_add", "he_sub", "he_addpt", "he_subpt", "he_neg", "he_copy_ct", "he_dec", "he_enc_pk", "he_enc_sk", "he_keypair", "he_conj", "he_rot", "he_genrlk", "he_genck", "he_genrk",
                  "he_gemv", "he_sum", "he_idx",
                  ]
 # libgpqhe_hip_ctx.so (ctx_compat.hip): context construction / storage names for hosts that are not GPQHE; driven from C

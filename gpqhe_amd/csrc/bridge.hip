@@ -737,6 +737,7 @@ void gpq_bridge_release(gpq_ctx *c) {
         if (q) (void)hipFree(q);
   }
   for (auto &kv : c->cache->decomps) { if (kv.second.d_bfrag) (void)hipFree(kv.second.d_bfrag); if (kv.second.d_pk) (void)hipFree(kv.second.d_pk); }
+  if (c->cache->d_error_table) (void)hipFree(c->cache->d_error_table);
   delete c->cache;
   c->cache = nullptr;
 }

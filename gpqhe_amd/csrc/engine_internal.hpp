@@ -25,7 +25,9 @@ enum { GPQ_K_STRIDED_FWD = 0, GPQ_K_STRIDED_INV, GPQ_K_CONTIG_FWD, GPQ_K_CONTIG_
        // he_ecd on the device: one workgroup per slot vector (he_ecd_lds, ecd_kernels.hpp)
        GPQ_K_ECD,
        // he_dcd on the device: one workgroup per plaintext (he_dcd_lds, dcd_kernels.hpp)
-       GPQ_K_DCD, GPQ_K_COUNT };
+       GPQ_K_DCD,
+       // samplers and encryption on the device (enc_kernels.hpp): the byte-fed samplers; small_to_rns_k / small_to_big_k / enc_tail_k
+       GPQ_K_SAMPLE, GPQ_K_ENC, GPQ_K_COUNT };
 
 // Constant matrix of the matrix-core CRT fast path for one basis and result width WL (bridge_mfma.hpp)
 struct gpq_recon_mfma {
@@ -88,6 +90,7 @@ struct gpq_table_cache {
   std::map<std::pair<unsigned, unsigned>, gpq_relin_tables> relins;  // by (dimP, dimB)
   std::map<std::pair<std::pair<unsigned, unsigned>, unsigned>, gpq_decomp_mfma> decomps;  // by ((first limb, limbs), W)
   size_t device_bytes = 0;            // read-only device memory behind this cache and the transform tables (gpq_table_malloc)
+  uint16_t *d_error_table = nullptr;  // gpq_sample_error's 65536 coefficient pairs (enc.hip), uploaded at first use
   // Scaled per-limb tables (ScaledInverse, bridge.hip) one of whose split pairs fails the wide class's table check (modarith.hpp:
   // split_entry_fits_wide), with the first such limb: a context that reads the table runs that limb and those after it in the split class.
   // Empty for every chain met so far (the failing constants are ~100 values in 2^59).

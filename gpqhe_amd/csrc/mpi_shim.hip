@@ -36,6 +36,11 @@ extern "C" struct he_ctx hectx __attribute__((weak));       // src/precomp.c:47
 // the reference's samplers (src/sample.c; externs at src/he-kem.c:33-34): key generation draws from them in the reference's order
 extern "C" void sample_error(poly_mpi_t *r) __attribute__((weak));
 extern "C" void sample_uniform(poly_mpi_t *r, const gpq_MPI q) __attribute__((weak));
+// ... and encryption / he_keypair (src/he-encrypt.c:33-35, src/he-kem.c:32): sample_zo, sample_sk; randombytes (src/rng.c) feeds the device
+// samplers after gpq_mpi_shim_set_device_samplers(1)
+extern "C" void sample_zo(poly_mpi_t *r) __attribute__((weak));
+extern "C" void sample_sk(poly_mpi_t *r) __attribute__((weak));
+extern "C" void randombytes(uint8_t *x, size_t xlen) __attribute__((weak));
 // the reference's encoder (src/he-encode.c:107-111): he_gemv / he_sum / he_idx encode their diagonals with the host program's own
 extern "C" void he_ecd(struct he_pt *pt, const _Complex double *m) __attribute__((weak));
 
@@ -180,6 +185,7 @@ void poly_mul(poly_mpi_t *r, const poly_mpi_t *a, const poly_mpi_t *b, const uns
 }
 
 #include "shim_decrypt.hpp"
+#include "shim_encrypt.hpp"
 
 // src/he-mult.c:88-156
 void he_mul(he_ct_t *ct, const he_ct_t *ct1, const he_ct_t *ct2, const he_evk_t *rlk) {

@@ -424,6 +424,59 @@ class PolyContext:
                                           self._ptr(ws), self._stream()), "gpq_he_dec")
         return m
 
+    # --- samplers and encryption on the device (include/gpqhe_hip.h, "samplers and encryption on the device") ---
+    def sample_zo(self, out, bytes_dev):
+        """sample_zo (src/sample.c:112-131) of the caller's bytes: bytes_dev = uint8 [count][n/4] on the device (any byte address),
+        out = int8 [count][n]."""
+        count = out.numel() // self.n
+        if bytes_dev.numel() != count * (self.n // 4):
+            raise ValueError("%d polynomials need %d bytes, not %d" % (count, count * (self.n // 4), bytes_dev.numel()))
+        _native.check(self.lib.gpq_sample_zo(self.h, self._ptr(out), self._ptr(bytes_dev), count, self._stream()), "gpq_sample_zo")
+        return out
+
+    def sample_error(self, out, bytes_dev):
+        """sample_error (src/sample.c:60-82) of the caller's bytes: bytes_dev = uint8 [count][n], out = int8 [count][n]."""
+        count = out.numel() // self.n
+        if bytes_dev.numel() != count * self.n:
+            raise ValueError("%d polynomials need %d bytes, not %d" % (count, count * self.n, bytes_dev.numel()))
+        _native.check(self.lib.gpq_sample_error(self.h, self._ptr(out), self._ptr(bytes_dev), count, self._stream()), "gpq_sample_error")
+        return out
+
+    def sample_uniform(self, big, bytes_dev, nbits, W):
+        """sample_uniform (src/sample.c:133-141) for a q of nbits bits: bytes_dev = uint8 [count][n][nbits // 8 + 1], big = [count][W][n],
+        the RAW values in [0, 2^nbits)."""
+        count = big.numel() // (W * self.n)
+        if bytes_dev.numel() != count * self.n * (nbits // 8 + 1):
+            raise ValueError("%d polynomials need %d bytes, not %d" % (count, count * self.n * (nbits // 8 + 1), bytes_dev.numel()))
+        _native.check(self.lib.gpq_sample_uniform(self.h, self._ptr(big), self._ptr(bytes_dev), nbits, W, count, self._stream()), "gpq_sample_uniform")
+        return big
+
+    def small_to_big(self, big, small, W):
+        """an int8 small slab [count][n] sign-extended into a big slab [count][W][n]"""
+        _native.check(self.lib.gpq_small_to_big(self.h, self._ptr(big), self._ptr(small), W, small.numel() // self.n, self._stream()), "gpq_small_to_big")
+        return big
+
+    def he_enc_pk(self, out_c0, out_c1, m, v, e0, e1, pk0_ntt, pk1_ntt, W, logq, dim):
+        """he_enc_pk (src/he-encrypt.c:37-73) with q = 2^logq: m = plaintext big slabs (None: none), v / e0 / e1 = int8 small slabs
+        (sample_zo, sample_error, sample_error), pk0_ntt / pk1_ntt = the public key as ONE NTT-domain slab pair [dim][n]."""
+        torch = _torch()
+        batch = v.numel() // self.n
+        ws = torch.empty(self.lib.gpq_he_enc_workspace_bytes(self.h, dim, batch, 1) // 8 + 8, dtype=torch.int64, device=self._dev)
+        _native.check(self.lib.gpq_he_enc_pk(self.h, self._ptr(out_c0), self._ptr(out_c1), None if m is None else self._ptr(m), self._ptr(v), self._ptr(e0),
+                                             self._ptr(e1), self._ptr(pk0_ntt), self._ptr(pk1_ntt), W, logq, dim, batch, self._ptr(ws), self._stream()),
+                      "gpq_he_enc_pk")
+        return out_c0, out_c1
+
+    def he_enc_sk(self, out_c0, out_c1, m, a, e, sk_ntt, W, logq, dim):
+        """he_enc_sk (src/he-encrypt.c:75-103) with q = 2^logq: a = the RAW sample_uniform big slabs, e = an int8 small slab, sk_ntt = the
+        secret key as he_dec takes it; m = None is he_keypair's pk.p0, pk.p1 (src/he-kem.c:59-65)."""
+        torch = _torch()
+        batch = e.numel() // self.n
+        ws = torch.empty(self.lib.gpq_he_enc_workspace_bytes(self.h, dim, batch, 0) // 8 + 8, dtype=torch.int64, device=self._dev)
+        _native.check(self.lib.gpq_he_enc_sk(self.h, self._ptr(out_c0), self._ptr(out_c1), None if m is None else self._ptr(m), self._ptr(a), self._ptr(e),
+                                             self._ptr(sk_ntt), W, logq, dim, batch, self._ptr(ws), self._stream()), "gpq_he_enc_sk")
+        return out_c0, out_c1
+
     def gemv_plan_from_matrix(self, ecd, A, logDelta=None, logql=None, dimpt=None, Delta=None):
         """A plan for he_gemv straight from the slots x slots complex128 matrix A on the device: the diagonals are encoded there."""
         return GemvPlan.from_matrix(self, ecd, A, log_delta(logDelta, Delta), logql, dimpt)
@@ -621,6 +674,13 @@ def ecd_roots(slots):
     """(4 slots + 1) x 2 float64: T[t] = (cos, sin)(2 PI t / (4 slots)) by the C library's sincos (include/gpqhe_hip.h: gpq_ecd_roots).  No device."""
     table = np.empty((4 * slots + 1, 2), dtype=np.float64)
     _native.check(_native.load().gpq_ecd_roots(table.ctypes.data_as(C.c_void_p), slots), "gpq_ecd_roots")
+    return table
+
+
+def sample_error_table():
+    """65536 x 2 int8: T[b0][b1] of sample_error's byte pairs, (0, 0) for b1 = 0 (include/gpqhe_hip.h: gpq_sample_error_table).  No device."""
+    table = np.empty((65536, 2), dtype=np.int8)
+    _native.check(_native.load().gpq_sample_error_table(table.ctypes.data_as(C.c_void_p)), "gpq_sample_error_table")
     return table
 
 

@@ -484,6 +484,53 @@ size_t gpq_he_dec_workspace_bytes(const gpq_ctx *ctx, unsigned dim, unsigned bat
 int gpq_he_dec(gpq_ctx *ctx, uint64_t *m, const uint64_t *c0, const uint64_t *c1, const uint64_t *sk_ntt, unsigned W, unsigned logql,
                unsigned dim, unsigned batch, void *workspace, void *stream);
 
+/* ---- samplers and encryption on the device ("Encrypting on the device") ------------------------------------------------------
+ * The randomness is the caller's, as for he_gen*k: the library never invents entropy, it turns the caller's BYTES (device memory, at any
+ * byte address: a caller slices one stream) into the polynomials the reference's samplers make of the same bytes.  A "small slab" is
+ * int8_t[count][n], one signed byte per coefficient.  All calls are asynchronous on `stream`; outputs may not overlap inputs or each other.
+ * gpq_sample_error_table: host only, no device.  table = 65536 x 2 entries, T[b0][b1] = ((int16_t)floor(rr cos(theta) + 0.5), (int16_t)floor(rr
+ *   sin(theta) + 0.5)) with theta = 2 PI b0 / 256, rr = sqrt(-2 log(b1 / 256)) SIGMA (src/sample.c:64-71, src/params.h:52, :55).  Every entry lies
+ *   in [-11, 11]; the argument of floor stays 5e-5 away from the integers, so the table does not depend on the libm.  For b1 = 0 (log 0 = -inf:
+ *   the conversion is undefined in C) it holds (0, 0), what the reference executed on x86-64 gives.  The context builds and uploads it (128 KiB,
+ *   counted in gpq_debug_table_bytes) at the first gpq_sample_error, which therefore runs once outside a stream capture -- by the one
+ *   host thread that drives the context, like every other table built at first use (see "slab operations" above: a context is not thread-safe).
+ * gpq_sample_zo: sample_zo, src/sample.c:112-131.  bytes_dev = [count][n/4]; with Z the little-endian integer of a polynomial's bytes,
+ *   coefficient i = 0 when bit 2i of Z is 0, else +1 when bit 2i + 1 is 0, else -1.  logn >= 2.
+ * gpq_sample_error: sample_error, :60-82.  bytes_dev = [count][n]; (coefficient i, i + 1) = T[byte i][byte i + 1] for even i.
+ * gpq_sample_uniform: sample_uniform, :133-141 with loadmpi_littleendian (src/types.c:166-184).  nbits = the bit length of q (logq + 1 for
+ *   q = 2^logq); bytes_dev = [count][n][nbits / 8 + 1]; a coefficient = the low nbits bits of its bytes' little-endian integer (the rest of the
+ *   last byte -- all of it when nbits % 8 == 0 -- is consumed and dropped), in [0, 2^nbits): NOT reduced and NOT centred.  big = a big slab
+ *   [count][W][n] of non-negative values, 64 W > nbits, W <= 32; every word of it is written.
+ * gpq_small_to_big: a small slab sign-extended into a big slab of W words, the format gpq_he_genswk's `e` and every other entry point takes.
+ * gpq_he_enc_pk: he_enc_pk, src/he-encrypt.c:37-73, for q = 2^logq on `batch` plaintexts:
+ *     c0 = smod(poly_mul(pk.p0, v, dim, q) + m + e0, q),  c1 = smod(poly_mul(pk.p1, v, dim, q) + e1, q)
+ *   m = plaintext big slabs [batch][W][n] (NULL: none); v, e0, e1 = small slabs [batch][n] (sample_zo, sample_error, sample_error, in the
+ *   reference's order); pk0_ntt / pk1_ntt = the public key as ONE NTT-domain slab pair uint64_t[dim][n] (gpq_evk_pack of the centred key
+ *   polynomials, batch 1), shared by the batch.  dim is the caller's (hectx.dim, src/precomp.c:401).  v goes straight to residues and is
+ *   transformed once for both products (gpq_keyswitch with the key pair, its launch groups and lanes included).
+ * gpq_he_enc_sk: he_enc_sk, :75-103:  c0 = smod(-poly_mul(a, sk, dim, q) + m + e, q),  c1 = smod(a, q)
+ *   a = the RAW sample of gpq_sample_uniform (nbits = logq + 1), big slabs [batch][W][n] with 64 W > logq + 1: the reference multiplies the
+ *   uncentred sample (:91) and centres it afterwards (:97), and so does this call; e = small slabs; sk_ntt = the secret key as gpq_he_dec
+ *   takes it.  The words are the reference's also when a * sk wraps the dim-limb basis.  m == NULL is no plaintext: exactly he_keypair's
+ *   pk.p0, pk.p1 (src/he-kem.c:59-65) from its sample_error and sample_uniform(q_L) -- he_keypair has no entry point of its own.
+ * Sampler order and bytes: he_enc_pk zo, error, error (n/4 + 2n); he_enc_sk error, uniform (n + n (nbits / 8 + 1)); he_keypair sample_sk
+ * (sequential rejection sampling: the host's), error, uniform.  The l / nu / B bookkeeping (:40-42) stays with the caller.
+ * GPQ_ERR_INVALID before anything is launched for: a null argument (except m); W outside 1..32, 64 W <= logq (gpq_he_enc_sk: <= logq + 1)
+ * or <= nbits; logq or nbits = 0; count or batch = 0; batch (and gpq_small_to_big's count) above 65535, a sampler's count beyond one
+ * launch (2^31 - 1 workgroups); logn < 2 for gpq_sample_zo, < 1 for gpq_sample_error; a dim the context lacks; an overlap of an output with an input,
+ * the other output or the workspace; the wrong current device.  workspace: gpq_he_enc_workspace_bytes(ctx, dim, batch, pk = 1 for gpq_he_enc_pk, 0 for gpq_he_enc_sk). */
+int gpq_sample_error_table(int8_t *table);
+int gpq_sample_zo(gpq_ctx *ctx, int8_t *out, const uint8_t *bytes_dev, unsigned count, void *stream);
+int gpq_sample_error(gpq_ctx *ctx, int8_t *out, const uint8_t *bytes_dev, unsigned count, void *stream);
+int gpq_sample_uniform(gpq_ctx *ctx, uint64_t *big, const uint8_t *bytes_dev, unsigned nbits, unsigned W, unsigned count, void *stream);
+int gpq_small_to_big(gpq_ctx *ctx, uint64_t *big, const int8_t *small, unsigned W, unsigned count, void *stream);
+size_t gpq_he_enc_workspace_bytes(const gpq_ctx *ctx, unsigned dim, unsigned batch, int pk);
+int gpq_he_enc_pk(gpq_ctx *ctx, uint64_t *out_c0, uint64_t *out_c1, const uint64_t *m, const int8_t *v, const int8_t *e0, const int8_t *e1,
+                  const uint64_t *pk0_ntt, const uint64_t *pk1_ntt, unsigned W, unsigned logq, unsigned dim, unsigned batch, void *workspace,
+                  void *stream);
+int gpq_he_enc_sk(gpq_ctx *ctx, uint64_t *out_c0, uint64_t *out_c1, const uint64_t *m, const uint64_t *a, const int8_t *e,
+                  const uint64_t *sk_ntt, unsigned W, unsigned logq, unsigned dim, unsigned batch, void *workspace, void *stream);
+
 /* ---- general moduli: any q_l (little-endian words ql_words[0..Lq)) and any Delta (uint64_t, as hectx_init takes it,
  * src/gpqhe.h:100).  Same reference semantics, through the multiword Barrett kernel: slow-path quality, meant for parameter
  * sets outside the powers of two that the fast entry points above cover. */

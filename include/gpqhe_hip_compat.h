@@ -81,6 +81,7 @@ struct he_ctx {                                                   /* src/gpqhe.h
   struct bnd_ctx bnd;
   double Bmult;
 };
+typedef struct he_pk { poly_mpi_t p0, p1; } he_pk_t;              /* src/gpqhe.h:72-76 */
 typedef struct he_evk { poly_rns_t p0, p1; } he_evk_t;            /* src/gpqhe.h:78-82 */
 typedef struct he_ct { unsigned int l; double nu, B; poly_mpi_t c0, c1; } he_ct_t;   /* src/gpqhe.h:84-91 */
 typedef struct he_pt { double nu; poly_mpi_t m; } he_pt_t;                            /* src/gpqhe.h:93-97 */
@@ -142,6 +143,21 @@ void he_copy_ct(struct he_ct *dest, const struct he_ct *src);
 /* src/he-encrypt.c:105-125 (decl src/gpqhe.h:130): m = c1 * sk + c0 centred mod q_l -- the caller of poly_mul at the end of every
  * computation; the sum and its centring stay on the device (2n libgcrypt calls on the host in the reference).  Optional. */
 void he_dec(struct he_pt *pt, const struct he_ct *ct, const poly_mpi_t *sk);
+/* src/he-kem.c:43-71 and src/he-encrypt.c:37-103 (decl src/gpqhe.h:127-129), with the reference's l / nu / B bookkeeping and he_keypair's
+ * two printf.  The randomness is the host program's: by default its own sample_sk / sample_zo / sample_error / sample_uniform (src/sample.c,
+ * weak references) are called in the reference's order -- he_keypair: sk, error, uniform(q_L); he_enc_sk: error, uniform(q_L); he_enc_pk: zo,
+ * error, error -- and the call ends the program with a message when one it needs is missing.  Power-of-two q_L runs gpqhe_hip.h's
+ * gpq_he_enc_sk / gpq_he_enc_pk, any other q_L the reference's sequence over the general entry points.  The key polynomials and the plaintext
+ * are resident operands like he_dec's, the written ciphertext / public key is remembered; he_keypair forgets the copies of what it overwrites. */
+void he_keypair(struct he_pk *pk, poly_mpi_t *sk);
+void he_enc_pk(struct he_ct *ct, const struct he_pt *pt, const struct he_pk *pk);
+void he_enc_sk(struct he_ct *ct, const struct he_pt *pt, const poly_mpi_t *sk);
+/* on != 0: he_keypair / he_enc_sk / he_enc_pk call the host program's randombytes (src/rng.c, weak reference) once per sampler call instead --
+ * n/4 bytes for sample_zo, n for sample_error, n (nbits(q_L) / 8 + 1) for sample_uniform, in the order above -- and gpqhe_hip.h's
+ * gpq_sample_zo / gpq_sample_error / gpq_sample_uniform expand those bytes on the device: no sampled polynomial becomes libgcrypt integers.
+ * sample_sk stays the host's.  Without a randombytes in the program the host's samplers are used as before, without an error.
+ * OPT-IN (default 0): a host whose samplers are not the reference's would get other polynomials from the same bytes. */
+void gpq_mpi_shim_set_device_samplers(int on);
 void he_conj(he_ct_t *ct, const he_evk_t *ck);                                          /* src/gpqhe.h:151  */
 void he_rot(he_ct_t *ct, const int rot, const he_evk_t *rk);                            /* src/gpqhe.h:152  */
 /* src/he-algo.c:47-113: the baby steps as one hoisted call, the whole body on the device (gpq_he_gemv) for power-of-two q_l, q_(l-1); the
