@@ -27,7 +27,10 @@ STREAM_NPY = os.path.join(ROOT, "tests", "golden", "ref_enc_stream.npy")
 STREAM_BYTES = 16384
 PROBE = 8
 SLOTS, LOGDELTA = 4, 30
-CASES = [(7, 120), (9, 100)]                      # logn, logq
+# logn, logq.  After the first two: W = 2, 2, 3, 3, 7, 3 words and hectx.dim = 2, 2, 3, 3, 8, 4 limbs -- logq one below and on a word
+# boundary (the raw sample of logq + 1 bits then fills a word resp. opens the next), the workload's q = 2^438, and a four-limb basis.
+# The model's whole `he` run of every case stays inside the stored STREAM_BYTES ((7, 438) ends at byte 15376 + PROBE).
+CASES = [(7, 120), (9, 100), (7, 63), (7, 64), (7, 127), (7, 128), (7, 438), (8, 190)]
 
 
 def case_name(case):

@@ -6,7 +6,7 @@ own.  Default mode: the drop-ins call the samplers in the reference's order (log
 l / nu / B are set as src/he-encrypt.c:40-42.  With gpq_mpi_shim_set_device_samplers(1): randombytes is called with the reference's byte
 counts in order, sample_zo / sample_error / sample_uniform are not called, sample_sk still is, and the ciphertexts are the model's on that
 stream.  he_dec of the results gives the model's plaintext plus noise; a second he_enc_pk runs with keys and plaintext resident (n = 2^13);
-and a q_L that is no power of two runs the fallback."""
+a q_L that is no power of two runs the fallback; and the workload's q_L = 2^438 runs with seven words and eight limbs."""
 import os
 import subprocess
 
@@ -67,14 +67,15 @@ def _parse(stdout):
 
 
 @pytest.mark.parametrize("mode,logn,logq,minus", [("host", 9, 100, 0), ("device", 9, 100, 0), ("host", 13, 100, 0), ("device", 13, 100, 0),
-                                                  ("host", 9, 100, 159), ("device", 9, 100, 159)],
+                                                  ("host", 9, 100, 159), ("device", 9, 100, 159), ("host", 9, 438, 0), ("device", 9, 438, 0)],
                          ids=["host_samplers", "device_samplers", "host_samplers_resident", "device_samplers_resident", "fallback_q_not_pow2",
-                              "fallback_device_samplers"])
+                              "fallback_device_samplers", "host_samplers_seven_words", "device_samplers_seven_words"])
 def test_drop_ins_equal_the_model(enc_host, tmp_path, mode, logn, logq, minus):
     from oracle.oracle import OracleCtx
     n, q = 1 << logn, (1 << logq) - minus
     nbits = q.bit_length()
     nb, dim = nbits // 8 + 1, enc_model.he_dim(logn, q)
+    assert (logq, minus) != (438, 0) or (dim == 8 and nbits // 64 + 1 == 7)   # the workload's q = 2^438: seven words, eight limbs
     o = OracleCtx(logn, dim)
     rng = np.random.default_rng(77 + logn + minus)
     sk = enc_model.sample_hwt(enc_model.Stream(rng.integers(0, 256, 8192, dtype=np.uint8)), n)

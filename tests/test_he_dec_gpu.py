@@ -2,7 +2,9 @@
 
 Word for word against the sequence the library already had -- gpq_poly_mul with the key replicated per ciphertext, gpq_big_addsub,
 gpq_he_rs(logDelta 0) -- at a single-pass ring with two and three limbs and at the first two-pass ring; with ternary keys, with a dense
-key in {-1, 1}^n whose product exceeds the basis, and against the Python-integer restatement with a sparse key; and the refusals."""
+key in {-1, 1}^n whose product exceeds the basis, and against the Python-integer restatement with a sparse key; against the model
+(tests/enc_model.he_dec) at the encryptor's shapes -- q_l of one bit up to 2^850, at and next to word boundaries, with slack words -- and
+one level down in the top level's words; at n = 2^13 with eight limbs; and the refusals."""
 import ctypes as C
 
 import numpy as np
@@ -12,6 +14,8 @@ import torch
 from gpqhe_amd import to_device, to_host
 from oracle import bigint_ref
 from oracle.expect import ints_to_words, words_to_ints
+from tests import enc_model
+from tests.test_he_enc_gpu import MODEL_SHAPES
 
 pytestmark = pytest.mark.gpu
 
@@ -83,6 +87,79 @@ def test_sparse_key_against_python_integers(engine_ctx):
     for k in range(batch):
         want = bigint_ref.he_dec_sparse((ints0[k * n:(k + 1) * n], ints1[k * n:(k + 1) * n]), terms, 1 << logql)
         assert words_to_ints(got[k], W, n) == want, "ciphertext %d" % k
+
+
+def _model_case(g, o, rng, logql, W, dim, batch):
+    """gpq_he_dec of `batch` seeded ciphertexts centred mod 2^logql in W words against enc_model.he_dec: Python integers through the oracle's
+    poly_mul.  A few c0 coefficients are built so that c1 s + c0 lands on 2^(logql-1) (smod wraps it down) and on -2^(logql-1) - 1 (up)"""
+    n, ql, half = g.n, 1 << logql, 1 << (logql - 1)
+    assert dim == (logql + 1) // 59 + 1                                       # the model's own dim, src/he-encrypt.c:113
+    sk = [int(v) for v in rng.integers(-1, 2, n)]
+    ints0, ints1 = _centred(rng, logql, batch * n), _centred(rng, logql, batch * n)
+    ups = downs = 0
+    for k in range(batch):
+        x = enc_model.poly_mul(o, ints1[k * n:(k + 1) * n], sk, dim, ql)      # centred: c0 = +-half -+ ... - x stays inside [-half, half)
+        up, down = [i for i, v in enumerate(x) if v > 0][:2], [i for i, v in enumerate(x) if v < 0][:2]
+        for i in up:
+            ints0[k * n + i] = half - x[i]
+        for i in down:
+            ints0[k * n + i] = -half - 1 - x[i]
+        ups, downs = ups + len(up), downs + len(down)
+    assert downs == 2 * batch and (ups == 2 * batch or logql == 1)            # (mod 2: x + c0 <= 0 never reaches half = 1)
+    assert all(-half <= v < half for v in ints0 + ints1) and min(ints0) < 0 and min(ints1) < 0
+    assert logql == 1 or (max(ints0) > 0 and max(ints1) > 0)                  # both signs (mod 2 the centred values are -1 and 0)
+    c0, c1 = _big(ints0, W, n), _big(ints1, W, n)
+    kept = c0.clone(), c1.clone()
+    got = _run(g, c0, c1, sk, W, logql, dim, batch)                           # (into a poisoned output)
+    want = [v for k in range(batch) for v in enc_model.he_dec(o, (ints0[k * n:(k + 1) * n], ints1[k * n:(k + 1) * n]), sk, ql)]
+    assert all(-half <= v < half for v in want)
+    bad = np.flatnonzero(got != np.concatenate([ints_to_words(want[k * n:(k + 1) * n], W) for k in range(batch)]))
+    assert not len(bad), "%d words differ from the model, first at %d (ciphertext, word, coefficient = %s)" % (
+        len(bad), bad[0], (bad[0] // (W * n), bad[0] // n % W, bad[0] % n))
+    assert torch.equal(c0, kept[0]) and torch.equal(c1, kept[1])              # inputs preserved
+
+
+DEC_SHAPES = [t for t in MODEL_SHAPES if "p" in t[2]]                         # gpq_he_enc_pk's shapes: 64 W > logql is all gpq_he_dec asks
+
+
+@pytest.mark.parametrize("logql,W,which,branch", DEC_SHAPES, ids=["q%d_w%d" % t[:2] for t in DEC_SHAPES])
+def test_words_equal_the_model_at_word_edges_and_wide_slabs(engine_ctx, oracle_ctx, logql, W, which, branch):
+    """the encryptor's shapes (test_he_enc_gpu.MODEL_SHAPES, where each one's word-position branch and its precondition are listed): one
+    word, logql one below / on / one above a word boundary, the workload's 2^438 and 2^850 with 8 and 15 limbs, and slack words"""
+    assert branch(logql, W) and 64 * W > logql
+    g, o = engine_ctx(7, 16), oracle_ctx(7, 16)
+    assert g.p == o.p
+    _model_case(g, o, np.random.default_rng(3000 + 40 * logql + W), logql, W, (logql + 1) // 59 + 1, 3)
+
+
+@pytest.mark.parametrize("logql,W,fill", [(88, 7, 5), (64, 7, 6), (388, 7, 0), (30, 2, 1)], ids=["q88_w7", "q64_w7", "q388_w7", "q30_w2"])
+def test_level_down_in_the_words_of_the_top_level(engine_ctx, oracle_ctx, logql, W, fill):
+    """a rescaled ciphertext keeps the top level's W while logql shrinks: words centred mod 2^logql and sign-extended.  `fill` whole words
+    lie at or above logql (the sign-fill branch of the final add): five after a straddling word, six after a full word (logql % 64 == 0),
+    none at 2^388 (one level below 2^438: the same seven words, seven limbs where the top level has eight), one after a single word"""
+    assert fill == W - (logql + 63) // 64 and (logql % 64 == 0) == (logql == 64)
+    g, o = engine_ctx(7, 16), oracle_ctx(7, 16)
+    _model_case(g, o, np.random.default_rng(4000 + 40 * logql + W), logql, W, logql // 59 + 1, 3)
+
+
+def test_two_pass_ring_with_eight_limbs_against_sparse_products(engine_ctx):
+    """logn 13, q = 2^438, W = 7, batch 2: the two-pass NTT and gpq_rns_mul_shared with eight limbs, against exact shifted sums"""
+    logn, logql, W, batch = 13, 438, 7, 2
+    dim = (logql + 1) // 59 + 1
+    assert dim == 8 and W == logql // 64 + 1
+    g = engine_ctx(logn, dim)
+    n, rng = g.n, np.random.default_rng(13439)
+    terms = {0: -1, 7: 1, 4099: 1, n - 2: -1, n - 1: 1}
+    sk = [terms.get(i, 0) for i in range(n)]
+    P = 1
+    for p in g.p[:dim]:
+        P *= int(p)
+    assert 2 * len(terms) << (logql - 1) < P                                  # the product fits the basis: he_dec_sparse's exact sum is poly_mul's
+    ints0, ints1 = _centred(rng, logql, batch * n), _centred(rng, logql, batch * n)
+    got = _run(g, _big(ints0, W, n), _big(ints1, W, n), sk, W, logql, dim, batch).reshape(batch, -1)
+    for k in range(batch):
+        want = bigint_ref.he_dec_sparse((ints0[k * n:(k + 1) * n], ints1[k * n:(k + 1) * n]), terms, 1 << logql)
+        assert np.array_equal(got[k], ints_to_words(want, W)), "ciphertext %d" % k
 
 
 def test_refusals(engine_ctx):

@@ -3,8 +3,10 @@
 Word for word against the sequence the library already had -- gpq_poly_mul with the key replicated per ciphertext, gpq_big_addsub,
 gpq_he_rs(logDelta 0), which the existing tests pin to the reference -- at test_he_dec_gpu.py's shapes, the dense key whose product with the
 RAW uniform sample exceeds the basis included; against the record of the executed reference (tests/golden/ref_enc.json) fed with the
-recorded stream's slices; over more launch groups than one; inputs preserved; the refusals; and encode -> encrypt -> decrypt -> decode on
-the device inside the reference's own noise bound."""
+recorded stream's slices; against the Python-integer model (tests/enc_model.py) at logn 7 with q of one bit up to 2^850, at, one below and
+one above a word boundary, with more words than q needs, and at n = 2^13 with eight limbs; over more launch groups than one; inputs
+preserved; the refusals; and encode -> encrypt -> decrypt -> decode on the device inside the reference's own noise bound, at the top level
+and one level down."""
 import ctypes as C
 import hashlib
 import math
@@ -136,9 +138,11 @@ def test_words_equal_the_record_of_the_executed_reference(engine_ctx, case):
     host's: the model's, from the same stream)"""
     logn, logq = case
     rec = enc_record.enc_golden()["cases"][enc_record.case_name(case)]
-    g = engine_ctx(logn, 6)
+    dim, dimdec = enc_model.he_dim(logn, 1 << logq), (logq + 1) // 59 + 1
+    g = engine_ctx(logn, max(6, dim))                                          # (7, 438) needs eight limbs
     n, W, nbits = g.n, rec["W"], logq + 1
-    dim, dimdec, nb = enc_model.he_dim(logn, 1 << logq), (logq + 1) // 59 + 1, nbits // 8 + 1
+    nb = nbits // 8 + 1
+    assert W == enc_record.words(logq) and dimdec <= dim <= len(g.p)
     host = enc_model.Stream(enc_record.stored_stream())
     dev = torch.from_numpy(host.data).cuda()
 
@@ -174,6 +178,154 @@ def test_words_equal_the_record_of_the_executed_reference(engine_ctx, case):
     assert host.pos == rec["pos"]["he_enc_pk"]
     key = _key_slab(g, sk_big, W, dimdec)
     check(("dec_sk", "dec_pk"), (g.he_dec(big(), s0, s1, key, W, logq, dimdec), g.he_dec(big(), q0, q1, key, W, logq, dimdec)))
+
+
+# (logq, W, which entry points, the enc_tail_k branch the shape is there for, the precondition that makes it take that branch)
+#   "p" = gpq_he_enc_pk, "s" = gpq_he_enc_sk (64 W > logq + 1: the raw sample of logq + 1 bits stays non-negative), he_keypair's form with it
+_ONE_WORD = lambda logq, W: W == 1 and logq < 64                              # the only word holds bit logq - 1 AND straddles logq
+_ONE_WORD_MOST = lambda logq, W: W == 1 and logq in (62, 63)                  # the most one word takes: 64 W > logq (enc_pk), > logq + 1 (enc_sk)
+_TOP_BIT = lambda logq, W: logq % 64 == 63 and 64 * W - logq >= 64            # bit logq - 1 is bit 62 of a word; with W > 1 a sign-fill word follows
+_FULL_WORD = lambda logq, W: logq % 64 == 0 and W == logq // 64 + 1           # no word straddles logq: the masking branch is skipped, the last word is sign fill
+_ONE_BIT = lambda logq, W: logq % 64 == 1 and W == logq // 64 + 1             # the straddling word keeps ONE bit, which is the sign bit
+_WORKLOAD = lambda logq, W: W == logq // 64 + 1 and (logq + 1) // 59 + 1 >= 8  # the workload's moduli: the least W, eight limbs or more
+_SLACK = lambda logq, W: 64 * W - logq >= 128                                 # two words or more at or above logq: sign fill (lo >= logq), a rescaled level
+MODEL_SHAPES = [(1, 1, "p", _ONE_WORD), (2, 1, "ps", _ONE_WORD), (62, 1, "s", _ONE_WORD_MOST), (63, 1, "p", _ONE_WORD_MOST),
+                (63, 2, "ps", _TOP_BIT), (64, 2, "ps", _FULL_WORD), (65, 2, "ps", _ONE_BIT),
+                (127, 3, "ps", _TOP_BIT), (128, 3, "ps", _FULL_WORD), (129, 3, "ps", _ONE_BIT),
+                (438, 7, "ps", _WORKLOAD), (850, 14, "ps", _WORKLOAD),
+                (100, 4, "ps", _SLACK), (64, 3, "ps", _SLACK), (438, 9, "ps", _SLACK)]
+
+
+def _crossing(x, e, half, picks=2):
+    """{i: m_i} for a few coefficients of ONE polynomial, chosen so that sign x_i + m_i + e_i lands on half or just above (smod wraps it down)
+    and on -half - 1 or just below (wraps it up); `x` is the centred product with its sign applied, so |m_i| <= half + 14 fits logq + 1 bits"""
+    up = [i for i, v in enumerate(x) if v >= 0][:picks]
+    down = [i for i, v in enumerate(x) if v < 0][:picks]
+    assert len(up) == picks and len(down) == picks
+    m = {i: half - x[i] - int(e[i]) + 3 * k for k, i in enumerate(up)}
+    m.update({i: -half - 1 - x[i] - int(e[i]) - 3 * k for k, i in enumerate(down)})
+    return m
+
+
+def _wraps(sums, half):
+    return sum(v >= half for v in sums), sum(v < -half for v in sums)
+
+
+@pytest.mark.parametrize("logq,W,which,branch", MODEL_SHAPES, ids=["q%d_w%d" % t[:2] for t in MODEL_SHAPES])
+def test_words_equal_the_model_at_word_edges_and_wide_slabs(engine_ctx, oracle_ctx, logq, W, which, branch):
+    """gpq_he_enc_sk (with and without a plaintext) and gpq_he_enc_pk against Python integers (enc_model.enc_sk_from / enc_pk_from) at logn 7,
+    batch 3 (the key switch of enc_pk runs its pair form and its single form); a few plaintext coefficients are built so that the sum
+    crosses +-2^(logq-1) in both directions"""
+    logn, batch = 7, 3
+    assert branch(logq, W) and 64 * W > logq
+    q, half = 1 << logq, 1 << (logq - 1)
+    dim = enc_model.he_dim(logn, q)
+    g, o = engine_ctx(logn, 16), oracle_ctx(logn, 16)
+    assert g.p == o.p and dim <= 16
+    n, rng = g.n, np.random.default_rng(7000 + 40 * logq + W)
+    x = _inputs(g, rng, logq, W, batch, False)
+    e, e1, v = (x[k].cpu().numpy().reshape(batch, n) for k in ("e", "e1", "v"))
+    a = [x["a_ints"][k * n:(k + 1) * n] for k in range(batch)]
+    assert e.min() < 0 < e.max() and e1.min() < 0 < e1.max()
+    names, got, exp, before = [], [], [], {}
+
+    def run(call, name, m_ints, tensors):
+        m = None if m_ints is None else _big([t for row in m_ints for t in row], W, n)
+        if m_ints is not None:
+            flat = [t for row in m_ints for t in row]
+            assert min(flat) < 0 < max(flat)                                    # the plaintext has both signs
+            tensors = dict(tensors, m=m)
+        before.update({name + " " + k: (t, t.clone()) for k, t in tensors.items()})
+        c0, c1 = _outputs(x["a"])                                               # poisoned
+        call(c0, c1, m)
+        names.extend((name + " c0", name + " c1"))
+        got.extend((c0, c1))
+
+    def plaintext(built):
+        m = [int(t) for t in rng.integers(-(1 << 40), 1 << 40, n)]
+        for i, t in built.items():
+            m[i] = t
+        return m
+
+    if "s" in which:
+        assert 64 * W > logq + 1
+        sk_slab = _key_slab(g, _big(x["sk"], W, n), W, dim)
+        xs = [[-t for t in enc_model.poly_mul(o, a[k], x["sk"], dim, q)] for k in range(batch)]                 # -a s, src/he-encrypt.c:91-93
+        m_sk = [plaintext(_crossing(xs[k], e[k], half)) for k in range(batch)]
+        up, down = _wraps([xs[k][i] + m_sk[k][i] + int(e[k][i]) for k in range(batch) for i in range(n)], half)
+        assert up >= 2 * batch and down >= 2 * batch                            # smod wraps in both directions
+        assert sum(t >= half for t in x["a_ints"]) > n // 4                     # and c1 = smod(a) wraps the raw sample
+        ins = {"a": x["a"], "e": x["e"], "sk": sk_slab}
+        run(lambda c0, c1, m: g.he_enc_sk(c0, c1, m, x["a"], x["e"], sk_slab, W, logq, dim), "enc_sk", m_sk, ins)
+        run(lambda c0, c1, m: g.he_enc_sk(c0, c1, None, x["a"], x["e"], sk_slab, W, logq, dim), "keypair", None, ins)
+        for m_rows in (m_sk, [None] * batch):
+            pairs = [enc_model.enc_sk_from(o, m_rows[k], a[k], e[k], x["sk"], dim, q) for k in range(batch)]
+            exp.extend(([t for c in pairs for t in c[0]], [t for c in pairs for t in c[1]]))
+    if "p" in which:
+        pk_slabs = [_key_slab(g, _big(p, W, n), W, dim) for p in x["pk"]]
+        x0 = [enc_model.poly_mul(o, x["pk"][0], [int(t) for t in v[k]], dim, q) for k in range(batch)]          # pk0 v, src/he-encrypt.c:58
+        m_pk = [plaintext(_crossing(x0[k], e[k], half)) for k in range(batch)]
+        up, down = _wraps([x0[k][i] + m_pk[k][i] + int(e[k][i]) for k in range(batch) for i in range(n)], half)
+        assert up >= 2 * batch and down >= 2 * batch
+        ins = {"v": x["v"], "e0": x["e"], "e1": x["e1"], "pk0": pk_slabs[0], "pk1": pk_slabs[1]}
+        run(lambda c0, c1, m: g.he_enc_pk(c0, c1, m, x["v"], x["e"], x["e1"], pk_slabs[0], pk_slabs[1], W, logq, dim), "enc_pk", m_pk, ins)
+        pairs = [enc_model.enc_pk_from(o, m_pk[k], v[k], e[k], e1[k], x["pk"], dim, q) for k in range(batch)]
+        exp.extend(([t for c in pairs for t in c[0]], [t for c in pairs for t in c[1]]))
+    torch.cuda.synchronize()
+    for name, t, want in zip(names, got, exp):
+        assert all(-half <= w < half for w in want)
+        words, want = to_host(t), np.concatenate([ints_to_words(want[k * n:(k + 1) * n], W) for k in range(batch)])
+        bad = np.flatnonzero(words != want)
+        assert not len(bad), "%s: %d words differ from the model, first at %d (ciphertext, word, coefficient = %s)" % (
+            name, len(bad), bad[0], (bad[0] // (W * n), bad[0] // n % W, bad[0] % n))
+    for name, (t, kept) in before.items():                                      # inputs preserved
+        assert torch.equal(t, kept), name
+
+
+def _sparse_terms(rng, n, count):
+    """`count` distinct positions with signs: a sparse polynomial in {-1, 0, 1}^n, x^0 and x^(n-1) among the positions"""
+    pos = [0, n - 1] + [int(t) for t in rng.choice(np.arange(1, n - 1), count - 2, replace=False)]
+    return [(k, int(rng.choice([-1, 1]))) for k in pos]
+
+
+def test_two_pass_ring_with_eight_limbs_against_sparse_products(engine_ctx):
+    """logn 13, q = 2^438, W = 7, batch 2: the two-pass NTT, gpq_rns_mul_shared, small_to_rns_k and the key switch of enc_pk with eight limbs.
+    The secret and v are sparse, so the products are exact shifted sums of Python integers (_sparse_negacyclic); they fit the basis, so
+    poly_rns2mpi's centring mod P is the identity and the model is smod(product + ..., q)"""
+    from tests.test_ckks_roundtrip_gpu import _dense_of, _sparse_negacyclic
+    logn, logq, W, batch = 13, 438, 7, 2
+    q, dim = 1 << logq, enc_model.he_dim(logn, 1 << logq)
+    assert dim == 8 and W == logq // 64 + 1
+    g = engine_ctx(logn, dim)
+    n, rng = g.n, np.random.default_rng(13438)
+    P = 1
+    for p in g.p[:dim]:
+        P *= int(p)
+    smod = lambda t: enc_model.br.mpi_smod(t, q)
+    sk_terms, v_terms = _sparse_terms(rng, n, 5), [_sparse_terms(rng, n, 4) for _ in range(batch)]
+    sk = _dense_of(sk_terms, n)
+    a = [_raw(rng, logq, n) for _ in range(batch)]
+    pk = (_centred(rng, logq, n), _centred(rng, logq, n))
+    m = [[int(t) for t in rng.integers(-(1 << 40), 1 << 40, n)] for _ in range(batch)]
+    e, e1 = (rng.integers(-11, 12, (batch, n), dtype=np.int8) for _ in range(2))
+    v = np.array([_dense_of(t, n) for t in v_terms], dtype=np.int8)
+    xs = [_sparse_negacyclic(a[k], sk_terms, n) for k in range(batch)]
+    x0, x1 = ([_sparse_negacyclic(p, v_terms[k], n) for k in range(batch)] for p in pk)
+    assert all(2 * abs(t) < P for rows in (xs, x0, x1) for row in rows for t in row)                            # the products fit the basis
+    want = [[smod(-xs[k][i] + m[k][i] + int(e[k][i])) for k in range(batch) for i in range(n)], [smod(t) for row in a for t in row],
+            [smod(x0[k][i] + m[k][i] + int(e[k][i])) for k in range(batch) for i in range(n)],
+            [smod(x1[k][i] + int(e1[k][i])) for k in range(batch) for i in range(n)]]
+    flat = lambda rows: [t for row in rows for t in row]
+    dm, da = _big(flat(m), W, n), _big(flat(a), W, n)
+    de, de1, dv = (torch.from_numpy(t.reshape(-1)).cuda() for t in (e, e1, v))
+    c0, c1 = _outputs(da)
+    g.he_enc_sk(c0, c1, dm, da, de, _key_slab(g, _big(sk, W, n), W, dim), W, logq, dim)
+    d0, d1 = _outputs(da)
+    g.he_enc_pk(d0, d1, dm, dv, de, de1, _key_slab(g, _big(pk[0], W, n), W, dim), _key_slab(g, _big(pk[1], W, n), W, dim), W, logq, dim)
+    torch.cuda.synchronize()
+    for name, t, w in zip(("enc_sk c0", "enc_sk c1", "enc_pk c0", "enc_pk c1"), (c0, c1, d0, d1), want):
+        bad = np.flatnonzero(to_host(t) != np.concatenate([ints_to_words(w[k * n:(k + 1) * n], W) for k in range(batch)]))
+        assert not len(bad), "%s: %d words differ from the model, first at %d" % (name, len(bad), bad[0])
 
 
 def test_batch_larger_than_the_launch_group(engine_ctx):
@@ -236,13 +388,15 @@ def test_refusals(engine_ctx):
     torch.cuda.synchronize()
 
 
-def test_encode_encrypt_decrypt_decode_on_the_device(engine_ctx):
-    """gpq_he_ecd -> gpq_he_enc_pk -> gpq_he_dec -> gpq_he_dcd at logn 9, 16 slots, Delta 2^30: every slot within Bclean / Delta of the
+def _round_trip(engine_ctx, logq, logql, W):
+    """gpq_he_ecd -> gpq_he_enc_pk at 2^logq -> (logql < logq: gpq_he_rs by 0 bits, the centring mod 2^logql he_rs leaves behind) ->
+    gpq_he_dec at 2^logql -> gpq_he_dcd, all in W words, at logn 9, 16 slots, Delta 2^30: every slot within Bclean / Delta of the
     message, Bclean the reference's own bound for a key of Hamming weight 64 (src/precomp.c:413-415), evaluated here"""
-    logn, logq, slots, logDelta, batch = 9, 100, 16, 30, 3
-    g = engine_ctx(logn, 6)
-    n, W, nbits = g.n, 2, logq + 1
-    dim, dimdec, nb = enc_model.he_dim(logn, 1 << logq), (logq + 1) // 59 + 1, nbits // 8 + 1
+    logn, slots, logDelta, batch = 9, 16, 30, 3
+    dim, dimdec = enc_model.he_dim(logn, 1 << logq), (logql + 1) // 59 + 1
+    g = engine_ctx(logn, max(6, dim))
+    n, nbits = g.n, logq + 1
+    nb = nbits // 8 + 1
     rng = np.random.default_rng(930)
     dev_bytes = lambda count: torch.from_numpy(rng.integers(0, 256, count + 1, dtype=np.uint8)).cuda()[1:]      # (odd addresses)
     sk = enc_model.sample_hwt(enc_model.Stream(rng.integers(0, 256, 4096, dtype=np.uint8)), n)
@@ -256,7 +410,9 @@ def test_encode_encrypt_decrypt_decode_on_the_device(engine_ctx):
         m = g.he_ecd(plan, big(batch), z, logDelta=logDelta, W=W)
         v, e0, e1 = g.sample_zo(small(batch), dev_bytes(batch * n // 4)), g.sample_error(small(batch), dev_bytes(batch * n)), g.sample_error(small(batch), dev_bytes(batch * n))
         c0, c1 = g.he_enc_pk(big(batch), big(batch), m, v, e0, e1, _key_slab(g, p0, W, dim), _key_slab(g, p1, W, dim), W, logq, dim)
-        back = g.he_dec(big(batch), c0, c1, _key_slab(g, sk_big, W, dimdec), W, logq, dimdec)
+        if logql < logq:
+            g.he_rs(c0, c1, W, 0, logql)
+        back = g.he_dec(big(batch), c0, c1, _key_slab(g, sk_big, W, dimdec), W, logql, dimdec)
         out = g.he_dcd(plan, torch.empty_like(z), back, float(1 << logDelta), W)
         torch.cuda.synchronize()
     sigma, h = enc_model.SIGMA, 64
@@ -266,3 +422,16 @@ def test_encode_encrypt_decrypt_decode_on_the_device(engine_ctx):
     assert err <= Bclean / 2.0 ** logDelta
     assert not torch.equal(c0, m)                                              # (it is a ciphertext)
     assert err > 0
+
+
+def test_encode_encrypt_decrypt_decode_on_the_device(engine_ctx):
+    """q = 2^100 in two words, decrypted at the level it was encrypted at"""
+    _round_trip(engine_ctx, 100, 100, 2)
+
+
+def test_encode_encrypt_decrypt_decode_one_level_down(engine_ctx):
+    """the hand-off a program makes after he_rs: encrypted at 2^438 in seven words, decrypted at 2^388 in the same seven words with seven
+    limbs instead of eight; the same bound"""
+    logq, logql, W = 438, 388, 7
+    assert W == logq // 64 + 1 == logql // 64 + 1 and (logql + 1) // 59 + 1 < enc_model.he_dim(9, 1 << logq)
+    _round_trip(engine_ctx, logq, logql, W)

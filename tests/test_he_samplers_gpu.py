@@ -4,7 +4,11 @@ tests/test_ref_enc.py holds against the executed reference) on seeded bytes and 
 Byte inputs at offset 0 and at an odd offset of an allocation; rings of one byte per polynomial (logn 2), of a single-pass and of a
 two-pass size; every one of the 65536 byte pairs through the Gaussian table, the b1 = 0 ones included; uniform samples with a dropped last
 byte (nbits 64, 2040), with ragged bit counts, at the reference's default modulus (439 bits) and at W = 32, into a buffer filled with a
-pattern beforehand; a ring so small that a staging tile is partial and spans polynomials; and the refusals."""
+pattern beforehand; a ring so small that a staging tile is partial and spans polynomials; and the refusals.
+
+Every alignment: gpq_sample_error's input at each of the 16 byte offsets of a line and gpq_sample_zo's at each of the 4 of a dword, with byte
+counts that make one launch do vector lanes AND a tail, into aligned and unaligned outputs between guard bytes; gpq_sample_uniform with
+every byte count per coefficient 1..255, with W above the least, and with tiles shorter than the alignment head."""
 import ctypes as C
 import hashlib
 
@@ -75,6 +79,117 @@ def test_unaligned_small_slab_takes_the_byte_path(engine_ctx):
     g.sample_error(er, _bytes_at(eb, 0))
     assert np.array_equal(zo.cpu().numpy(), enc_model.zo_from_bytes(zb, g.n)) and np.array_equal(er.cpu().numpy(), enc_model.error_from_bytes(eb, g.n))
     assert not room[:3].any() and not room[3 + g.n:g.n + 21].any() and not room[2 * g.n + 21:].any()
+
+
+GUARD = 32
+
+
+def _guarded(nbytes, shift):
+    """(room, out): an int8 output of `nbytes` bytes, `shift` bytes past a 16-byte boundary, with GUARD patterned bytes on both sides"""
+    room = torch.full((2 * GUARD + nbytes,), 0x5A, dtype=torch.int8, device="cuda")
+    out = room[GUARD + shift:GUARD + shift + nbytes]
+    assert out.data_ptr() % 16 == shift
+    return room, out
+
+
+def _guards_kept(room, out):
+    lo = out.data_ptr() - room.data_ptr()
+    return bool((room[:lo] == 0x5A).all()) and bool((room[lo + out.numel():] == 0x5A).all())
+
+
+# gpq_sample_error: (logn, count) -> count n bytes = 16 per vector lane + a tail of pairs IN THE SAME LAUNCH when the output is aligned
+ERROR_SHAPES = {(7, 3): (24, 0), (3, 3): (1, 8), (4, 3): (3, 0), (5, 3): (6, 0), (2, 7): (1, 12), (1, 9): (1, 2)}     # -> (vectors, tail bytes)
+
+
+def test_error_at_every_input_alignment(engine_ctx):
+    """load16_any at each of its 16 shifts (p & 15: the a & 8 word move with and without a funnel shift, s == 0 at 0 and 8), with whole
+    vectors only, and with one vector plus tails of 1, 4 and 6 pairs in one launch; then the byte path (an output at an odd address) at
+    inputs {0, 7, 8, 9, 15}.  Guard bytes on both sides of the output stay"""
+    rng = np.random.default_rng(1616)
+    assert {t for _, t in ERROR_SHAPES.values()} >= {0, 2, 8, 12}                # whole vectors, and three different tail lengths
+    for (logn, count), (nvec, tail) in ERROR_SHAPES.items():
+        g = engine_ctx(logn, 2)
+        nbytes = count * g.n
+        assert (nbytes // 16, nbytes % 16) == (nvec, tail) and nvec >= 1        # tail > 0: nbytes % 16 != 0 and nbytes > 16, both paths in one launch
+        data = rng.integers(0, 256, nbytes, dtype=np.uint8)
+        data[1::2][::3] = 0                                                      # b1 = 0 pairs, in the tail too
+        want = np.concatenate([enc_model.error_from_bytes(data[k * g.n:(k + 1) * g.n], g.n) for k in range(count)])
+        runs = [(offset, 0) for offset in range(16)] + [(offset, shift) for offset, shift in ((0, 1), (7, 3), (8, 5), (9, 15), (15, 1))]
+        assert sum(1 for offset, shift in runs if not shift and offset & 8) == 8 and sum(1 for offset, shift in runs if not shift and not offset & 7) == 2
+        for offset, shift in runs:
+            room, out = _guarded(nbytes, shift)
+            assert (out.data_ptr() % 16 != 0) == bool(shift)                     # shift != 0: wide is false, everything goes by pairs
+            g.sample_error(out, _bytes_at(data, offset))
+            assert np.array_equal(out.cpu().numpy(), want), (logn, count, offset, shift)
+            assert _guards_kept(room, out), (logn, count, offset, shift)
+
+
+# gpq_sample_zo: (logn, count) -> count n/4 bytes = 4 per vector lane + a tail of single bytes
+ZO_SHAPES = {(3, 3): (1, 2), (4, 3): (3, 0), (5, 3): (6, 0), (7, 3): (24, 0), (2, 7): (1, 3)}                          # -> (vectors, tail bytes)
+
+
+def test_zo_at_every_input_alignment(engine_ctx):
+    """load4_any at each of its four shifts (p & 3) and at {8, 13} of a 16-byte line, with whole vectors only, and with one vector plus a
+    tail of 2 and of 3 bytes in one launch; into an aligned output and into an unaligned one (all by bytes), guards on both sides"""
+    rng = np.random.default_rng(44)
+    assert {t for _, t in ZO_SHAPES.values()} == {0, 2, 3}
+    for (logn, count), (nvec, tail) in ZO_SHAPES.items():
+        g = engine_ctx(logn, 2)
+        nbytes = count * g.n // 4
+        assert (nbytes // 4, nbytes % 4) == (nvec, tail) and nvec >= 1           # tail > 0: nbytes % 4 != 0 and nbytes > 4, both paths in one launch
+        data = rng.integers(0, 256, nbytes, dtype=np.uint8)
+        want = np.concatenate([enc_model.zo_from_bytes(data[k * g.n // 4:(k + 1) * g.n // 4], g.n) for k in range(count)])
+        offsets = (0, 1, 2, 3, 8, 13)
+        assert {t & 3 for t in offsets} == {0, 1, 2, 3}
+        for offset in offsets:
+            for shift in (0, 5):
+                room, out = _guarded(4 * nbytes, shift)
+                g.sample_zo(out, _bytes_at(data, offset))
+                assert np.array_equal(out.cpu().numpy(), want), (logn, count, offset, shift)
+                assert _guards_kept(room, out), (logn, count, offset, shift)
+
+
+def _uniform_sweep(g, rng, cases, count=1):
+    """[(nbits, W, offset)]: every launch into a patterned buffer against enc_model.uniform_from_bytes; the words above the value are zero"""
+    n = g.n
+    for nbits, W, offset in cases:
+        nb = nbits // 8 + 1
+        assert 64 * W > nbits
+        data = rng.integers(0, 256, count * n * nb, dtype=np.uint8)
+        data[nb - 1::nb] |= 0x80 | (1 << (nbits % 8))                          # set in every coefficient: the first dropped bit and the top bit of the last byte
+        got = _uniform(g, data, nbits, W, count, offset)
+        want = [enc_model.uniform_from_bytes(data[k * n * nb:(k + 1) * n * nb], n, nbits) for k in range(count)]
+        assert np.array_equal(got, np.concatenate([ints_to_words(v, W) for v in want])), (nbits, W, offset)
+        assert not got.reshape(count, W, n)[:, (nbits + 63) // 64:, :].any()    # (what ints_to_words put there: zero, not the pattern)
+
+
+def test_uniform_at_every_byte_count_per_coefficient(engine_ctx):
+    """logn 6, count 1 = exactly one full staging tile, W the least: nb = nbits / 8 + 1 takes every value 1..255 (256 is
+    test_uniform_equals_the_model's 2040), so __umulhi(o, magic) divides by every nb it can meet and nb == 1 takes its own branch; bit
+    counts at a byte and at a word boundary; inputs at offset 0 (head 0) and 5 (head 11, which nb < 11 makes span coefficients)"""
+    g = engine_ctx(6, 2)
+    assert g.n == 64                                                             # kUniformTile
+    widths = [1, 7, 8, 15, 16, 63] + [8 * k + 3 for k in range(255)]
+    assert {t // 8 + 1 for t in widths} == set(range(1, 256)) and [t for t in widths if t < 8] == [1, 7, 3]     # nb == 1 three times over
+    _uniform_sweep(g, np.random.default_rng(255), [(nbits, nbits // 64 + 1, offset) for nbits in widths for offset in (0, 5)])
+
+
+def test_uniform_with_words_above_the_least(engine_ctx):
+    """W = 32 for values of 1 .. 17 words: the planes above the value are written as zero (64 j >= nbits), not left as the pattern"""
+    g = engine_ctx(6, 2)
+    widths = [1, 7, 8, 63, 64, 439, 1027]
+    assert all(32 > t // 64 + 1 for t in widths)
+    _uniform_sweep(g, np.random.default_rng(32), [(nbits, 32, offset) for nbits in widths for offset in (0, 5)])
+
+
+def test_uniform_with_tiles_shorter_than_the_alignment_head(engine_ctx):
+    """logn 2: count 1 at nbits 1 is a launch of 4 bytes at offset 3, fewer than the 13 bytes to the next 16-byte line (head > len, clamped);
+    count 5 at nbits 17 is 20 coefficients of 3 bytes at offset 9: one partial tile over five polynomials, head 7 = two coefficients and a byte"""
+    g = engine_ctx(2, 2)
+    rng = np.random.default_rng(2)
+    assert g.n * 1 * (1 // 8 + 1) == 4 < (-3) % 16 and 5 * g.n < 64 and (-9) % 16 == 7 and 7 % (17 // 8 + 1) != 0
+    _uniform_sweep(g, rng, [(1, 1, 3)], count=1)
+    _uniform_sweep(g, rng, [(17, 1, 9), (17, 2, 9)], count=5)
 
 
 def _uniform(g, data, nbits, W, count, offset):
