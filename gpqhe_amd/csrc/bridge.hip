@@ -173,13 +173,12 @@ static unsigned first_unfit_wide_limb(const gpq_ctx *c, const std::vector<LimbTa
 int get_scaled_tabs(gpq_ctx *c, gpq_bridge_basis *b, const LimbTab **out) {
   if (!b->d_tabs_scaled) {
     std::vector<LimbTab> t = c->h_tabs;
-    auto pair_of = [](uint64_t w, uint64_t p) { return TwS{p - w, p - (uint64_t)(((u128h)w << 31) % p)}; };
     for (unsigned d = 0; d < b->dim; ++d) {
       LimbTab &e = t[b->first + d];
       const uint64_t p = e.k.p, s = b->h_phat_inv[d];
       e.ninv = (uint64_t)((u128h)e.ninv * s % p);
       e.winv1_ninv = (uint64_t)((u128h)e.winv1_ninv * s % p);
-      if (b->first + d < c->nsplit_tables) { e.ninv_s = pair_of(e.ninv, p); e.winv1_ninv_s = pair_of(e.winv1_ninv, p); }
+      if (b->first + d < c->nsplit_tables) { e.ninv_s = split_pair_of(e.ninv, p); e.winv1_ninv_s = split_pair_of(e.winv1_ninv, p); }
     }
     const unsigned unfit = first_unfit_wide_limb(c, t, b->first, b->dim);
     DeviceScope on_device(c->device);
@@ -940,13 +939,12 @@ int get_relin_front(gpq_ctx *c, unsigned dimP, unsigned dimB, gpq_relin_tables *
   // the context's per-limb table for the key switch's inverse pass: (P/p_d)^-1 on the limbs of P, w_j above
   std::vector<LimbTab> tw = c->h_tabs;
   if (!tw.empty()) {
-    auto pair_of = [](uint64_t w, uint64_t p) { return TwS{p - w, p - (uint64_t)(((u128h)w << 31) % p)}; };
     for (unsigned d = 0; d < dimB; ++d) {
       LimbTab &e = tw[d];
       const uint64_t p = e.k.p, sc = d < dimP ? bp->h_phat_inv[d] : wscale[d - dimP];
       e.ninv = (uint64_t)((u128h)e.ninv * sc % p);
       e.winv1_ninv = (uint64_t)((u128h)e.winv1_ninv * sc % p);
-      if (d < c->nsplit_tables) { e.ninv_s = pair_of(e.ninv, p); e.winv1_ninv_s = pair_of(e.winv1_ninv, p); }
+      if (d < c->nsplit_tables) { e.ninv_s = split_pair_of(e.ninv, p); e.winv1_ninv_s = split_pair_of(e.winv1_ninv, p); }
     }
   }
   DeviceScope on_device(c->device);

@@ -191,10 +191,7 @@ static int upload_tables(gpq_ctx *c) {
       wistd[d * n + i] = from_mont(c->zetas_inv[d * n + i]);
     }
     LimbTab &t = tabs[d];
-    t.k.p = p; t.k.p2 = 2 * p; t.k.p4 = 4 * p; t.k.c = (uint32_t)(p - (1ull << 59)); t.k.c1 = t.k.c + 1;
-    t.k.kinj = 31 * (uint64_t)t.k.c - 1; t.k.one = 1;     // mulmod_split's injected K = 2^64 + 31c - 1 (modarith.hpp)
-    t.k.p3 = 3 * p; t.k.np3 = (uint64_t)0 - 3 * p;
-    t.k.np = (uint64_t)0 - p; t.k.np2 = (uint64_t)0 - 2 * p; t.k.np4 = (uint64_t)0 - 4 * p;
+    t.k = make_prime_k(p);
     t.ninv = from_mont(c->ninv_mont[d]);
     t.winv1_ninv = n >= 2 ? mulm(wistd[d * n + 1], t.ninv, p) : t.ninv;
     t.ninv_s = t.winv1_ninv_s = TwS{0, 0};
@@ -210,15 +207,14 @@ static int upload_tables(gpq_ctx *c) {
   if (c->nsplit) {
     const size_t ns = c->nsplit;
     std::vector<TwS> ws(ns * n), wis(ns * n);
-    auto pair_of = [](uint64_t w, uint64_t p) { return TwS{p - w, p - (uint64_t)(((u128h)w << 31) % p)}; };
     for (size_t d = 0; d < ns; ++d) {
       const uint64_t p = c->p[d];
       for (size_t i = 0; i < n; ++i) {
-        ws[d * n + i] = pair_of(wstd[d * n + i], p);
-        wis[d * n + i] = pair_of(wistd[d * n + i], p);
+        ws[d * n + i] = split_pair_of(wstd[d * n + i], p);
+        wis[d * n + i] = split_pair_of(wistd[d * n + i], p);
       }
-      tabs[d].ninv_s = pair_of(tabs[d].ninv, p);
-      tabs[d].winv1_ninv_s = pair_of(tabs[d].winv1_ninv, p);
+      tabs[d].ninv_s = split_pair_of(tabs[d].ninv, p);
+      tabs[d].winv1_ninv_s = split_pair_of(tabs[d].winv1_ninv, p);
       // the wide butterflies run multiplicands up to 8p - 1 through the injected multiply: every entry they read (index 0, the
       // twiddle 1, is read by no stage) must keep th in 32 bits.  A limb with a failing entry ends the wide range: it and the
       // limbs after it take the split class, whose multiplicands (< 6p) leave the margin for any entry.

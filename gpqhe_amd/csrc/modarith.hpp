@@ -60,6 +60,17 @@ struct PrimeK {        // per-limb constants handed to kernels (uniform per bloc
   uint32_t one;        // 1: the high dword of K's carry word; the kernels keep it in one VGPR (pin_consts)
 };
 
+// Host side: the constants of one prime p = 2^59 + c.  The one place they are computed: the context's LimbTab (engine.hip:
+// upload_tables) and the primitive probe (modarith_probe.hip) both take them from here.
+inline PrimeK make_prime_k(uint64_t p) {
+  PrimeK k;
+  k.p = p; k.p2 = 2 * p; k.p4 = 4 * p; k.c = (uint32_t)(p - (1ull << 59)); k.c1 = k.c + 1;
+  k.kinj = 31 * (uint64_t)k.c - 1; k.one = 1;     // mulmod_split's injected K = 2^64 + 31c - 1
+  k.p3 = 3 * p; k.np3 = (uint64_t)0 - 3 * p;
+  k.np = (uint64_t)0 - p; k.np2 = (uint64_t)0 - 2 * p; k.np4 = (uint64_t)0 - 4 * p;
+  return k;
+}
+
 // The 1 in the high dword of mulmod_split's carry word has to sit in a VGPR next to the carry.  As a literal or a table scalar the
 // compiler re-materialises it with a v_mov per multiply (what the removed 64-bit add cost, back again); pinned once at kernel entry
 // it is an opaque value in ONE VGPR that every multiply of the kernel shares, as they shared the zero register.  (31c - 1, the other
@@ -189,6 +200,9 @@ __device__ __forceinline__ void gs_bfly(uint64_t &x, uint64_t &y, uint64_t w, co
 // (tests/test_lazy_ranges.py is the integer model; measured in tools/bfly_lab at the 4p / 2p ranges: +20 % CT, +27 % GS over the 7-mad form.)
 // ---------------------------------------------------------------------------
 typedef ulonglong2 TwS;   // .x = p - w, .y = p - (w*2^31 mod p)
+
+// Host side: the table entry of a multiplier w < p (twiddle tables and last-stage constants, engine.hip and bridge.hip).
+inline TwS split_pair_of(uint64_t w, uint64_t p) { return TwS{p - w, p - (uint64_t)(((u128)w << 31) % p)}; }
 
 // Same storage, other butterflies: the forward stages of limbs with c < GPQ_WIDE_CMAX (ct_bfly_wide).
 struct alignas(16) TwW { uint64_t x, y; };

@@ -2,8 +2,9 @@
 (gpqhe_amd/csrc/modarith.hpp: mulmod_split injects K = 2^64 + 31c - 1 == -(c+1), mulmod_raw_t injects c+1) and of every
 butterfly class built on them: the results are congruent to the product with nothing left to add, every intermediate fits
 the register it lives in, the lazy ranges close as the header states them, and the table check of the wide class rejects
-exactly the entries whose fold would outgrow 32 bits.  CPU only; the kernels are compared with the oracle word for word in
-tests/test_inject_gpu.py."""
+exactly the entries whose fold would outgrow 32 bits.  CPU only: this proves the algebra, on a restatement.  The HIP text of the
+primitives is run on the device at the edges of these ranges by tests/test_modarith_device_gpu.py; the kernels are compared with the
+oracle word for word in tests/test_inject_gpu.py."""
 import random
 
 import pytest

@@ -1,6 +1,7 @@
 """Integer model of the split-twiddle multiply and of the wide-split forward stages (gpqhe_amd/csrc/modarith.hpp):
 every intermediate fits the register it lives in and the lazy ranges close, for the largest c each class admits.
-CPU only; the kernels themselves are checked bit for bit on the GPU (tests/test_ntt_gpu.py)."""
+CPU only: this proves the algebra, on a restatement.  The HIP text of the primitives is run on the device at the edges of these ranges by
+tests/test_modarith_device_gpu.py; whole kernels are checked bit for bit on the GPU (tests/test_ntt_gpu.py)."""
 import random
 
 import pytest
