@@ -210,7 +210,7 @@ struct ReconMfmaArgs {
   Two<const uint64_t> addend;    // optional [polys][Wout][n]: d of src/he-mult.c:72-76
   const unsigned char *rflags;   // optional [polys][n]: RF_GT = round the quotient up (mpi_rdiv)
   unsigned prescaled;            // the slab already holds y_d = ahat_d * phat_invmp_d (bridge_relin_front_mfma writes it so)
-  // The whole relinearisation tail as ONE product (WL = 16 only; bridge.hip: tail_direct): with frac_bits = 104 the constant matrix holds
+  // The whole relinearisation tail as ONE product (WL = 16 only; bridge_tail.hpp: tail_product): with frac_bits = 104 the constant matrix holds
   // floor(Pi' 2^104 / p_d) for ALL limbs of the key switch's basis, so the columns are 2^104 x / P as a fixed-point number -- the low
   // 104 bits its fraction (x mod P) / P, the rest floor(x / P): the quotient and the rounding decision of mpi_rdiv come out of the same
   // contraction that centres x, without the residues of r = x mod P, without the exact division, without a second CRT.

@@ -317,7 +317,7 @@ struct CrtDecomposeArgs {
   unsigned char *redo;       // [polys][n]
   unsigned *wave_any;        // [waves of the launch]
   unsigned dimA, dimB, NTD, logn, logq, W, total_groups;
-  unsigned dimS;             // limbs per polynomial of `out` (its stride); = dimB unless a launch writes a sub-range of the limbs (A/B builds: GPQ_CRT_SPLIT)
+  unsigned dimS;             // limbs per polynomial of `out` (its stride); always dimB today (it differed in the two-launch A/B form GPQ_CRT_SPLIT, measured 38 % slower and removed: profiles/README.md)
   unsigned force;            // tests: also flag every coefficient whose index is a multiple of it (the exact kernels must then give the same words)
   unsigned lazy;             // residues out in (0, 3p) for the forward transform that follows (decompose_tile_finish)
 };

@@ -48,18 +48,13 @@ int encode(gpq_ctx *c, const gpq_ecd_plan *p, uint64_t *out, const double *src, 
   int dev = -1;
   if (hipGetDevice(&dev) == hipSuccess && dev != c->device)
     return gpq_fail(GPQ_ERR_INVALID, "%s: the context lives on device %d but the calling thread's current device is %d (gpq_set_device(gpq_ctx_device(ctx)) first)", who, c->device, dev);
-  static bool raised[64] = {};
-  const size_t lds = (size_t)p->slots * 16;
-  if (lds > 65536 && !(dev >= 0 && dev < 64 && raised[dev])) {            // dynamic LDS above 64 KB needs the attribute, once per device
-    HIP_TRY(hipFuncSetAttribute((const void *)he_ecd_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kEcdMaxSlots * 16)));
-    if (dev >= 0 && dev < 64) raised[dev] = true;
-  }
+  const size_t lds = (size_t)p->slots * 16;                                // above 64 KB for many slots: gpq_launch_lds
   EcdArgs a{src, out, p->d_roots, p->d_pow5, bad, std::ldexp(1.0, (int)logDelta), 1.0 / p->slots, p->slots, p->logslots, c->logn, W, n1};
   const unsigned threads = (p->slots / 2 >= kEcdMaxThreads || ((size_t)W << c->logn) >= 8192) ? kEcdMaxThreads : 256u;
   hipStream_t s = (hipStream_t)stream;
   {
     ProfScope prof(c, GPQ_K_ECD, s);
-    hipLaunchKernelGGL(he_ecd_lds, dim3(count), dim3(threads), lds, s, a);
+    if (int rc = gpq_launch_lds<&he_ecd_lds>((int)(kEcdMaxSlots * 16), dim3(count), dim3(threads), lds, s, a)) return rc;
   }
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? GPQ_OK : gpq_fail(GPQ_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(e));
@@ -146,18 +141,13 @@ extern "C" int gpq_he_dcd(gpq_ctx *c, const gpq_ecd_plan *p, double *z_dev, cons
   int dev = -1;
   if (hipGetDevice(&dev) == hipSuccess && dev != c->device)
     return gpq_fail(GPQ_ERR_INVALID, "%s: the context lives on device %d but the calling thread's current device is %d (gpq_set_device(gpq_ctx_device(ctx)) first)", who, c->device, dev);
-  static bool raised[64] = {};
-  const size_t lds = (size_t)p->slots * 16;
-  if (lds > 65536 && !(dev >= 0 && dev < 64 && raised[dev])) {            // the attribute is per kernel function: he_ecd_lds having it does not serve
-    HIP_TRY(hipFuncSetAttribute((const void *)he_dcd_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kEcdMaxSlots * 16)));
-    if (dev >= 0 && dev < 64) raised[dev] = true;
-  }
+  const size_t lds = (size_t)p->slots * 16;                                // (the attribute is per kernel function: he_ecd_lds having it does not serve)
   DcdArgs a{in, z_dev, p->d_roots, p->d_pow5, nu, p->slots, p->logslots, c->logn, W};
   const unsigned threads = p->slots >= kEcdMaxThreads ? kEcdMaxThreads : 256u;     // 2 slots conversions, slots / 2 butterflies per stage
   hipStream_t s = (hipStream_t)stream;
   {
     ProfScope prof(c, GPQ_K_DCD, s);
-    hipLaunchKernelGGL(he_dcd_lds, dim3(count), dim3(threads), lds, s, a);
+    if (int rc = gpq_launch_lds<&he_dcd_lds>((int)(kEcdMaxSlots * 16), dim3(count), dim3(threads), lds, s, a)) return rc;
   }
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? GPQ_OK : gpq_fail(GPQ_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(e));

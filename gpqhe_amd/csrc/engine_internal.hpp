@@ -1,5 +1,6 @@
 // engine_internal.hpp -- the context object behind the opaque gpq_ctx handle.
 #pragma once
+#include <atomic>
 #include <cstdio>
 #include <map>
 #include <set>
@@ -37,7 +38,7 @@ struct gpq_recon_mfma {
   size_t lds_bytes = 0;
 };
 
-// CRT constants of one prefix of the prime chain (bridge.hip)
+// CRT constants of one prefix of the prime chain (bridge_tables.hpp)
 struct gpq_bridge_basis {
   unsigned first = 0, dim = 0, pbits = 0;
   int WP = 0;
@@ -46,7 +47,7 @@ struct gpq_bridge_basis {
   std::vector<uint64_t> h_P;          // the product itself, little-endian words
   std::vector<uint64_t> h_phat;       // [dim][WP]
   std::map<int, gpq_recon_mfma> mfma; // by result width WL
-  gpq::LimbTab *d_tabs_scaled = nullptr;   // the context's LimbTab array with n^-1 * (P/p_d)^-1 for the limbs of this basis (ScaledInverse, bridge.hip)
+  gpq::LimbTab *d_tabs_scaled = nullptr;   // the context's LimbTab array with n^-1 * (P/p_d)^-1 for the limbs of this basis (ScaledInverse, bridge_tables.hpp)
 };
 
 // Constant matrix of the matrix-core rns_decompose for (first limb, limbs, words) (bridge_mfma.hpp)
@@ -67,11 +68,11 @@ struct gpq_relin_tables {
   unsigned NT = 0, KS = 0;
   size_t lds_bytes = 0;
   // the same tables for limbs that arrive multiplied by w_j = P^-1 (Pi'/p_j)^-1, and the per-limb table that makes the key switch's
-  // inverse pass deliver them so (bridge.hip: get_relin_front, tail_prescale_mode)
+  // inverse pass deliver them so (bridge_tables.hpp: get_relin_front; bridge_tail.hpp: tail_prescale_mode)
   void *d_bfrag_w = nullptr;
   uint64_t *d_pk_w = nullptr, *d_tkp_w = nullptr;
   gpq::LimbTab *d_tabs_w = nullptr;
-  // the one-product tail (bridge.hip: get_tail_direct): constant matrix of floor(Pi' 2^104 / p_d) over all dimB limbs, the per-limb table that
+  // the one-product tail (bridge_tables.hpp: get_tail_direct): constant matrix of floor(Pi' 2^104 / p_d) over all dimB limbs, the per-limb table that
   // makes the key switch deliver CRT-weighted limbs (owned by the basis), the weights and their inverses for bridge_limb_scale
   bool direct_tried = false;
   gpq_recon_mfma direct;
@@ -81,7 +82,7 @@ struct gpq_relin_tables {
 };
 
 // Everything a context builds once and only reads afterwards on the device: the transform tables of upload_tables (engine.hip) and the bridge
-// constants bridge.hip builds at first use.  ONE object per prime chain: a context's peer lane (gpq_ctx_clone) points at its parent's, so the second
+// constants bridge_tables.hpp builds at first use.  ONE object per prime chain: a context's peer lane (gpq_ctx_clone) points at its parent's, so the second
 // lane costs no table memory, no table-building time, and "the peer's tables differ" is not a state the library can be in.  Built and read by the
 // one host thread that drives the context (single caller); uploads are synchronous hipMemcpy, so a launch on either lane's stream that
 // follows a build on the host sees the table.
@@ -91,7 +92,7 @@ struct gpq_table_cache {
   std::map<std::pair<std::pair<unsigned, unsigned>, unsigned>, gpq_decomp_mfma> decomps;  // by ((first limb, limbs), W)
   size_t device_bytes = 0;            // read-only device memory behind this cache and the transform tables (gpq_table_malloc)
   uint16_t *d_error_table = nullptr;  // gpq_sample_error's 65536 coefficient pairs (enc.hip), uploaded at first use
-  // Scaled per-limb tables (ScaledInverse, bridge.hip) one of whose split pairs fails the wide class's table check (modarith.hpp:
+  // Scaled per-limb tables (ScaledInverse, bridge_tables.hpp) one of whose split pairs fails the wide class's table check (modarith.hpp:
   // split_entry_fits_wide), with the first such limb: a context that reads the table runs that limb and those after it in the split class.
   // Empty for every chain met so far (the failing constants are ~100 values in 2^59).
   std::map<const gpq::LimbTab *, unsigned> scaled_wide_limit;
@@ -113,10 +114,10 @@ struct gpq_ctx {
   bool low9 = false;                              // n = 2^17: strided passes over 512-coefficient rows, 9 low stages (Lane8<9>)
   unsigned nwide = 0, nwide_max = 0;              // leading limbs with c < GPQ_WIDE_CMAX (<= nsplit): forward stages as ct_bfly_wide
   gpq::LimbTab *d_tabs = nullptr;
-  std::vector<gpq::LimbTab> h_tabs;               // host copy (bridge.hip derives tables with pre-scaled n^-1 from it)
+  std::vector<gpq::LimbTab> h_tabs;               // host copy (bridge_tables.hpp derives tables with pre-scaled n^-1 from it)
   // When set, the inverse strided pass of gpq_he_mul_tensor / gpq_keyswitch reads its per-limb constants here: the same tables
   // with n^-1 (and winv[1] n^-1) multiplied by a CRT weight, so that the limbs leave the transform already scaled for the
-  // reconstruction that follows (bridge.hip: ScaledInverse).  Internal to gpq_he_mul / gpq_he_swk.
+  // reconstruction that follows (bridge_tables.hpp: ScaledInverse).  Internal to gpq_he_mul / gpq_he_swk.
   const gpq::LimbTab *inv_tabs_override = nullptr;
   gpq_table_cache *cache = nullptr;   // the lazily built bridge constants (owned unless tables_of is set)
   const gpq_ctx *tables_of = nullptr; // a peer lane: d_w / d_winv / d_ws / d_winvs / d_tabs and `cache` are the PARENT's, borrowed for the parent's lifetime
@@ -132,7 +133,7 @@ struct gpq_ctx {
   bool exact_crt = false;             // force the exact CRT kernel (tests)
   bool prescale = true;               // gpq_he_mul / gpq_he_swk: inverse passes write limbs pre-multiplied by (P/p_d)^-1 for the CRT kernels (gpq_set_prescale)
   bool prescale_upper = true;         // ... and the limbs above P by w_j for the relinearisation front
-  bool tail_direct = true;            // ... or every limb by the weights of the whole basis: the relinearisation tail as ONE product (bridge.hip: get_tail_direct)
+  bool tail_direct = true;            // ... or every limb by the weights of the whole basis: the relinearisation tail as ONE product (bridge_tables.hpp: get_tail_direct)
   bool fuse_tail = false;             // gpq_set_fused_tail(ctx, 1): the relinearisation tail in one pass per coefficient (bridge_relin_tail_mfma) -- measured 2 % SLOWER
                                       // than the two-kernel form on the whole he_mul (profiles/r03/v3_fused_tail_ab.txt: both are bound by integer VALU work, not by the
                                       // 60 words per coefficient the fusion saves), kept for the parity tests and as the record of the attempt
@@ -226,6 +227,25 @@ inline hipError_t gpq_table_malloc(gpq_ctx *c, void **p, size_t bytes) {
   return e;
 }
 void gpq_bridge_release(gpq_ctx *c);
+
+// Launches a kernel whose dynamic LDS may exceed 64 KB.  That needs the function attribute (ceiling `lds_max`), set once per (kernel, device):
+// per kernel through the template argument -- one flag array per kernel address -- and per device through the calling thread's current one.
+// The flags are atomics because host threads that drive contexts on different devices meet here; a context and its peer still belong to one
+// thread at a time (include/gpqhe_hip.h).  Two threads that find a flag clear both set the attribute, to the same value.
+template <auto Kernel, typename Args>
+int gpq_launch_lds(int lds_max, dim3 grid, dim3 block, size_t lds, hipStream_t s, const Args &a) {
+  static std::atomic<bool> raised[64] = {};
+  int d = -1;
+  hipError_t e = hipGetDevice(&d);
+  const bool known = e == hipSuccess && d >= 0 && d < 64;
+  if (e == hipSuccess && !(known && raised[d].load(std::memory_order_acquire))) {
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
+    if (e == hipSuccess && known) raised[d].store(true, std::memory_order_release);
+  }
+  if (e != hipSuccess) return gpq_fail(GPQ_ERR_HIP, "dynamic LDS limit of a kernel: %s", hipGetErrorString(e));
+  hipLaunchKernelGGL(Kernel, grid, block, lds, s, a);
+  return GPQ_OK;
+}
 
 // ---------------------------------------------------------------------------
 // Two launch groups in flight (gpq_set_overlap).  A call over more than one launch group hands every other group to the context's PEER -- a

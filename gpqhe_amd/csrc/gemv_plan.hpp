@@ -1,6 +1,6 @@
 // gemv_plan.hpp -- he_gemv for a fixed matrix (include/gpqhe_hip.h, "he_gemv with a plan"): the plan object, one giant step's inner sum in
 // the NTT domain (gpq_gemv_inner) and the whole call (gpq_he_gemv_planned).  Part of bridge.hip's translation unit (it uses that file's
-// launch_decompose, gemv_steps, align64 and check); the kernel is gemv_mac in ntt_kernels.hpp, launched by engine.hip's gpq_gemv_mac.
+// gemv_steps and align64, and bridge_launch.hpp's launch_decompose and check); the kernel is gemv_mac in ntt_kernels.hpp, launched by engine.hip's gpq_gemv_mac.
 //
 // The inner sum is exact, not approximate: see the header for the identity, the bound behind gpq_gemv_acc_dim and the guard.  What runs per
 // call: the live baby rotations as ONE gpq_he_rot_hoisted, their rns_decompose + complete forward transform over `dim` limbs once, and per

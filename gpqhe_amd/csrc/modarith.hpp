@@ -196,12 +196,12 @@ __device__ __forceinline__ void gs_bfly(uint64_t &x, uint64_t &y, uint64_t w, co
 // w + (w*2^31 mod p) < 2c + 15 * 2^29: w = q 2^28 + j with j = 1, 2, 3 and q (2^28 - c) < (15 - 4j) 2^29 + 2c, i.e. q from 0 up to 22..44, 14..28, 6..12
 // by c (w*2^31 = q p + j 2^31 - q c): some hundred values in 2^59, no root of unity of a real chain.  split_entry_fits_wide is the exact bound; the host checks every pair a
 // wide limb reads with it -- the twiddle tables and the last stage's constants (engine.hip: upload_tables), and the scaled copies of those
-// constants the bridge builds (bridge.hip: first_unfit_wide_limb) -- and a limb with a failing pair leaves the wide class.
+// constants the bridge builds (bridge_tables.hpp: first_unfit_wide_limb) -- and a limb with a failing pair leaves the wide class.
 // (tests/test_lazy_ranges.py is the integer model; measured in tools/bfly_lab at the 4p / 2p ranges: +20 % CT, +27 % GS over the 7-mad form.)
 // ---------------------------------------------------------------------------
 typedef ulonglong2 TwS;   // .x = p - w, .y = p - (w*2^31 mod p)
 
-// Host side: the table entry of a multiplier w < p (twiddle tables and last-stage constants, engine.hip and bridge.hip).
+// Host side: the table entry of a multiplier w < p (twiddle tables and last-stage constants, engine.hip and bridge_tables.hpp).
 inline TwS split_pair_of(uint64_t w, uint64_t p) { return TwS{p - w, p - (uint64_t)(((u128)w << 31) % p)}; }
 
 // Same storage, other butterflies: the forward stages of limbs with c < GPQ_WIDE_CMAX (ct_bfly_wide).

@@ -126,6 +126,8 @@ int gpq_device_local_cpus(int device, const char *sysfs_root, char *cpulist, siz
  * that its launches share in stream order (gpq_ntt's zero flags, the per-coefficient redo flags and per-wave words of the bridge,
  * the table override of gpq_he_mul's inverse passes).  Work that should overlap on several streams uses one context per stream
  * (contexts of the same ring share nothing mutable; tools/ntt_stream_probe.py, tests/c/shard_host.c do exactly that).
+ * A context and its peer lane (gpq_set_overlap) belong to ONE host thread at a time.  Threads that drive different contexts, one per
+ * device, may call concurrently: the only state they share is the once-per-(kernel, device) LDS attribute flags, which are atomic.
  */
 
 /* ntt / invntt over every limb of every polynomial, in place.

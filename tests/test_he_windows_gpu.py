@@ -26,7 +26,7 @@ from tests.he_anchors import assert_anchored, expect_all, he_mul_tasks, he_swk_t
 pytestmark = pytest.mark.gpu
 
 # (logn, log2 q_L, log2 q_l).  The key switch hands the tail limbs weighted for the one-product tail only in the two-pass transforms
-# (bridge.hip: can_prescale, logn > 12), so n = 2^13 is the smallest ring in which bridge_tail_stream runs inside a whole call:
+# (bridge_tables.hpp: can_prescale, logn > 12), so n = 2^13 is the smallest ring in which bridge_tail_stream runs inside a whole call:
 #   STREAM_SHAPES  dims 4/8/12 (<8,4,true,6>, he_swk <6,0,false,3>); 8/16/24, the reference's default limb counts; 15/30/45 with 14 words
 #                  (<12,8,true,5>, <12,0,false,4>); a lower level of it (zero-padded k steps) -- here the profile must show the streaming tail;
 #   SMALL_SHAPES   the same moduli in single-pass rings (dims 4/7/11, 8/16/24, 15/30/45): the same coefficients reach round 3's tail
@@ -285,7 +285,7 @@ def test_a_wave_that_walks_several_groups(engine_ctx, oracle_ctx):
     logn, logq, batch = 13, 438, 9
     g, o, dims, W, M = _setup(engine_ctx, oracle_ctx, logn, logq, logq)
     n, ql, (dimA, dimB, dimP) = g.n, 1 << logq, dims
-    assert 2 * batch * (n // 64) > 8 * 256                 # more groups than waves (bridge.hip: kStreamBlocks, kStreamWaves)
+    assert 2 * batch * (n // 64) > 8 * 256                 # more groups than waves (bridge_launch.hpp: kStreamBlocks, kStreamWaves)
     rng = random.Random(9100)
     crafted = [wc.build(M, n, 71), wc.build(M, n, 72)]
     _report("n=2^13 q=2^438, 2304 groups", crafted)

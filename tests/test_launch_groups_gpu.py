@@ -183,7 +183,7 @@ def test_gpq_ntt_zero_flags_in_every_launch_group(oracle_ctx, logn):
         _free()
 
 
-# ---- bridge launches whose grid carries the batch in y (bridge.hip): a batch above 65 535 polynomials ----------------------------
+# ---- bridge launches whose grid carries the batch in y (bridge_launch.hpp, bridge.hip): a batch above 65 535 polynomials ----------------------------
 
 BRIDGE_BATCH = 65537
 

@@ -5,7 +5,7 @@ THE CONSTRUCTION.  The key switch of the constant polynomial 1 with the key NTT(
 a1 = b1 = 1, hence d2 = 1; he_swk / he_rot: d1 = 1) and a key that is the forward transform of chosen residues, the tail is handed exactly
 the integers chosen here, while dense d0, d1 become its addends.
 
-THE MODEL (TailModel) restates the tail's fixed-point estimate from its definition (bridge.hip, get_tail_direct's comment), never from a
+THE MODEL (TailModel) restates the tail's fixed-point estimate from its definition (bridge_tables.hpp, get_tail_direct's comment), never from a
 kernel's output:  y_d = x_d (Pi_B/p_d)^-1 mod p_d,  weight_d = floor(Pi' 2^104 / p_d),  V = sum y_d weight_d,  frac = V mod 2^104  -- an
 underestimate of 2^104 (x mod P)/P by less than dimP 2^60.  A coefficient is IN A WINDOW when bits 102..66 of frac are all ones: bit 103
 clear = within 2^-38 below 1/2 (mpi_rdiv's decision), set = within 2^-38 below 1 (the estimate may have borrowed from floor(x/P)).  The
