@@ -26,47 +26,9 @@ using namespace gpq;
 #include "bridge_launch.hpp"   // one launcher per kernel family
 #include "bridge_tail.hpp"     // the relinearisation tail: tail_prescale_mode, relin_tail and its four flows
 
-void gpq_bridge_release(gpq_ctx *c) {
-  // the context's own mutable words
-  if (c->d_redo) (void)hipFree(c->d_redo);
-  c->d_redo = nullptr; c->redo_cap = 0;
-  if (c->d_wave_any) (void)hipFree(c->d_wave_any);
-  c->d_wave_any = nullptr;
-  for (void *old : c->retired) (void)hipFree(old);
-  c->retired.clear();
-  // the constant cache: the owner's to free (a peer lane borrows its parent's, engine_internal.hpp)
-  if (c->tables_of || !c->cache) { c->cache = nullptr; return; }
-  for (auto &kv : c->cache->bases) {
-    (void)hipFree(kv.second.d_phat); (void)hipFree(kv.second.d_phat_inv);
-    (void)hipFree(kv.second.d_pmult); (void)hipFree(kv.second.d_phalf); (void)hipFree(kv.second.d_inv128);
-    if (kv.second.d_tabs_scaled) (void)hipFree(kv.second.d_tabs_scaled);
-    for (auto &m : kv.second.mfma) {
-      if (m.second.d_bfrag) (void)hipFree(m.second.d_bfrag);
-      if (m.second.d_lk) (void)hipFree(m.second.d_lk);
-      if (m.second.d_kc) (void)hipFree(m.second.d_kc);
-      if (m.second.d_pm) (void)hipFree(m.second.d_pm);
-    }
-  }
-  for (auto &kv : c->cache->relins) {
-    (void)hipFree(kv.second.d_pinv);
-    for (void *q : {kv.second.d_bfrag, (void *)kv.second.d_lk, (void *)kv.second.d_pk, (void *)kv.second.d_tkp, (void *)kv.second.d_kf,
-                    kv.second.d_bfrag_w, (void *)kv.second.d_pk_w, (void *)kv.second.d_tkp_w, (void *)kv.second.d_tabs_w,
-                    kv.second.direct.d_bfrag, (void *)kv.second.direct.d_lk, (void *)kv.second.direct.d_kc, (void *)kv.second.direct.d_pm,
-                    (void *)kv.second.d_scale, (void *)kv.second.d_unscale})
-      if (q) (void)hipFree(q);
-    for (auto &m : kv.second.direct_padded)
-      for (void *q : {m.second.d_bfrag, (void *)m.second.d_lk, (void *)m.second.d_kc, (void *)m.second.d_pm})
-        if (q) (void)hipFree(q);
-  }
-  for (auto &kv : c->cache->decomps) { if (kv.second.d_bfrag) (void)hipFree(kv.second.d_bfrag); if (kv.second.d_pk) (void)hipFree(kv.second.d_pk); }
-  if (c->cache->d_error_table) (void)hipFree(c->cache->d_error_table);
-  delete c->cache;
-  c->cache = nullptr;
-}
-
 extern "C" int gpq_set_bridge_mfma(gpq_ctx *c, int on) {
   if (!c) return gpq_fail(GPQ_ERR_INVALID, "gpq_set_bridge_mfma: null context");
-  c->bridge_mfma = on != 0;
+  c->set.bridge_mfma = on != 0;
   return GPQ_OK;
 }
 
@@ -114,15 +76,14 @@ extern "C" int gpq_rns_reconstruct_one(gpq_ctx *c, uint64_t *words, unsigned Wou
   for (unsigned d = 0; d < dim; ++d)
     if (residues[d] >= c->p[d]) return gpq_fail(GPQ_ERR_INVALID, "gpq_rns_reconstruct_one: residue %u is not reduced", d);
   DeviceScope on_device(c->device);
-  uint64_t *dev = nullptr;
-  HIP_TRY(hipMalloc((void **)&dev, (size_t)(dim + Wout) * 8));
+  gpq_dev<uint64_t> dev;
+  HIP_TRY(dev.alloc((size_t)(dim + Wout) * 8));
   hipError_t e = hipMemcpy(dev, residues, (size_t)dim * 8, hipMemcpyHostToDevice);
   if (e == hipSuccess) {
     rc = launch_reconstruct(c, b, dev + dim, Wout, dev, dim, 0, 1, 0, false, nullptr, nullptr, 0);
     if (rc == GPQ_OK) rc = launched("gpq_rns_reconstruct_one");
     if (rc == GPQ_OK) e = hipMemcpy(words, dev + dim, (size_t)Wout * 8, hipMemcpyDeviceToHost);
   }
-  (void)hipFree(dev);
   if (e != hipSuccess) return gpq_fail(GPQ_ERR_HIP, "gpq_rns_reconstruct_one: %s", hipGetErrorString(e));
   return rc;
 }
@@ -288,21 +249,20 @@ static int he_mul_impl(gpq_ctx *c, uint64_t *out_c0, uint64_t *out_c1, const uin
       StageRange stage(square ? "gpq_he_mul: rns_decompose x2 (squaring)" : "gpq_he_mul: rns_decompose x4");
       const unsigned nin = square ? 2 : 4;                                                   // :117-120, one launch: h[0..3] are adjacent
       BigSources src{{in[0] + k0 * bigpoly, in[1] + k0 * bigpoly, in[square ? 0 : 2] + k0 * bigpoly, in[square ? 1 : 3] + k0 * bigpoly}, polys};
-      if ((rc = launch_decompose(c, h[0], src, W, 0, dimA, nin * polys, s, c->lazy_decompose && c->logn > 12))) return rc;
+      if ((rc = launch_decompose(c, h[0], src, W, 0, dimA, nin * polys, s, c->set.lazy_decompose && c->logn > 12))) return rc;
     }
     const bool pre = can_prescale(c);      // the inverse passes hand the CRT kernels limbs already multiplied by (P/p_d)^-1
     const LimbTab *tabsA = nullptr, *tabsP = nullptr;
     int tail_mode = 0;
     if (pre && ((rc = get_scaled_tabs(c, bA, &tabsA)) || (rc = tail_prescale_mode(c, dimP, dimB, &tabsP, &tail_mode)))) return rc;
-    {
-      ScaledInverse scaled(c, tabsA);
-      if ((rc = gpq_he_mul_tensor(c, d0h, d1h, d2h, h[0], h[1], square ? h[0] : h[2], square ? h[1] : h[3], dimA, polys, wsT, stream))) return rc;  // :121-136
-    }
+    apply_scaled_wide_limit(c, tabsA);
+    apply_scaled_wide_limit(c, tabsP);
+    if ((rc = gpq_he_mul_tensor_scaled(c, d0h, d1h, d2h, h[0], h[1], square ? h[0] : h[2], square ? h[1] : h[3], dimA, polys, wsT, stream, tabsA))) return rc;  // :121-136
     uint64_t *d0 = dbig, *d1 = dbig + polys * bigpoly, *d2 = dbig + 2 * polys * bigpoly;
     uint64_t *d2hat = sB, *c0hat = sB + pb, *c1hat = sB + 2 * pb;
     // With the one-product tail and bridge_stream.hpp, d0, d1, d2 (:139-141) never exist as words: d2hat goes CRT -> rns_decompose (:59) in
     // one kernel, d0hat | d1hat enter the tail as limbs.  Otherwise: poly_rns2mpi of the three adjacent slabs in one launch, rns_decompose of d2.
-    const bool limbs_addend = pre && tail_mode == 3 && c->stream_bridge;
+    const bool limbs_addend = pre && tail_mode == 3 && c->set.stream_bridge;
     bool fused = false;
     if (limbs_addend) {
       StageRange stage("gpq_he_mul: poly_rns2mpi d2 -> he_relin rns_decompose (one kernel)");
@@ -318,13 +278,10 @@ static int he_mul_impl(gpq_ctx *c, uint64_t *out_c0, uint64_t *out_c1, const uin
         if (rc) return rc;
       }
       StageRange stage("gpq_he_mul: he_relin rns_decompose d2");
-      if ((rc = launch_decompose(c, d2hat, d2, W, 0, dimB, polys, s, c->lazy_decompose && c->logn > 12))) return rc;          // :59
+      if ((rc = launch_decompose(c, d2hat, d2, W, 0, dimB, polys, s, c->set.lazy_decompose && c->logn > 12))) return rc;          // :59
     }
     // he_relin, :40-85
-    {
-      ScaledInverse scaled(c, tabsP);
-      if ((rc = gpq_keyswitch(c, c0hat, c1hat, d2hat, rlk0, rlk1, dimB, polys, wsK, stream))) return rc;           // :60-64
-    }
+    if ((rc = gpq_keyswitch_scaled(c, c0hat, c1hat, d2hat, rlk0, rlk1, dimB, polys, wsK, stream, tabsP))) return rc;   // :60-64
     StageRange stage("gpq_he_mul: he_relin tail (CRT, exact division by P, + d)");
     // c0 and c1 as one batch of 2 x polys polynomials: c0hat | c1hat and d0 | d1 are adjacent, the outputs are the caller's two slabs
     const TailD dh{d0h, bA, dimA, d0};
@@ -367,14 +324,12 @@ extern "C" int gpq_he_swk(gpq_ctx *c, uint64_t *out_c0, uint64_t *out_c1, const 
     int rc;
     const size_t pb = (size_t)polys * dimB * n;
     uint64_t *d1hat = sB, *c0hat = sB + pb, *c1hat = sB + 2 * pb;
-    if ((rc = launch_decompose(c, d1hat, d1 + k0 * bigpoly, W, 0, dimB, polys, s, c->lazy_decompose && c->logn > 12))) return rc;   // :60
+    if ((rc = launch_decompose(c, d1hat, d1 + k0 * bigpoly, W, 0, dimB, polys, s, c->set.lazy_decompose && c->logn > 12))) return rc;   // :60
     const LimbTab *tabsP = nullptr;
     int tail_mode = 0;
     if ((rc = tail_prescale_mode(c, dimP, dimB, &tabsP, &tail_mode))) return rc;
-    {
-      ScaledInverse scaled(c, tabsP);
-      if ((rc = gpq_keyswitch(c, c0hat, c1hat, d1hat, swk0, swk1, dimB, polys, wsK, stream))) return rc;           // :61-65
-    }
+    apply_scaled_wide_limit(c, tabsP);
+    if ((rc = gpq_keyswitch_scaled(c, c0hat, c1hat, d1hat, swk0, swk1, dimB, polys, wsK, stream, tabsP))) return rc;   // :61-65
     // c0 (+ d0) and c1 (no addend) as one batch of 2 x polys polynomials                                           // :68-75
     if ((rc = relin_tail(c, Two<uint64_t>{out_c0 + k0 * bigpoly, out_c1 + k0 * bigpoly, polys}, c0hat, Two<const uint64_t>{d0 + k0 * bigpoly, nullptr, polys},
                          W, dimP, dimB, logql, 2 * polys, wsTail, s, tail_mode))) return rc;
@@ -426,7 +381,7 @@ int hoist_plan(gpq_ctx *c, unsigned W, unsigned dimB, unsigned dimP, unsigned nr
 extern "C" size_t gpq_he_rot_hoisted_workspace_bytes(gpq_ctx *c, unsigned W, unsigned dimB, unsigned dimP, unsigned nrot, unsigned batch) {
   if (!c || !nrot || !batch) return 0;
   HoistPlan h;
-  return hoist_plan(c, W, dimB, dimP, nrot, batch < c->chunk ? batch : c->chunk, &h) == GPQ_OK ? h.total : 0;
+  return hoist_plan(c, W, dimB, dimP, nrot, batch < c->set.chunk ? batch : c->set.chunk, &h) == GPQ_OK ? h.total : 0;
 }
 
 extern "C" int gpq_he_rot_hoisted(gpq_ctx *c, uint64_t *out_c0, uint64_t *out_c1, const uint64_t *c0, const uint64_t *c1,
@@ -447,7 +402,7 @@ extern "C" int gpq_he_rot_hoisted(gpq_ctx *c, uint64_t *out_c0, uint64_t *out_c1
         overlap(out_c1, out_words, c0, in_words) || overlap(out_c1, out_words, c1, in_words))
       return gpq_fail(GPQ_ERR_INVALID, "gpq_he_rot_hoisted: the outputs alias each other or an input");
   }
-  const unsigned m = batch < c->chunk ? batch : c->chunk;
+  const unsigned m = batch < c->set.chunk ? batch : c->set.chunk;
   HoistPlan hp;
   if ((rc = hoist_plan(c, W, dimB, dimP, nrot, m, &hp))) return rc;
   char *w = (char *)workspace;
@@ -469,6 +424,7 @@ extern "C" int gpq_he_rot_hoisted(gpq_ctx *c, uint64_t *out_c0, uint64_t *out_c1
   const LimbTab *tabsP = nullptr;
   int tail_mode = 0;
   if ((rc = tail_prescale_mode(c, dimP, dimB, &tabsP, &tail_mode))) return rc;
+  apply_scaled_wide_limit(c, tabsP);
   const uint64_t mask2n = 2 * (uint64_t)n - 1;
   for (unsigned k0 = 0; k0 < batch; k0 += m) {
     const unsigned polys = batch - k0 < m ? batch - k0 : m;
@@ -482,10 +438,7 @@ extern "C" int gpq_he_rot_hoisted(gpq_ctx *c, uint64_t *out_c0, uint64_t *out_c1
       StageRange stage("gpq_he_rot_hoisted: one rotation (permuted key switch + tail)");
       const unsigned g = (unsigned)(rot_power(rots[r]) & mask2n);
       if ((rc = gpq_poly_rot(c, d0, c0 + k0 * bigpoly, W, rots[r], polys, stream))) return rc;            // :108 (c1's is in the index map)
-      {
-        ScaledInverse scaled(c, tabsP);
-        if ((rc = gpq_keyswitch_rotated(c, chat, chat + pb, X, rk0[r], rk1[r], dimB, polys, g, wsK, s))) return rc;   // :61-65
-      }
+      if ((rc = gpq_keyswitch_rotated(c, chat, chat + pb, X, rk0[r], rk1[r], dimB, polys, g, wsK, s, tabsP))) return rc;   // :61-65
       const size_t o = ((size_t)r * batch + k0) * bigpoly;
       if ((rc = relin_tail(c, Two<uint64_t>{out_c0 + o, out_c1 + o, polys}, chat, Two<const uint64_t>{d0, nullptr, polys},
                            W, dimP, dimB, logql, 2 * polys, wsTail, s, tail_mode))) return rc;                // :68-75
@@ -637,7 +590,7 @@ extern "C" int gpq_relin_tail_overwriting(gpq_ctx *c, uint64_t *out, uint64_t *c
 // bit-identical (tests run both).
 extern "C" int gpq_set_fused_tail(gpq_ctx *c, int on) {
   if (!c) return gpq_fail(GPQ_ERR_INVALID, "gpq_set_fused_tail: null context");
-  c->fuse_tail = on != 0;
+  c->set.fuse_tail = on != 0;
   return GPQ_OK;
 }
 
@@ -645,9 +598,9 @@ extern "C" int gpq_set_fused_tail(gpq_ctx *c, int on) {
 // CRT kernels do that multiplication themselves.  Same results (tests run both).
 extern "C" int gpq_set_prescale(gpq_ctx *c, int on) {      // 0: off, 1: the CRT weights only, 2: also w_j on the limbs above P for the relinearisation front, 3 (default): the one-product tail
   if (!c) return gpq_fail(GPQ_ERR_INVALID, "gpq_set_prescale: null context");
-  c->prescale = on != 0;
-  c->prescale_upper = on >= 2;
-  c->tail_direct = on >= 3;
+  c->set.prescale = on != 0;
+  c->set.prescale_upper = on >= 2;
+  c->set.tail_direct = on >= 3;
   return GPQ_OK;
 }
 
@@ -655,7 +608,7 @@ extern "C" int gpq_set_prescale(gpq_ctx *c, int on) {      // 0: off, 1: the CRT
 // Same words either way (tests run both).
 extern "C" int gpq_set_stream_bridge(gpq_ctx *c, int on) {
   if (!c) return gpq_fail(GPQ_ERR_INVALID, "gpq_set_stream_bridge: null context");
-  c->stream_bridge = on != 0;
+  c->set.stream_bridge = on != 0;
   return GPQ_OK;
 }
 
@@ -679,27 +632,27 @@ extern "C" unsigned gpq_last_lanes(const gpq_ctx *c) { return c ? c->last_lanes 
 // (default on; canonical with 0).  Same results: the transforms reduce lazily anyway.
 extern "C" int gpq_set_lazy_decompose(gpq_ctx *c, int on) {
   if (!c) return gpq_fail(GPQ_ERR_INVALID, "gpq_set_lazy_decompose: null context");
-  c->lazy_decompose = on != 0;
+  c->set.lazy_decompose = on != 0;
   return GPQ_OK;
 }
 
 // Tests: bridge_stream.hpp's kernels also hand every coefficient whose index is a multiple of `every` to the exact kernels behind them (0: off).
 extern "C" int gpq_debug_force_redo(gpq_ctx *c, unsigned every) {
   if (!c) return gpq_fail(GPQ_ERR_INVALID, "gpq_debug_force_redo: null context");
-  c->debug_force_redo = every;
+  c->set.debug_force_redo = every;
   return GPQ_OK;
 }
 
 // Tests: force the exact (full-width) CRT kernel instead of the low-word fast path.
 extern "C" int gpq_set_exact_crt(gpq_ctx *c, int on) {
   if (!c) return gpq_fail(GPQ_ERR_INVALID, "gpq_set_exact_crt: null context");
-  c->exact_crt = on != 0;
+  c->set.exact_crt = on != 0;
   return GPQ_OK;
 }
 
 // Diagnostics: how many of the first `count` coefficients the last fast CRT pass flagged for the exact kernel.
 extern "C" long gpq_debug_redo_count(gpq_ctx *c, size_t count) {
-  if (!c || !c->d_redo || count > c->redo_cap) return -1;
+  if (!c || !c->d_redo || count > c->d_redo.bytes) return -1;
   std::vector<unsigned char> h(count);
   if (hipMemcpy(h.data(), c->d_redo, count, hipMemcpyDeviceToHost) != hipSuccess) return -2;
   long k = 0;

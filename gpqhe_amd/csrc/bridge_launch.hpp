@@ -54,19 +54,8 @@ struct ReconExtra {
 
 // per-coefficient "redo exactly" flags of the fast CRT paths
 int ensure_redo(gpq_ctx *c, size_t flags, hipStream_t s) {
-  if (flags <= c->redo_cap) return GPQ_OK;
-  // Growing inside a stream capture would put hipMalloc into the graph; and a graph captured earlier keeps the old
-  // pointer, so outgrown buffers are retired (freed with the context), never freed here.
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
-    return gpq_fail(GPQ_ERR_INVALID, "the first call at a new batch size allocates scratch: run it once outside stream capture");
-  DeviceScope on_device(c->device);
-  unsigned char *grown = nullptr;
-  HIP_TRY(hipMalloc((void **)&grown, flags));
-  if (c->d_redo) c->retired.push_back(c->d_redo);
-  c->d_redo = grown;
-  c->redo_cap = flags;
-  return GPQ_OK;
+  if (flags <= c->d_redo.bytes) return GPQ_OK;
+  return c->d_redo.grow(c, s, flags, false, "the first call at a new batch size allocates scratch: run it once outside stream capture");
 }
 
 // arguments of the exact kernel bridge_reconstruct<b->WP> for one call (launch_reconstruct, and the fused fallback kernels behind bridge_stream.hpp)
@@ -86,13 +75,13 @@ int launch_reconstruct(gpq_ctx *c, const gpq_bridge_basis *b, uint64_t *big, uns
   // fast path: centred result modulo a power of two that needs fewer words than P has
   const unsigned need = (logq + 63) / 64;
   // (the centring threshold floor(P/2)/P differs from 1/2 by 1/(2P): negligible against the 2^-61 slack only for large P)
-  const bool fast = logq && centre && !c->exact_crt && need + 1 < (unsigned)b->WP && need <= 16 && b->pbits >= 160;
+  const bool fast = logq && centre && !c->set.exact_crt && need + 1 < (unsigned)b->WP && need <= 16 && b->pbits >= 160;
   if (fast && !x.exact_only) {
     if (int rc = ensure_redo(c, (size_t)batch << logn, s)) return rc;
     ProfScope prof(c, GPQ_K_RECONSTRUCT, s);
     const int WL = recon_wl(need);
     bool done = false;
-    if (c->bridge_mfma && logn >= 6 && b->dim >= 4) {      // CRT sum as bytes x constant matrix on the matrix cores
+    if (c->set.bridge_mfma && logn >= 6 && b->dim >= 4) {      // CRT sum as bytes x constant matrix on the matrix cores
       gpq_recon_mfma *t;
       int rc = get_recon_mfma(c, const_cast<gpq_bridge_basis *>(b), WL, &t);
       if (rc) return rc;
@@ -150,7 +139,7 @@ int launch_decompose_valu(const DecomposeArgs &a, unsigned W, dim3 grid, hipStre
 // (0, 3p) (matrix-core kernel only; for slabs that go straight into a two-pass forward transform: gpq_he_mul's own decompositions)
 int launch_decompose(gpq_ctx *c, uint64_t *slab, const BigSources &big, unsigned W, unsigned limb0, unsigned dim, unsigned batch, hipStream_t s, bool lazy = false) {
   ProfScope prof(c, GPQ_K_DECOMPOSE, s);
-  if (c->bridge_mfma && c->logn >= 6 && W <= 32 && dim >= 4) {
+  if (c->set.bridge_mfma && c->logn >= 6 && W <= 32 && dim >= 4) {
     gpq_decomp_mfma *t;
     int rc = get_decomp_mfma(c, limb0, dim, W, &t);
     if (rc) return rc;
@@ -184,15 +173,8 @@ constexpr size_t kStreamLdsMax = 156 * 1024;
 
 int ensure_wave_any(gpq_ctx *c, hipStream_t s) {
   if (c->d_wave_any) return GPQ_OK;
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
-    return gpq_fail(GPQ_ERR_INVALID, "the first call allocates scratch: run it once outside stream capture");
-  DeviceScope on_device(c->device);
-  HIP_TRY(hipMalloc((void **)&c->d_wave_any, kStreamBlocks * kStreamWaves * sizeof(unsigned)));
-  // on the LAUNCH stream: a plain hipMemset goes to the null stream, which a non-blocking stream (torch's side streams, the peer lane's) does not
-  // wait for -- the producer kernel's flag words could be zeroed after it wrote them (tests/test_stream_bridge_gpu.py: a fresh peer lane)
-  HIP_TRY(hipMemsetAsync(c->d_wave_any, 0, kStreamBlocks * kStreamWaves * sizeof(unsigned), s));
-  return GPQ_OK;
+  // (zeroed on the launch stream: tests/test_stream_bridge_gpu.py, a fresh peer lane)
+  return c->d_wave_any.grow(c, s, kStreamBlocks * kStreamWaves * sizeof(unsigned), true, "the first call allocates scratch: run it once outside stream capture");
 }
 inline unsigned stream_blocks(unsigned total_groups) {
   const unsigned need = (total_groups + kStreamWaves - 1) / kStreamWaves;
@@ -200,7 +182,7 @@ inline unsigned stream_blocks(unsigned total_groups) {
 }
 inline bool stream_fast_ok(const gpq_ctx *c, const gpq_bridge_basis *b, unsigned logq) {   // launch_reconstruct's conditions for the fast CRT path
   const unsigned need = (logq + 63) / 64;
-  return logq && !c->exact_crt && c->bridge_mfma && c->logn >= 6 && b->dim >= 4 && need + 1 < (unsigned)b->WP && b->pbits >= 160;
+  return logq && !c->set.exact_crt && c->set.bridge_mfma && c->logn >= 6 && b->dim >= 4 && need + 1 < (unsigned)b->WP && b->pbits >= 160;
 }
 
 template <int WL, int KS, int KSD, int R>
@@ -214,7 +196,7 @@ int crt_decompose_stream(gpq_ctx *c, gpq_bridge_basis *bA, uint64_t *out, const 
                          unsigned dimB, unsigned logq, unsigned polys, hipStream_t s, bool *done) {
   *done = false;
   const unsigned need = (logq + 63) / 64;
-  if (!c->stream_bridge || !stream_fast_ok(c, bA, logq) || W < need || dimB < 4) return GPQ_OK;
+  if (!c->set.stream_bridge || !stream_fast_ok(c, bA, logq) || W < need || dimB < 4) return GPQ_OK;
   int WL, KS, KSD;
   if (W <= 7 && dimA <= 16) { WL = 7; KS = 4; KSD = 2; }
   else if (W <= 14 && dimA <= 32) { WL = 14; KS = 8; KSD = 4; }
@@ -232,7 +214,7 @@ int crt_decompose_stream(gpq_ctx *c, gpq_bridge_basis *bA, uint64_t *out, const 
   const size_t slab_bytes = ((size_t)polys * dimA << c->logn) * 8;
   if (slab_bytes >= 0xfffff000ull) return GPQ_OK;
   CrtDecomposeArgs a{slab, slab_bytes, out, (const v4i *)tr->d_bfrag, tr->d_kc, tr->d_pm, (const v4i *)td->d_bfrag, td->d_pk, c->d_redo, c->d_wave_any,
-                     dimA, dimB, td->NT, c->logn, logq, W, groups, dimB, c->debug_force_redo, (c->lazy_decompose && c->logn > 12) ? 1u : 0u};
+                     dimA, dimB, td->NT, c->logn, logq, W, groups, dimB, c->set.debug_force_redo, (c->set.lazy_decompose && c->logn > 12) ? 1u : 0u};
   {
     ProfScope prof(c, GPQ_K_CRT_DECOMPOSE, s);
     if (WL == 7) rc = launch_crt_decompose_t<7, 4, 2, 4>(a, lds, blocks, s);

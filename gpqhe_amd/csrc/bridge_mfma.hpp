@@ -441,7 +441,7 @@ struct RelinFrontArgs {
   // are left alone -- the re-run behind bridge_relin_tail_mfma, which needs yq in memory for the few coefficients it could not finish
   const unsigned char *only;
   unsigned only_writes_flags;   // with `only`: write flags / amb for the groups it re-runs after all (behind the one-product tail nothing else has)
-  unsigned prescaled;        // the limbs below dimP already hold y_d = chat_d * phat_invmp_d (the key switch's inverse pass scaled them: ScaledInverse)
+  unsigned prescaled;        // the limbs below dimP already hold y_d = chat_d * phat_invmp_d (the key switch's inverse pass scaled them: gpq_keyswitch_scaled)
   unsigned wscaled;          // ... and the limbs above hold chat_j * w_j, bfrag / pk / tkp are the w-scaled tables: yq_j = x'_j - (r w_j mod p_j)
   FlagScope scope;           // with `only`: the launch that wrote it (bridge_stream.hpp); the grid is then scope.waves / 4 workgroups, so that
                              // wave w of this launch walks the groups of the producer's wave w

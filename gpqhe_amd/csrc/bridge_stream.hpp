@@ -413,7 +413,7 @@ __global__ __launch_bounds__(512) void bridge_crt_decompose(CrtDecomposeArgs a) 
 //   out = smod(floor(x/P) + round + d, 2^logq)
 // ---------------------------------------------------------------------------
 struct TailStreamArgs {
-  const uint64_t *chat;      // [polys][dimB][n]   limbs weighted for the CRT over all dimB limbs (ScaledInverse, get_tail_direct)
+  const uint64_t *chat;      // [polys][dimB][n]   limbs weighted for the CRT over all dimB limbs (get_scaled_tabs via get_tail_direct)
   const uint64_t *dhat;      // DCRT: [polys][dimA][n] limbs of d weighted for the CRT over dimA limbs
   size_t chat_bytes, dhat_bytes;   // (< 4 GB each: the host checks)
   Two<const uint64_t> addend;// !DCRT: [polys][W][n] or null places

@@ -30,14 +30,6 @@ void put(std::vector<uint64_t> &dst, size_t off, const Big &v, size_t words) {
   for (size_t j = 0; j < words; ++j) dst[off + j] = j < v.size() ? v[j] : 0;
 }
 
-// a host vector as a read-only device table of the context (on the current device; the copy is synchronous)
-template <typename P, typename T>
-int upload_table(gpq_ctx *c, P **dst, const std::vector<T> &v) {
-  HIP_TRY(gpq_table_malloc(c, (void **)dst, v.size() * sizeof(T)));
-  HIP_TRY(hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-  return GPQ_OK;
-}
-
 const int kWP[] = {8, 16, 32, 48, 56};
 
 // ---- host big integers for the general-modulus path (sizes of a few thousand bits) ----
@@ -98,14 +90,13 @@ int get_basis(gpq_ctx *c, unsigned first, unsigned dim, gpq_bridge_basis **out) 
     const u128h q = ~(u128h)0 / c->p[first + d];                     // floor(2^128 / p_d): p_d does not divide 2^128
     inv128[2 * d] = (uint64_t)q; inv128[2 * d + 1] = (uint64_t)(q >> 64);
   }
-  DeviceScope on_device(c->device);
   int rc;
-  if ((rc = upload_table(c, &b.d_phat, phat)) || (rc = upload_table(c, &b.d_phat_inv, pinv)) || (rc = upload_table(c, &b.d_pmult, pmult)) ||
-      (rc = upload_table(c, &b.d_phalf, phalf)) || (rc = upload_table(c, &b.d_inv128, inv128))) return rc;
+  if ((rc = b.d_phat.upload(c, phat)) || (rc = b.d_phat_inv.upload(c, pinv)) || (rc = b.d_pmult.upload(c, pmult)) ||
+      (rc = b.d_phalf.upload(c, phalf)) || (rc = b.d_inv128.upload(c, inv128))) return rc;
   b.h_phat_inv = pinv;
   b.h_P = P;
   b.h_phat = phat;
-  *out = &(c->cache->bases[key] = b);
+  *out = &c->cache->bases.emplace(key, std::move(b)).first->second;
   return GPQ_OK;
 }
 
@@ -119,8 +110,8 @@ int get_relin(gpq_ctx *c, unsigned dimP, unsigned dimB, gpq_relin_tables **out) 
   std::vector<uint64_t> pinv(dimB - dimP);
   for (unsigned d = dimP; d < dimB; ++d) pinv[d - dimP] = powm(mod_small(bp->h_P, c->p[d]), c->p[d] - 2, c->p[d]);
   gpq_relin_tables t;
-  if ((rc = upload_table(c, &t.d_pinv, pinv))) return rc;
-  *out = &(c->cache->relins[key] = t);
+  if ((rc = t.d_pinv.upload(c, pinv))) return rc;
+  *out = &c->cache->relins.emplace(key, std::move(t)).first->second;
   return GPQ_OK;
 }
 
@@ -137,7 +128,7 @@ static unsigned first_unfit_wide_limb(const gpq_ctx *c, const std::vector<LimbTa
 }
 int get_scaled_tabs(gpq_ctx *c, gpq_bridge_basis *b, const LimbTab **out) {
   if (!b->d_tabs_scaled) {
-    std::vector<LimbTab> t = c->h_tabs;
+    std::vector<LimbTab> t = c->cache->h_tabs;
     for (unsigned d = 0; d < b->dim; ++d) {
       LimbTab &e = t[b->first + d];
       const uint64_t p = e.k.p, s = b->h_phat_inv[d];
@@ -146,30 +137,23 @@ int get_scaled_tabs(gpq_ctx *c, gpq_bridge_basis *b, const LimbTab **out) {
       if (b->first + d < c->nsplit_tables) { e.ninv_s = split_pair_of(e.ninv, p); e.winv1_ninv_s = split_pair_of(e.winv1_ninv, p); }
     }
     const unsigned unfit = first_unfit_wide_limb(c, t, b->first, b->dim);
-    DeviceScope on_device(c->device);
-    if (int rc = upload_table(c, &b->d_tabs_scaled, t)) return rc;
+    if (int rc = b->d_tabs_scaled.upload(c, t)) return rc;
     if (unfit != ~0u) c->cache->scaled_wide_limit[b->d_tabs_scaled] = unfit;
   }
   *out = b->d_tabs_scaled;
   return GPQ_OK;
 }
-// Makes the inverse strided pass read such a table for the duration of one gpq_he_mul_tensor / gpq_keyswitch call.  A table with a pair that does not fit the wide class ends the context's
-// wide range at that limb, for good (the calls between which this happens hand over canonical residues: any class reads them).
-struct ScaledInverse {
-  gpq_ctx *c;
-  ScaledInverse(gpq_ctx *ctx, const LimbTab *tabs) : c(ctx) {
-    c->inv_tabs_override = tabs;
-    if (tabs && c->cache && !c->cache->scaled_wide_limit.empty()) {
-      const auto it = c->cache->scaled_wide_limit.find(tabs);
-      if (it != c->cache->scaled_wide_limit.end()) {
-        if (c->nwide_max > it->second) c->nwide_max = it->second;
-        if (c->nwide > it->second) c->nwide = it->second;
-      }
-    }
-  }
-  ~ScaledInverse() { c->inv_tabs_override = nullptr; }
-};
-inline bool can_prescale(const gpq_ctx *c) { return c->prescale && c->logn > 12 && !c->h_tabs.empty(); }   // the two-pass transforms only (small rings: gpq_invntt)
+// A context that is about to hand such a table to an inverse pass (gpq_he_mul_tensor_scaled / gpq_keyswitch_scaled / gpq_keyswitch_rotated): a table
+// with a pair that does not fit the wide class ends the context's wide range at that limb, FOR GOOD (the calls between which this happens hand
+// over canonical residues: any class reads them).  Called where the table is chosen, by the callers of get_scaled_tabs / tail_prescale_mode.
+void apply_scaled_wide_limit(gpq_ctx *c, const LimbTab *tabs) {
+  if (!tabs || c->cache->scaled_wide_limit.empty()) return;
+  const auto it = c->cache->scaled_wide_limit.find(tabs);
+  if (it == c->cache->scaled_wide_limit.end()) return;
+  if (c->nwide_max > it->second) c->nwide_max = it->second;
+  if (c->set.nwide > it->second) c->set.nwide = it->second;
+}
+inline bool can_prescale(const gpq_ctx *c) { return c->set.prescale && c->logn > 12 && !c->cache->h_tabs.empty(); }   // the two-pass transforms only (small rings: gpq_invntt)
 
 // balanced base-256 digits of a little-endian multiword value, `nd` digits (the final carry is dropped: mod 256^nd)
 void balanced_digits(const uint64_t *words, size_t nwords, int8_t *out, size_t nd) {
@@ -246,9 +230,8 @@ int build_recon_mfma(gpq_ctx *c, const std::vector<uint64_t> &primes, const std:
       }
       mP = nxt;
     }
-    DeviceScope on_device(c->device);
     int rc;
-    if ((rc = upload_table(c, &t.d_bfrag, bf)) || (rc = upload_table(c, &t.d_lk, lk)) || (rc = upload_table(c, &t.d_kc, kc)) || (rc = upload_table(c, &t.d_pm, pm))) return rc;
+    if ((rc = t.d_bfrag.upload(c, bf)) || (rc = t.d_lk.upload(c, lk)) || (rc = t.d_kc.upload(c, kc)) || (rc = t.d_pm.upload(c, pm))) { t = gpq_recon_mfma(); return rc; }
   }
   return GPQ_OK;
 }
@@ -266,7 +249,7 @@ int get_recon_mfma(gpq_ctx *c, gpq_bridge_basis *b, int WL, gpq_recon_mfma **out
     weight[d].assign(b->h_phat.begin() + (size_t)d * b->WP, b->h_phat.begin() + (size_t)(d + 1) * b->WP);
   }
   if (int rc = build_recon_mfma(c, primes, b->h_phat_inv, weight, b->h_P, WL, &t, KSpad)) return rc;
-  *out = &(b->mfma[key] = t);
+  *out = &b->mfma.emplace(key, std::move(t)).first->second;
   return GPQ_OK;
 }
 
@@ -291,7 +274,7 @@ int get_addend_rows(gpq_ctx *c, gpq_bridge_basis *b, unsigned KSpad, gpq_recon_m
   }
   gpq_recon_mfma t;
   if (int rc = build_recon_mfma(c, primes, b->h_phat_inv, weight, shifted(b->h_P), 16, &t, KSpad, 144)) return rc;
-  *out = &(b->mfma[key] = t);
+  *out = &b->mfma.emplace(key, std::move(t)).first->second;
   return GPQ_OK;
 }
 
@@ -342,11 +325,10 @@ int get_decomp_mfma(gpq_ctx *c, unsigned limb0, unsigned dim, unsigned W, gpq_de
         }
       }
     }
-    DeviceScope on_device(c->device);
     int rc;
-    if ((rc = upload_table(c, &t.d_bfrag, bf)) || (rc = upload_table(c, &t.d_pk, pk))) return rc;
+    if ((rc = t.d_bfrag.upload(c, bf)) || (rc = t.d_pk.upload(c, pk))) return rc;
   }
-  *out = &(c->cache->decomps[key] = t);
+  *out = &c->cache->decomps.emplace(key, std::move(t)).first->second;
   return GPQ_OK;
 }
 
@@ -362,7 +344,7 @@ int get_relin_front(gpq_ctx *c, unsigned dimP, unsigned dimB, gpq_relin_tables *
   std::vector<int8_t> bf((size_t)NT * KS * 1024, 0);
   std::vector<uint64_t> lk((size_t)8 * KS, 0), pk((size_t)12 * NTp, 0), tkp((size_t)cnt * 64, 0), kf(2, 0);
   // The same tables with every constant of limb j multiplied by w_j = P^-1 (Pi'/p_j)^-1 mod p_j: with the limbs above P arriving
-  // already multiplied by w_j (ScaledInverse on the key switch's inverse pass) Q's scaled residue is x'_j - (r w_j mod p_j), a
+  // already multiplied by w_j (the key switch's inverse pass reads d_tabs_w) Q's scaled residue is x'_j - (r w_j mod p_j), a
   // subtraction where the plain tables need a modular multiplication per (coefficient, limb).
   std::vector<int8_t> bfw;
   std::vector<uint64_t> pkw((size_t)12 * NTp, 0), tkpw((size_t)cnt * 64, 0), wscale(cnt, 1);
@@ -418,7 +400,7 @@ int get_relin_front(gpq_ctx *c, unsigned dimP, unsigned dimB, gpq_relin_tables *
     }
   }
   // the context's per-limb table for the key switch's inverse pass: (P/p_d)^-1 on the limbs of P, w_j above
-  std::vector<LimbTab> tw = c->h_tabs;
+  std::vector<LimbTab> tw = c->cache->h_tabs;
   if (!tw.empty()) {
     for (unsigned d = 0; d < dimB; ++d) {
       LimbTab &e = tw[d];
@@ -428,13 +410,14 @@ int get_relin_front(gpq_ctx *c, unsigned dimP, unsigned dimB, gpq_relin_tables *
       if (d < c->nsplit_tables) { e.ninv_s = split_pair_of(e.ninv, p); e.winv1_ninv_s = split_pair_of(e.winv1_ninv, p); }
     }
   }
-  DeviceScope on_device(c->device);
+  // (in place: rt is the cache's entry.  d_bfrag and d_tabs_w are what the callers test, so a build that fails half way takes them back:
+  // the tables count as absent, what was uploaded stays owned and accounted)
   int rc;
-  if ((rc = upload_table(c, &rt->d_bfrag, bf)) || (rc = upload_table(c, &rt->d_lk, lk)) || (rc = upload_table(c, &rt->d_pk, pk)) ||
-      (rc = upload_table(c, &rt->d_tkp, tkp)) || (rc = upload_table(c, &rt->d_kf, kf))) return rc;
+  if ((rc = rt->d_lk.upload(c, lk)) || (rc = rt->d_pk.upload(c, pk)) || (rc = rt->d_tkp.upload(c, tkp)) || (rc = rt->d_kf.upload(c, kf)) ||
+      (rc = rt->d_bfrag.upload(c, bf))) { rt->d_bfrag.reset(); return rc; }
   if (!tw.empty()) {
-    if ((rc = upload_table(c, &rt->d_bfrag_w, bfw)) || (rc = upload_table(c, &rt->d_pk_w, pkw)) || (rc = upload_table(c, &rt->d_tkp_w, tkpw)) ||
-        (rc = upload_table(c, &rt->d_tabs_w, tw))) return rc;
+    if ((rc = rt->d_bfrag_w.upload(c, bfw)) || (rc = rt->d_pk_w.upload(c, pkw)) || (rc = rt->d_tkp_w.upload(c, tkpw)) ||
+        (rc = rt->d_tabs_w.upload(c, tw))) { rt->d_bfrag.reset(); rt->d_tabs_w.reset(); return rc; }
     const unsigned unfit = first_unfit_wide_limb(c, tw, 0, dimB);
     if (unfit != ~0u) c->cache->scaled_wide_limit[rt->d_tabs_w] = unfit;
   }
@@ -466,7 +449,7 @@ int build_tail_direct(gpq_ctx *c, unsigned dimP, unsigned dimB, unsigned KSpad, 
 // exact integers for the limbs above P (p_j divides Pi'), floors for the limbs of P -- an underestimate by less than dimP 2^60 units of
 // 2^-104.  The low 104 bits of the 16-word sum are the fraction (x mod P)/P that mpi_rdiv rounds on, the bits above floor(x/P); kappa
 // (the multiples of Pi_B the centring of x takes off) comes from the same F columns as in any CRT.  Also: the per-limb table that makes
-// the key switch's inverse pass deliver y_d (ScaledInverse), and the weights Pi_B/p_d mod p_d that take the scaling off again
+// the key switch's inverse pass deliver y_d (gpq_keyswitch_scaled), and the weights Pi_B/p_d mod p_d that take the scaling off again
 // (bridge_limb_scale) for the few groups the exact kernels re-run.
 int get_tail_direct(gpq_ctx *c, unsigned dimP, unsigned dimB, gpq_relin_tables *rt) {
   if (rt->direct_tried) return GPQ_OK;
@@ -474,7 +457,7 @@ int get_tail_direct(gpq_ctx *c, unsigned dimP, unsigned dimB, gpq_relin_tables *
   gpq_bridge_basis *bB;
   int rc;
   if (dimB > 60 || dimB - dimP < 4) return GPQ_OK;
-  if ((rc = get_basis(c, 0, dimB, &bB)) || c->h_tabs.empty()) return rc;
+  if ((rc = get_basis(c, 0, dimB, &bB)) || c->cache->h_tabs.empty()) return rc;
   if ((rc = build_tail_direct(c, dimP, dimB, 0, &rt->direct)) || !rt->direct.d_bfrag) return rc;
   std::vector<uint64_t> unscale(dimB);
   for (unsigned d = 0; d < dimB; ++d) {
@@ -482,11 +465,10 @@ int get_tail_direct(gpq_ctx *c, unsigned dimP, unsigned dimB, gpq_relin_tables *
     unscale[d] = mod_small(ph, c->p[d]);                    // Pi_B/p_d mod p_d
   }
   const LimbTab *tabs;
-  if ((rc = get_scaled_tabs(c, bB, &tabs))) return rc;
+  if ((rc = get_scaled_tabs(c, bB, &tabs)) || (rc = rt->d_scale.upload(c, bB->h_phat_inv)) ||   // (Pi_B/p_d)^-1 mod p_d
+      (rc = rt->d_unscale.upload(c, unscale))) { rt->direct = gpq_recon_mfma(); return rc; }   // (in place too: no half-built one-product tail)
   rt->d_tabs_direct = tabs;
-  DeviceScope on_device(c->device);
-  if ((rc = upload_table(c, &rt->d_scale, bB->h_phat_inv))) return rc;         // (Pi_B/p_d)^-1 mod p_d
-  return upload_table(c, &rt->d_unscale, unscale);
+  return GPQ_OK;
 }
 
 // get_tail_direct's matrix zero-padded to KST k steps
@@ -496,7 +478,7 @@ int get_tail_direct_padded(gpq_ctx *c, unsigned dimP, unsigned dimB, gpq_relin_t
   if (it != rt->direct_padded.end()) { *out = &it->second; return GPQ_OK; }
   gpq_recon_mfma t;
   if (int rc = build_tail_direct(c, dimP, dimB, KST, &t)) return rc;
-  *out = &(rt->direct_padded[KST] = t);
+  *out = &rt->direct_padded.emplace(KST, std::move(t)).first->second;
   return GPQ_OK;
 }
 

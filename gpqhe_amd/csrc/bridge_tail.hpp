@@ -21,7 +21,7 @@ int tail_plan(gpq_ctx *c, unsigned W, unsigned dimP, unsigned dimB, unsigned pol
 // matrix are there (built on first use).  Asked by tail_prescale_mode, gpq_relin_tail_overwriting and relin_tail; what else each needs stands at the call.
 int tail_product_tables(gpq_ctx *c, unsigned dimP, unsigned dimB, gpq_relin_tables *rt, gpq_bridge_basis *bp, gpq_bridge_basis *bq, bool *ok) {
   *ok = false;
-  if (!c->bridge_mfma || c->logn < 6 || !c->tail_direct || c->exact_crt) return GPQ_OK;
+  if (!c->set.bridge_mfma || c->logn < 6 || !c->set.tail_direct || c->set.exact_crt) return GPQ_OK;
   int rc;
   if ((rc = get_relin_front(c, dimP, dimB, rt, bp, bq)) || (rt->d_bfrag && (rc = get_tail_direct(c, dimP, dimB, rt)))) return rc;
   *ok = rt->d_bfrag && rt->direct.d_bfrag;
@@ -38,11 +38,11 @@ int tail_prescale_mode(gpq_ctx *c, unsigned dimP, unsigned dimB, const LimbTab *
   gpq_relin_tables *rt;
   int rc;
   if ((rc = get_basis(c, 0, dimP, &bp)) || (rc = get_basis(c, dimP, dimB - dimP, &bq)) || (rc = get_relin(c, dimP, dimB, &rt))) return rc;
-  if (c->bridge_mfma && c->logn >= 6 && (rc = get_relin_front(c, dimP, dimB, rt, bp, bq))) return rc;
+  if (c->set.bridge_mfma && c->logn >= 6 && (rc = get_relin_front(c, dimP, dimB, rt, bp, bq))) return rc;
   bool product = false;
-  if (!c->fuse_tail && (rc = tail_product_tables(c, dimP, dimB, rt, bp, bq, &product))) return rc;
+  if (!c->set.fuse_tail && (rc = tail_product_tables(c, dimP, dimB, rt, bp, bq, &product))) return rc;
   if (product && rt->d_tabs_direct) { *tabs = rt->d_tabs_direct; *mode = 3; return GPQ_OK; }
-  if (c->bridge_mfma && c->logn >= 6 && rt->d_bfrag && rt->d_tabs_w && c->prescale_upper) { *tabs = rt->d_tabs_w; *mode = 2; return GPQ_OK; }
+  if (c->set.bridge_mfma && c->logn >= 6 && rt->d_bfrag && rt->d_tabs_w && c->set.prescale_upper) { *tabs = rt->d_tabs_w; *mode = 2; return GPQ_OK; }
   *mode = 1;
   return get_scaled_tabs(c, bp, tabs);
 }
@@ -83,7 +83,7 @@ int tail_stream(const Tail &t, const TailD *dh, FlagScope *scope, bool *done, un
   const unsigned W = t.W, dimB = t.dimB, logql = t.logql, polys = t.polys;
   *done = false;
   const unsigned need = (logql + 63) / 64;
-  if (!c->stream_bridge || W > 14 || W < need || logql > 896) return GPQ_OK;
+  if (!c->set.stream_bridge || W > 14 || W < need || logql > 896) return GPQ_OK;
   int KST, KSD = 0;
   if (dh) {
     if (!stream_fast_ok(c, dh->bA, logql)) return GPQ_OK;
@@ -106,7 +106,7 @@ int tail_stream(const Tail &t, const TailD *dh, FlagScope *scope, bool *done, un
   if (chat_bytes >= 0xfffff000ull || dhat_bytes >= 0xfffff000ull) return GPQ_OK;
   TailStreamArgs a{t.chat, dh ? dh->hat : nullptr, chat_bytes, dhat_bytes, t.dbig, t.out, (const v4i *)tt->d_bfrag, tt->d_kc, tt->d_pm,
                    dh ? (const v4i *)td->d_bfrag : nullptr, dh ? td->d_kc : nullptr, dh ? td->d_pm : nullptr,
-                   c->d_redo, t.w.tie, t.w.amb, c->d_wave_any, dimB, dh ? dh->dimA : 0u, c->logn, W, logql, groups, c->debug_force_redo,
+                   c->d_redo, t.w.tie, t.w.amb, c->d_wave_any, dimB, dh ? dh->dimA : 0u, c->logn, W, logql, groups, c->set.debug_force_redo,
                    rs, rs ? logql - rs : 0u};
   ProfScope prof(c, GPQ_K_TAIL_STREAM, t.s);
   if (dh && KST == 8) rc = launch_tail_stream_t<8, 4, true, 6>(a, lds, blocks, t.s);
@@ -155,7 +155,7 @@ int tail_exact_finish(const Tail &t, const RelinFrontArgs &front, bool front_fir
 // where he_mul's addend lies as words once its CRT has run into dh->scratch
 Two<const uint64_t> addend_words(const Tail &t, const TailD *dh) { return {dh->scratch, dh->scratch + (size_t)t.out.split * t.W * t.c->n, t.out.split}; }
 
-// Flow 1, the one-product tail.  The limbs carry the CRT weights of the whole basis (ScaledInverse with get_tail_direct's table): ONE
+// Flow 1, the one-product tail.  The limbs carry the CRT weights of the whole basis (gpq_keyswitch_scaled with get_tail_direct's table): ONE
 // product gives floor(x/P), the rounding decision and the centring of x -- as a stream (tail_stream) or as bridge_reconstruct_low_mfma<16>.
 // `chat` is the caller's scratch here (c0hat | c1hat of the workspace): the groups of 64 coefficients the product cannot decide get their
 // weights taken off in place and go through the exact finish.  Behind the streaming kernel the chains whose hand-overs stay inside a thread
@@ -210,7 +210,7 @@ int tail_one_pass_tables(const Tail &t, gpq_recon_mfma **tq) {
   *tq = nullptr;
   const unsigned need = (t.logql + 63) / 64;
   const int WLf = width_for(need, {7, 14});
-  const bool can_fuse = c->fuse_tail && !t.in_place && !c->exact_crt && need <= 14 && need + 1 < (unsigned)t.bq->WP && t.bq->pbits >= 160 && t.tp.cnt >= 4 &&
+  const bool can_fuse = c->set.fuse_tail && !t.in_place && !c->set.exact_crt && need <= 14 && need + 1 < (unsigned)t.bq->WP && t.bq->pbits >= 160 && t.tp.cnt >= 4 &&
                         t.tp.cnt <= 4 * RELIN_TAIL_MAXTILES && (t.rt->KS == 2 || t.rt->KS == 4);
   if (!can_fuse) return GPQ_OK;
   gpq_recon_mfma *q;
@@ -324,8 +324,8 @@ int relin_tail(gpq_ctx *c, Two<uint64_t> out, const uint64_t *chat, Two<const ui
     launch_masked(t, bridge_limb_scale, kNoScope, LimbScaleArgs{c->d_tabs, const_cast<uint64_t *>(chat), rt->d_unscale, nullptr, dimB, c->logn, kNoScope});
     chat_prescaled = 0;
   }
-  if (c->bridge_mfma && c->logn >= 6 && (rc = get_relin_front(c, dimP, dimB, rt, bp, bq))) return rc;
-  if (c->bridge_mfma && c->logn >= 6 && rt->d_bfrag) {
+  if (c->set.bridge_mfma && c->logn >= 6 && (rc = get_relin_front(c, dimP, dimB, rt, bp, bq))) return rc;
+  if (c->set.bridge_mfma && c->logn >= 6 && rt->d_bfrag) {
     gpq_recon_mfma *tq;
     if ((rc = tail_one_pass_tables(t, &tq))) return rc;
     // the front makes Q's (pre-scaled) residues and the round bits from chat; wsc: the limbs above P arrive multiplied by w_j -- the w-scaled tables

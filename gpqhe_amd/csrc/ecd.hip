@@ -23,9 +23,9 @@ using namespace gpq;
 struct gpq_ecd_plan {
   gpq_ctx *ctx = nullptr;
   unsigned slots = 0, logslots = 0;
-  double2 *d_roots = nullptr;      // T[0 .. 4 slots]
-  uint32_t *d_pow5 = nullptr;      // 5^j mod 4 slots
-  uint32_t *d_bad = nullptr;       // gpq_gemv_plan_create_from_matrix's own counter ...
+  gpq_dev<double2> d_roots;        // T[0 .. 4 slots]
+  gpq_dev<uint32_t> d_pow5;        // 5^j mod 4 slots
+  gpq_dev<uint32_t> d_bad;         // gpq_gemv_plan_create_from_matrix's own counter ...
   uint32_t *h_bad = nullptr;       // ... and the page-locked word it is read through
 };
 
@@ -77,9 +77,6 @@ extern "C" int gpq_ecd_roots(double *table, unsigned slots) {
 extern "C" void gpq_ecd_plan_destroy(gpq_ecd_plan *p) {
   if (!p) return;
   DeviceScope on_device(p->ctx->device);
-  if (p->d_roots) (void)hipFree(p->d_roots);
-  if (p->d_pow5) (void)hipFree(p->d_pow5);
-  if (p->d_bad) (void)hipFree(p->d_bad);
   if (p->h_bad) (void)hipHostFree(p->h_bad);
   delete p;
 }
@@ -108,9 +105,9 @@ extern "C" int gpq_ecd_plan_create(gpq_ctx *c, gpq_ecd_plan **out, unsigned slot
   if (!p) return gpq_fail(GPQ_ERR_NOMEM, "out of host memory");
   p->ctx = c; p->slots = slots; p->logslots = log2u(slots);
   DeviceScope on_device(c->device);
-  HIP_TRY(hipMalloc((void **)&p->d_roots, T.size() * sizeof(double)));
-  HIP_TRY(hipMalloc((void **)&p->d_pow5, pow5.size() * sizeof(uint32_t)));
-  HIP_TRY(hipMalloc((void **)&p->d_bad, sizeof(uint32_t)));
+  HIP_TRY(p->d_roots.alloc(T.size() * sizeof(double)));
+  HIP_TRY(p->d_pow5.alloc(pow5.size() * sizeof(uint32_t)));
+  HIP_TRY(p->d_bad.alloc(sizeof(uint32_t)));
   HIP_TRY(hipHostMalloc((void **)&p->h_bad, sizeof(uint32_t), hipHostMallocDefault));
   HIP_TRY(hipMemcpy(p->d_roots, T.data(), T.size() * sizeof(double), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(p->d_pow5, pow5.data(), pow5.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
@@ -157,17 +154,15 @@ extern "C" int gpq_gemv_plan_create_from_matrix(gpq_ctx *c, gpq_gemv_plan **out,
                                                 unsigned logql, unsigned dimpt, void *stream) {
   if (!c || !out || !p || p->ctx != c || !A_dev) return gpq_fail(GPQ_ERR_INVALID, "gpq_gemv_plan_create_from_matrix: null argument, or a plan of another context");
   hipStream_t s = (hipStream_t)stream;
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
+  if (gpq_capturing(s))
     return gpq_fail(GPQ_ERR_INVALID, "gpq_gemv_plan_create_from_matrix allocates and waits for the stream: not inside a stream capture");
   // one word per coefficient: every encodable value fits (|v| < 2^63), 8 n bytes per diagonal
-  uint64_t *slab = nullptr;
+  gpq_dev<uint64_t> slab;                                     // (its hipFree waits for the transforms that read it)
   const size_t bytes = (size_t)p->slots * c->n * 8;
-  if (hipMalloc((void **)&slab, bytes) != hipSuccess) {
+  if (slab.alloc(bytes) != hipSuccess) {
     (void)hipGetLastError();
     return gpq_fail(GPQ_ERR_NOMEM, "gpq_gemv_plan_create_from_matrix: no room for %zu bytes of encoded diagonals", bytes);
   }
-  struct Release { uint64_t *q; ~Release() { (void)hipFree(q); } } release{slab};   // (hipFree waits for the transforms that read it)
   *p->h_bad = 0;
   HIP_TRY(hipMemsetAsync(p->d_bad, 0, sizeof(uint32_t), s));
   int rc = gpq_he_ecd_diagonals(c, p, slab, A_dev, logDelta, 1, p->d_bad, stream);

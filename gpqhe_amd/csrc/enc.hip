@@ -43,12 +43,7 @@ int error_table(gpq_ctx *c, const uint16_t **out) {
     std::vector<int8_t> T(2 * 65536);
     int rc = gpq_sample_error_table(T.data());
     if (rc) return rc;
-    DeviceScope scope(c->device);
-    uint16_t *d = nullptr;
-    HIP_TRY(gpq_table_malloc(c, (void **)&d, T.size()));
-    hipError_t e = hipMemcpy(d, T.data(), T.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(d); c->cache->device_bytes -= T.size(); return gpq_fail(GPQ_ERR_HIP, "gpq_sample_error: uploading the table: %s", hipGetErrorString(e)); }
-    c->cache->d_error_table = d;
+    if ((rc = c->cache->d_error_table.upload(c, T))) return rc;
   }
   *out = c->cache->d_error_table;
   return GPQ_OK;

@@ -168,11 +168,10 @@ static int upload_tables(gpq_ctx *c) {
   HIP_TRY(hipGetDeviceCount(&ndev));
   if (c->device < 0 || c->device >= ndev) return gpq_fail(GPQ_ERR_INVALID, "device %d outside 0..%d", c->device, ndev - 1);
   DeviceScope on_device(c->device);
-  if (!c->cache) c->cache = new (std::nothrow) gpq_table_cache();
+  c->cache.reset(new (std::nothrow) gpq_table_cache());
   if (!c->cache) return gpq_fail(GPQ_ERR_NOMEM, "out of host memory");
-  HIP_TRY(gpq_table_malloc(c, (void **)&c->d_w, np * n * sizeof(uint64_t)));
-  HIP_TRY(gpq_table_malloc(c, (void **)&c->d_winv, np * n * sizeof(uint64_t)));
-  HIP_TRY(gpq_table_malloc(c, (void **)&c->d_tabs, np * sizeof(LimbTab)));
+  gpq_table_cache &tc = *c->cache;
+  int rc;
   std::vector<uint64_t> wstd(np * n), wistd(np * n);
   std::vector<LimbTab> tabs(np);
   for (size_t d = 0; d < np; ++d) {
@@ -197,15 +196,15 @@ static int upload_tables(gpq_ctx *c) {
     t.ninv_s = t.winv1_ninv_s = TwS{0, 0};
   }
   // split-twiddle pairs (p - w, p - w*2^31 mod p) for the leading limbs whose c allows the single fold ...
-  c->nsplit = 0;
-  while (c->nsplit < np && c->p[c->nsplit] - (1ull << 59) < GPQ_SPLIT_CMAX) ++c->nsplit;
+  c->set.nsplit = 0;
+  while (c->set.nsplit < np && c->p[c->set.nsplit] - (1ull << 59) < GPQ_SPLIT_CMAX) ++c->set.nsplit;
   // ... and among them the leading limbs whose forward stages may skip every other conditional subtraction (ct_bfly_wide)
-  c->nwide = 0;
-  while (c->nwide < c->nsplit && c->p[c->nwide] - (1ull << 59) < GPQ_WIDE_CMAX) ++c->nwide;
-  c->nsplit_tables = c->nsplit;
+  c->set.nwide = 0;
+  while (c->set.nwide < c->set.nsplit && c->p[c->set.nwide] - (1ull << 59) < GPQ_WIDE_CMAX) ++c->set.nwide;
+  c->nsplit_tables = c->set.nsplit;
   c->low9 = c->logn == 17;            // n = 2^17: 8 strided stages over 512-coefficient rows + 9 low stages
-  if (c->nsplit) {
-    const size_t ns = c->nsplit;
+  if (c->set.nsplit) {
+    const size_t ns = c->set.nsplit;
     std::vector<TwS> ws(ns * n), wis(ns * n);
     for (size_t d = 0; d < ns; ++d) {
       const uint64_t p = c->p[d];
@@ -218,23 +217,19 @@ static int upload_tables(gpq_ctx *c) {
       // the wide butterflies run multiplicands up to 8p - 1 through the injected multiply: every entry they read (index 0, the
       // twiddle 1, is read by no stage) must keep th in 32 bits.  A limb with a failing entry ends the wide range: it and the
       // limbs after it take the split class, whose multiplicands (< 6p) leave the margin for any entry.
-      if (d < c->nwide) {
+      if (d < c->set.nwide) {
         bool ok = split_entry_fits_wide(p, tabs[d].ninv_s.x, tabs[d].ninv_s.y) && split_entry_fits_wide(p, tabs[d].winv1_ninv_s.x, tabs[d].winv1_ninv_s.y);
         for (size_t i = 1; ok && i < n; ++i)
           ok = split_entry_fits_wide(p, ws[d * n + i].x, ws[d * n + i].y) && split_entry_fits_wide(p, wis[d * n + i].x, wis[d * n + i].y);
-        if (!ok) c->nwide = (unsigned)d;
+        if (!ok) c->set.nwide = (unsigned)d;
       }
     }
-    HIP_TRY(gpq_table_malloc(c, (void **)&c->d_ws, ns * n * sizeof(TwS)));
-    HIP_TRY(gpq_table_malloc(c, (void **)&c->d_winvs, ns * n * sizeof(TwS)));
-    HIP_TRY(hipMemcpy(c->d_ws, ws.data(), ns * n * sizeof(TwS), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(c->d_winvs, wis.data(), ns * n * sizeof(TwS), hipMemcpyHostToDevice));
+    if ((rc = tc.d_ws.upload(c, ws)) || (rc = tc.d_winvs.upload(c, wis))) return rc;
   }
-  c->nwide_max = c->nwide;
-  HIP_TRY(hipMemcpy(c->d_w, wstd.data(), np * n * 8, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(c->d_winv, wistd.data(), np * n * 8, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(c->d_tabs, tabs.data(), np * sizeof(LimbTab), hipMemcpyHostToDevice));
-  c->h_tabs = tabs;
+  c->nwide_max = c->set.nwide;
+  if ((rc = tc.d_w.upload(c, wstd)) || (rc = tc.d_winv.upload(c, wistd)) || (rc = tc.d_tabs.upload(c, tabs))) return rc;
+  tc.h_tabs = std::move(tabs);
+  c->d_w = tc.d_w; c->d_winv = tc.d_winv; c->d_ws = tc.d_ws; c->d_winvs = tc.d_winvs; c->d_tabs = tc.d_tabs;
   return alloc_zero_flags(c);
 }
 
@@ -243,10 +238,9 @@ static int alloc_zero_flags(gpq_ctx *c) {
   DeviceScope on_device(c->device);
   // gpq_ntt's zero flags for launches of up to 4096 (polynomial, limb) units exist from the start, so that a FIRST gpq_ntt inside a
   // stream capture works; larger launches grow them at their first call, outside capture (zero_flags)
-  HIP_TRY(hipMalloc((void **)&c->d_zflag, 4096 * sizeof(unsigned)));
+  HIP_TRY(c->d_zflag.alloc(4096 * sizeof(unsigned)));
   HIP_TRY(hipMemset(c->d_zflag, 0, 4096 * sizeof(unsigned)));
   HIP_TRY(hipStreamSynchronize(nullptr));      // (a device memset is not host-synchronous: done before any stream of the caller's can see the words)
-  c->zflag_cap = 4096;
   return GPQ_OK;
 }
 
@@ -323,40 +317,21 @@ int gpq_ctx_clone(const gpq_ctx *c, gpq_ctx **out) {
   q->p = c->p; q->pinv_mont = c->pinv_mont; q->pinv_barr = c->pinv_barr; q->ninv_mont = c->ninv_mont; q->psi = c->psi;
   // (no host twiddles: gpq_ctx_zetas is the parent's business; nothing the peer runs reads them)
   q->overlap = 0;
-  // every read-only device table is the parent's (engine_internal.hpp: gpq_table_cache)
-  q->tables_of = c;
+  // every read-only device table is the parent's, shared (engine_internal.hpp: gpq_table_cache)
+  q->cache = c->cache; q->tables_borrowed = true;
   q->d_w = c->d_w; q->d_winv = c->d_winv; q->d_ws = c->d_ws; q->d_winvs = c->d_winvs; q->d_tabs = c->d_tabs;
-  q->h_tabs = c->h_tabs;
-  q->nsplit = c->nsplit; q->nsplit_tables = c->nsplit_tables; q->nwide = c->nwide; q->nwide_max = c->nwide_max; q->low9 = c->low9;
-  q->cache = c->cache;
+  q->set.nsplit = c->set.nsplit; q->nsplit_tables = c->nsplit_tables; q->set.nwide = c->set.nwide; q->nwide_max = c->nwide_max; q->low9 = c->low9;
   int rc = alloc_zero_flags(q);
   if (rc != GPQ_OK) { gpq_ctx_destroy(q); return rc; }
   *out = q;
   return GPQ_OK;
 }
 
+// Everything a context holds is an owner (engine_internal.hpp), and the table cache is shared with the peer: nothing to free by hand
 extern "C" void gpq_ctx_destroy(gpq_ctx *c) {
   if (!c) return;
-  if (c->peer) {
-    if (c->peer_stream) (void)hipStreamSynchronize(c->peer_stream);
-    gpq_ctx_destroy(c->peer);                                    // before the tables it borrows go
-  }
-  if (c->peer_stream) (void)hipStreamDestroy(c->peer_stream);
-  if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-  if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-  if (c->peer_ws) (void)hipFree(c->peer_ws);
-  if (!c->tables_of) {
-    if (c->d_w) (void)hipFree(c->d_w);
-    if (c->d_winv) (void)hipFree(c->d_winv);
-    if (c->d_ws) (void)hipFree(c->d_ws);
-    if (c->d_winvs) (void)hipFree(c->d_winvs);
-    if (c->d_tabs) (void)hipFree(c->d_tabs);
-  }
-  if (c->d_zflag) (void)hipFree(c->d_zflag);
-  if (c->d_zwatch) (void)hipFree(c->d_zwatch);
-  gpq_bridge_release(c);
-  for (gpq_prof_rec &r : c->prof) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
-  for (hipEvent_t e : c->prof_pool) (void)hipEventDestroy(e);
+  if (c->peer && c->peer_stream) (void)hipStreamSynchronize(c->peer_stream);
+  gpq_ctx_destroy(c->peer);
   delete c;
 }
 
@@ -364,8 +339,8 @@ extern "C" void gpq_ctx_destroy(gpq_ctx *c) {
 // peer lane owns of the same kind (1: zero by construction, the peer borrows), and whether a peer exists (2).
 extern "C" size_t gpq_debug_table_bytes(const gpq_ctx *c, int which) {
   if (!c) return 0;
-  if (which == 0) return c->cache && !c->tables_of ? c->cache->device_bytes : 0;
-  if (which == 1) return c->peer && !c->peer->tables_of && c->peer->cache ? c->peer->cache->device_bytes : 0;
+  if (which == 0) return c->cache && !c->tables_borrowed ? c->cache->device_bytes : 0;
+  if (which == 1) return c->peer && !c->peer->tables_borrowed && c->peer->cache ? c->peer->cache->device_bytes : 0;
   if (which == 2) return c->peer ? 1 : 0;
   if (which == 3) return c->peer ? (size_t)(c->peer->d_w == c->d_w && c->peer->d_winv == c->d_winv && c->peer->d_ws == c->d_ws && c->peer->d_winvs == c->d_winvs &&
                                             c->peer->d_tabs == c->d_tabs && c->peer->cache == c->cache) : 0;
@@ -473,7 +448,7 @@ int check_shape(const gpq_ctx *c, unsigned dim, unsigned batch, const char *who)
 // tables and each other's lines (336 MB: +4.6 %; the he_mul core at the headline shape: +2.4 %) -- profiles/r04/v10_nt_policy_ab.txt.
 // `slabs` = the slabs of polys x limbs x n words the group moves between its kernels.
 static unsigned nt_for(const gpq_ctx *c, size_t polys, unsigned limbs, unsigned slabs) {
-  if (c->nt_mode >= 0) return (unsigned)c->nt_mode;
+  if (c->set.nt_mode >= 0) return (unsigned)c->set.nt_mode;
   return polys * limbs * ((size_t)8 << c->logn) * slabs > ((size_t)288 << 20);
 }
 
@@ -500,7 +475,7 @@ template <bool WIDE, typename F>
 int for_limb_ranges(const gpq_ctx *c, PassArgs a, unsigned dim, const uint64_t **evk0, const uint64_t **evk1, F f) {
   const unsigned lo = a.limb0, hi = a.limb0 + dim;
   auto upto = [&](unsigned bound) { return bound < lo ? lo : (bound > hi ? hi : bound); };
-  const unsigned e_wide = WIDE ? upto(c->nwide) : lo, e_split = upto(c->nsplit);
+  const unsigned e_wide = WIDE ? upto(c->set.nwide) : lo, e_split = upto(c->set.nsplit);
   auto advance = [&](unsigned limbs) {
     const size_t shift = (size_t)limbs << c->logn;
     a.limb0 += limbs;
@@ -629,19 +604,9 @@ int after_launch(const char *who) {
 // The zero flags of a forward launch (tables.hpp: PassArgs::zflag), polys * dim words, all zero between calls (ref_zero_redo
 // clears what it finds set).  An outgrown buffer is retired, not freed: a HIP graph captured earlier may still use it.
 int zero_flags(gpq_ctx *c, size_t count, hipStream_t s, unsigned **out) {
-  if (count > c->zflag_cap) {
-    // (growing inside a stream capture would put the allocation into the graph: the first call at a new size runs outside capture, as for the CRT scratch)
-    hipStreamCaptureStatus cap_status = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cap_status) == hipSuccess && cap_status != hipStreamCaptureStatusNone)
-      return gpq_fail(GPQ_ERR_INVALID, "the first gpq_ntt at a new batch size allocates its zero flags: run it once outside stream capture");
-    DeviceScope on_device(c->device);
-    unsigned *fresh = nullptr;
-    const size_t cap = count < 4096 ? 4096 : count;
-    HIP_TRY(hipMalloc((void **)&fresh, cap * sizeof(unsigned)));
-    HIP_TRY(hipMemsetAsync(fresh, 0, cap * sizeof(unsigned), s));
-    if (c->d_zflag) c->retired.push_back(c->d_zflag);
-    c->d_zflag = fresh; c->zflag_cap = cap;
-  }
+  // (the first call at a new size runs outside capture, as for the CRT scratch)
+  if (count * sizeof(unsigned) > c->d_zflag.bytes)
+    if (int rc = c->d_zflag.grow(c, s, count * sizeof(unsigned), true, "the first gpq_ntt at a new batch size allocates its zero flags: run it once outside stream capture")) return rc;
   *out = c->d_zflag;
   return GPQ_OK;
 }
@@ -710,13 +675,13 @@ extern "C" int gpq_debug_zero_watch(gpq_ctx *c, int on) {
   if (!c) return gpq_fail(GPQ_ERR_INVALID, "gpq_debug_zero_watch: null context");
   DeviceScope on_device(c->device);
   if (!on) {
-    if (c->d_zwatch) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(c->d_zwatch)); }
-    c->d_zwatch = nullptr; c->zwatch_cap = c->zwatch_count = 0;
+    if (c->d_zwatch) { HIP_TRY(hipDeviceSynchronize()); c->d_zwatch.reset(); }
+    c->zwatch_cap = c->zwatch_count = 0;
     return GPQ_OK;
   }
   if (!c->d_zwatch) {
     const size_t want = (size_t)kMaxPolysPerLaunch * c->nprimes, cap = want < ((size_t)1 << 20) ? want : ((size_t)1 << 20);   // larger launch groups are not watched
-    HIP_TRY(hipMalloc((void **)&c->d_zwatch, 2 * cap * sizeof(unsigned)));
+    HIP_TRY(c->d_zwatch.alloc(2 * cap * sizeof(unsigned)));
     HIP_TRY(hipMemset(c->d_zwatch, 0xff, 2 * cap * sizeof(unsigned)));
     HIP_TRY(hipDeviceSynchronize());
     c->zwatch_cap = cap; c->zwatch_count = 0;
@@ -857,7 +822,7 @@ extern "C" int gpq_mulpt_rns(gpq_ctx *c, uint64_t *r0, uint64_t *r1, uint64_t *m
 // fused he_mul RNS core
 // ---------------------------------------------------------------------------
 static unsigned limb_block(const gpq_ctx *c, unsigned dim) {
-  return (c->limb_block && c->limb_block < dim) ? c->limb_block : dim;
+  return (c->set.limb_block && c->set.limb_block < dim) ? c->set.limb_block : dim;
 }
 
 extern "C" size_t gpq_tensor_workspace_bytes(const gpq_ctx *c, unsigned dim, unsigned batch) {
@@ -872,6 +837,10 @@ extern "C" size_t gpq_keyswitch_workspace_bytes(const gpq_ctx *c, unsigned dim, 
 extern "C" int gpq_he_mul_tensor(gpq_ctx *c, uint64_t *d0, uint64_t *d1, uint64_t *d2,
                                  const uint64_t *a0, const uint64_t *a1, const uint64_t *b0, const uint64_t *b1,
                                  unsigned dim, unsigned batch, void *workspace, void *stream) {
+  return gpq_he_mul_tensor_scaled(c, d0, d1, d2, a0, a1, b0, b1, dim, batch, workspace, stream, nullptr);
+}
+int gpq_he_mul_tensor_scaled(gpq_ctx *c, uint64_t *d0, uint64_t *d1, uint64_t *d2, const uint64_t *a0, const uint64_t *a1, const uint64_t *b0,
+                             const uint64_t *b1, unsigned dim, unsigned batch, void *workspace, void *stream, const LimbTab *inv_tabs) {
   int rc = check_shape(c, dim, batch, "gpq_he_mul_tensor");
   if (rc) return rc;
   if (!d0 || !d1 || !d2 || !a0 || !a1 || !b0 || !b1 || !workspace)
@@ -906,7 +875,7 @@ extern "C" int gpq_he_mul_tensor(gpq_ctx *c, uint64_t *d0, uint64_t *d1, uint64_
   const unsigned lblock = limb_block(c, dim);
   auto peer = [&](const PeerLane &lane, unsigned k0, unsigned polys) {
     const size_t o = k0 * poly;
-    return gpq_he_mul_tensor(lane.c, d0 + o, d1 + o, d2 + o, a0 + o, a1 + o, b0 + o, b1 + o, dim, polys, lane.ws, lane.s);
+    return gpq_he_mul_tensor_scaled(lane.c, d0 + o, d1 + o, d2 + o, a0 + o, a1 + o, b0 + o, b1 + o, dim, polys, lane.ws, lane.s, inv_tabs);
   };
   auto own = [&](unsigned k0, unsigned polys) {
     int rc;
@@ -934,20 +903,24 @@ extern "C" int gpq_he_mul_tensor(gpq_ctx *c, uint64_t *d0, uint64_t *d1, uint64_
       // 3. strided inverse pass in place on the three outputs
       PassArgs b = make_args(c, dim, 3, nt);
       b.limb0 = l0;
-      if (c->inv_tabs_override) b.tabs = c->inv_tabs_override;
+      if (inv_tabs) b.tabs = inv_tabs;
       for (int i = 0; i < 3; ++i) { b.src[i] = m.dst[i]; b.dst[i] = m.dst[i]; }
       if ((rc = launch_strided<true>(c, b, limbs, polys, s))) return rc;
     }
     return (int)GPQ_OK;
   };
-  // two launch groups in flight (engine_internal.hpp: gpq_launch_groups)
-  if ((rc = gpq_launch_groups(c, s, batch, chunk, gpq_lane_key(3, dim, chunk, 0, 0, 0), [&](gpq_ctx *q) { return gpq_tensor_workspace_bytes(q, dim, chunk); }, own, peer))) return rc;
+  // two launch groups in flight (engine_internal.hpp: gpq_launch_groups; a workspace of 0 bytes: no lane for a call with a scaled table)
+  if ((rc = gpq_launch_groups(c, s, batch, chunk, gpq_lane_key(3, dim, chunk, 0, 0, 0), [&](gpq_ctx *q) { return inv_tabs ? 0 : gpq_tensor_workspace_bytes(q, dim, chunk); }, own, peer))) return rc;
   return after_launch("gpq_he_mul_tensor");
 }
 
 extern "C" int gpq_keyswitch(gpq_ctx *c, uint64_t *c0, uint64_t *c1, const uint64_t *x,
                              const uint64_t *evk0, const uint64_t *evk1,
                              unsigned dim, unsigned batch, void *workspace, void *stream) {
+  return gpq_keyswitch_scaled(c, c0, c1, x, evk0, evk1, dim, batch, workspace, stream, nullptr);
+}
+int gpq_keyswitch_scaled(gpq_ctx *c, uint64_t *c0, uint64_t *c1, const uint64_t *x, const uint64_t *evk0, const uint64_t *evk1, unsigned dim,
+                         unsigned batch, void *workspace, void *stream, const LimbTab *inv_tabs) {
   int rc = check_shape(c, dim, batch, "gpq_keyswitch");
   if (rc) return rc;
   if (!c0 || !c1 || !x || !evk0 || !evk1 || !workspace) return gpq_fail(GPQ_ERR_INVALID, "gpq_keyswitch: null pointer");
@@ -970,7 +943,7 @@ extern "C" int gpq_keyswitch(gpq_ctx *c, uint64_t *c0, uint64_t *c1, const uint6
   const unsigned lblock = limb_block(c, dim);
   auto peer = [&](const PeerLane &lane, unsigned k0, unsigned polys) {
     const size_t o = k0 * poly;
-    return gpq_keyswitch(lane.c, c0 + o, c1 + o, x + o, evk0, evk1, dim, polys, lane.ws, lane.s);
+    return gpq_keyswitch_scaled(lane.c, c0 + o, c1 + o, x + o, evk0, evk1, dim, polys, lane.ws, lane.s, inv_tabs);
   };
   auto own = [&](unsigned k0, unsigned polys) {
     int rc;
@@ -994,13 +967,13 @@ extern "C" int gpq_keyswitch(gpq_ctx *c, uint64_t *c0, uint64_t *c1, const uint6
           }))) return rc;
       PassArgs b = make_args(c, dim, 2, nt);
       b.limb0 = l0;
-      if (c->inv_tabs_override) b.tabs = c->inv_tabs_override;
+      if (inv_tabs) b.tabs = inv_tabs;
       for (int i = 0; i < 2; ++i) { b.src[i] = m.p.dst[i]; b.dst[i] = m.p.dst[i]; }
       if ((rc = launch_strided<true>(c, b, limbs, polys, s))) return rc;
     }
     return (int)GPQ_OK;
   };
-  if ((rc = gpq_launch_groups(c, s, batch, chunk, gpq_lane_key(4, dim, chunk, 0, 0, 0), [&](gpq_ctx *q) { return gpq_keyswitch_workspace_bytes(q, dim, chunk); }, own, peer))) return rc;
+  if ((rc = gpq_launch_groups(c, s, batch, chunk, gpq_lane_key(4, dim, chunk, 0, 0, 0), [&](gpq_ctx *q) { return inv_tabs ? 0 : gpq_keyswitch_workspace_bytes(q, dim, chunk); }, own, peer))) return rc;
   return after_launch("gpq_keyswitch");
 }
 
@@ -1033,7 +1006,7 @@ int gpq_hoist_forward(gpq_ctx *c, uint64_t *slab, unsigned dim, unsigned polys, 
 }
 
 int gpq_keyswitch_rotated(gpq_ctx *c, uint64_t *c0, uint64_t *c1, const uint64_t *X, const uint64_t *evk0, const uint64_t *evk1,
-                          unsigned dim, unsigned polys, unsigned g, void *workspace, hipStream_t s) {
+                          unsigned dim, unsigned polys, unsigned g, void *workspace, hipStream_t s, const LimbTab *inv_tabs) {
   const size_t poly = (size_t)dim << c->logn;
   int rc;
   if (!two_pass(c)) {
@@ -1061,7 +1034,7 @@ int gpq_keyswitch_rotated(gpq_ctx *c, uint64_t *c0, uint64_t *c1, const uint64_t
         return keyswitch_rot_mid8x2<typename I::TW, I::LOW, decltype(two)::value, I::NT>;
       }, g))) return rc;
   PassArgs b = make_args(c, dim, 2, nt);
-  if (c->inv_tabs_override) b.tabs = c->inv_tabs_override;
+  if (inv_tabs) b.tabs = inv_tabs;
   b.src[0] = b.dst[0] = c0; b.src[1] = b.dst[1] = c1;
   if ((rc = launch_strided<true>(c, b, dim, polys, s))) return rc;
   return after_launch("gpq_he_rot_hoisted: key switch");
@@ -1089,15 +1062,15 @@ int gpq_gemv_mac(gpq_ctx *c, uint64_t *acc0, uint64_t *acc1, const uint64_t *r0,
 extern "C" int gpq_set_nt_policy(gpq_ctx *c, int mode) {
   if (!c) return gpq_fail(GPQ_ERR_INVALID, "gpq_set_nt_policy: null context");
   if (mode < -1 || mode > 1) return gpq_fail(GPQ_ERR_INVALID, "gpq_set_nt_policy: mode %d (want -1 by working set, 0 never, 1 always)", mode);
-  c->nt_mode = mode;
+  c->set.nt_mode = mode;
   return GPQ_OK;
 }
 
 extern "C" int gpq_set_limb_classes(gpq_ctx *c, unsigned wide, unsigned split) {
   if (!c) return gpq_fail(GPQ_ERR_INVALID, "gpq_set_limb_classes: null context");
-  c->nsplit = split < c->nsplit_tables ? split : c->nsplit_tables;
-  c->nwide = wide < c->nwide_max ? wide : c->nwide_max;
-  if (c->nwide > c->nsplit) c->nwide = c->nsplit;
+  c->set.nsplit = split < c->nsplit_tables ? split : c->nsplit_tables;
+  c->set.nwide = wide < c->nwide_max ? wide : c->nwide_max;
+  if (c->set.nwide > c->set.nsplit) c->set.nwide = c->set.nsplit;
   return GPQ_OK;
 }
 
@@ -1109,13 +1082,13 @@ extern "C" int gpq_debug_split_entry_fits_wide(uint64_t p, uint64_t x, uint64_t 
 
 extern "C" int gpq_set_limb_block(gpq_ctx *c, unsigned limbs) {
   if (!c) return gpq_fail(GPQ_ERR_INVALID, "gpq_set_limb_block: null context");
-  c->limb_block = limbs;
+  c->set.limb_block = limbs;
   return GPQ_OK;
 }
 
 extern "C" int gpq_set_chunk(gpq_ctx *c, unsigned chunk) {
   if (!c || chunk < 1 || chunk > kMaxPolysPerLaunch) return gpq_fail(GPQ_ERR_INVALID, "gpq_set_chunk: bad arguments");
-  c->chunk = chunk;
+  c->set.chunk = chunk;
   return GPQ_OK;
 }
 
@@ -1195,8 +1168,8 @@ extern "C" int gpq_profile_collect(gpq_ctx *c, double *total_ms, unsigned long l
     HIP_TRY(hipEventElapsedTime(&ms, r.a, r.b));
     total_ms[r.kernel] += ms;
     launches[r.kernel] += 1;
-    c->prof_pool.push_back(r.a);
-    c->prof_pool.push_back(r.b);
+    c->prof_pool.push_back(std::move(r.a));
+    c->prof_pool.push_back(std::move(r.b));
   }
   c->prof.clear();
   return GPQ_OK;

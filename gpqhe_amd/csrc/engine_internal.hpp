@@ -3,14 +3,78 @@
 #include <atomic>
 #include <cstdio>
 #include <map>
+#include <memory>
 #include <set>
 #include <string>
+#include <utility>
 #include <vector>
 #include "tables.hpp"
 
+struct gpq_ctx;
+int gpq_fail(int code, const char *fmt, ...);
+
+// Is `s` inside a stream capture?  A failed query counts as "no" (*query_failed says so: gpq_peer_lane then takes no lane and clears the error).
+inline bool gpq_capturing(hipStream_t s, bool *query_failed = nullptr) {
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  const bool ok = hipStreamIsCapturing(s, &cap) == hipSuccess;
+  if (query_failed) *query_failed = !ok;
+  return ok && cap != hipStreamCaptureStatusNone;
+}
+
+// The one owner of a device allocation: move-only, frees in its destructor, hands out its pointer wherever a T * is wanted (launch code and
+// kernel-argument structs read members of this type as plain pointers).  Bytes that upload() added to a table cache's device_bytes leave it
+// again with the owner, so a builder that fails half way leaks nothing and over-counts nothing.
+template <typename T>
+struct gpq_dev {
+  T *p = nullptr;
+  size_t bytes = 0;
+  size_t *counted = nullptr;          // the device_bytes these bytes are part of (read-only tables), or null
+  gpq_dev() = default;
+  gpq_dev(gpq_dev &&o) noexcept : p(o.p), bytes(o.bytes), counted(o.counted) { o.p = nullptr; o.bytes = 0; o.counted = nullptr; }
+  gpq_dev &operator=(gpq_dev &&o) noexcept { if (this != &o) { reset(); std::swap(p, o.p); std::swap(bytes, o.bytes); std::swap(counted, o.counted); } return *this; }
+  gpq_dev(const gpq_dev &) = delete;
+  gpq_dev &operator=(const gpq_dev &) = delete;
+  ~gpq_dev() { reset(); }
+  void reset() {
+    if (p) (void)hipFree(p);
+    if (counted) *counted -= bytes;
+    p = nullptr; bytes = 0; counted = nullptr;
+  }
+  operator T *() const { return p; }
+  template <typename U> explicit operator U *() const { return (U *)p; }
+  // a fresh block of `nbytes` on the current device (what it held before is freed)
+  hipError_t alloc(size_t nbytes) {
+    reset();
+    const hipError_t e = hipMalloc((void **)&p, nbytes);
+    if (e == hipSuccess) bytes = nbytes; else p = nullptr;
+    return e;
+  }
+  // a host vector as a read-only table of the context's cache, on the context's device; the copy is synchronous
+  template <typename U> int upload(gpq_ctx *c, const std::vector<U> &v);
+  // Scratch that grows at the first call of a new size: refused inside a stream capture (`refusal`: hipMalloc would go into the graph),
+  // allocated on the context's device, zeroed on the LAUNCH stream if asked (a plain hipMemset goes to the null stream, which a non-blocking
+  // stream -- torch's side streams, the peer lane's -- does not wait for: the words could be zeroed after a kernel wrote them); the
+  // outgrown block is retired to the context, not freed: a HIP graph captured earlier may still use it.
+  int grow(gpq_ctx *c, hipStream_t s, size_t nbytes, bool zero_on_stream, const char *refusal);
+  void retire(gpq_ctx *c);
+};
+
+// ... and of a stream or an event
+template <typename H, hipError_t (*Destroy)(H)>
+struct gpq_handle {
+  H h = nullptr;
+  gpq_handle() = default;
+  gpq_handle(gpq_handle &&o) noexcept : h(o.h) { o.h = nullptr; }
+  gpq_handle &operator=(gpq_handle &&o) noexcept { std::swap(h, o.h); return *this; }
+  ~gpq_handle() { if (h) (void)Destroy(h); }
+  operator H() const { return h; }
+};
+using gpq_event = gpq_handle<hipEvent_t, hipEventDestroy>;
+using gpq_stream_own = gpq_handle<hipStream_t, hipStreamDestroy>;
+
 // Optional per-launch timing with HIP events recorded on the launch stream
 // (bench.py's roofline leg).  Off by default: no events are created.
-struct gpq_prof_rec { int kernel; hipEvent_t a, b; };
+struct gpq_prof_rec { int kernel = 0; gpq_event a, b; };
 enum { GPQ_K_STRIDED_FWD = 0, GPQ_K_STRIDED_INV, GPQ_K_CONTIG_FWD, GPQ_K_CONTIG_INV, GPQ_K_TENSOR_MID,
        GPQ_K_KEYSWITCH_MID, GPQ_K_POINTWISE, GPQ_K_SMALL, GPQ_K_REFERENCE,
        // the MPI <-> RNS bridge (bridge.hip): rns_decompose, the CRT fast paths, the relinearisation front, its one-pass form, the exact /
@@ -32,8 +96,8 @@ enum { GPQ_K_STRIDED_FWD = 0, GPQ_K_STRIDED_INV, GPQ_K_CONTIG_FWD, GPQ_K_CONTIG_
 
 // Constant matrix of the matrix-core CRT fast path for one basis and result width WL (bridge_mfma.hpp)
 struct gpq_recon_mfma {
-  void *d_bfrag = nullptr;
-  uint64_t *d_lk = nullptr, *d_kc = nullptr, *d_pm = nullptr;
+  gpq_dev<void> d_bfrag;
+  gpq_dev<uint64_t> d_lk, d_kc, d_pm;
   unsigned KS = 0;
   size_t lds_bytes = 0;
 };
@@ -42,90 +106,78 @@ struct gpq_recon_mfma {
 struct gpq_bridge_basis {
   unsigned first = 0, dim = 0, pbits = 0;
   int WP = 0;
-  uint64_t *d_phat = nullptr, *d_phat_inv = nullptr, *d_pmult = nullptr, *d_phalf = nullptr, *d_inv128 = nullptr;
+  gpq_dev<uint64_t> d_phat, d_phat_inv, d_pmult, d_phalf, d_inv128;
   std::vector<uint64_t> h_phat_inv;
   std::vector<uint64_t> h_P;          // the product itself, little-endian words
   std::vector<uint64_t> h_phat;       // [dim][WP]
   std::map<int, gpq_recon_mfma> mfma; // by result width WL
-  gpq::LimbTab *d_tabs_scaled = nullptr;   // the context's LimbTab array with n^-1 * (P/p_d)^-1 for the limbs of this basis (ScaledInverse, bridge_tables.hpp)
+  gpq_dev<gpq::LimbTab> d_tabs_scaled;     // the context's LimbTab array with n^-1 * (P/p_d)^-1 for the limbs of this basis (get_scaled_tabs, bridge_tables.hpp)
 };
 
 // Constant matrix of the matrix-core rns_decompose for (first limb, limbs, words) (bridge_mfma.hpp)
 struct gpq_decomp_mfma {
-  void *d_bfrag = nullptr;
-  uint64_t *d_pk = nullptr;
+  gpq_dev<void> d_bfrag;
+  gpq_dev<uint64_t> d_pk;
   unsigned NT = 0, KS = 0;
   size_t lds_bytes = 0;
 };
 
 // P^-1 mod p_d for the limbs above a P of dimP limbs (exact division in he_relin / he_swk)
 struct gpq_relin_tables {
-  uint64_t *d_pinv = nullptr;
+  gpq_dev<uint64_t> d_pinv;
   // bridge_relin_front_mfma (bridge_mfma.hpp): constant matrix and per-limb tables, built on first use
   bool front_tried = false;
-  void *d_bfrag = nullptr;
-  uint64_t *d_lk = nullptr, *d_pk = nullptr, *d_tkp = nullptr, *d_kf = nullptr;
+  gpq_dev<void> d_bfrag;
+  gpq_dev<uint64_t> d_lk, d_pk, d_tkp, d_kf;
   unsigned NT = 0, KS = 0;
   size_t lds_bytes = 0;
   // the same tables for limbs that arrive multiplied by w_j = P^-1 (Pi'/p_j)^-1, and the per-limb table that makes the key switch's
   // inverse pass deliver them so (bridge_tables.hpp: get_relin_front; bridge_tail.hpp: tail_prescale_mode)
-  void *d_bfrag_w = nullptr;
-  uint64_t *d_pk_w = nullptr, *d_tkp_w = nullptr;
-  gpq::LimbTab *d_tabs_w = nullptr;
+  gpq_dev<void> d_bfrag_w;
+  gpq_dev<uint64_t> d_pk_w, d_tkp_w;
+  gpq_dev<gpq::LimbTab> d_tabs_w;
   // the one-product tail (bridge_tables.hpp: get_tail_direct): constant matrix of floor(Pi' 2^104 / p_d) over all dimB limbs, the per-limb table that
   // makes the key switch deliver CRT-weighted limbs (owned by the basis), the weights and their inverses for bridge_limb_scale
   bool direct_tried = false;
   gpq_recon_mfma direct;
   std::map<unsigned, gpq_recon_mfma> direct_padded;   // the same matrix zero-padded to KS k steps (bridge_stream.hpp's instantiations)
-  const gpq::LimbTab *d_tabs_direct = nullptr;
-  uint64_t *d_scale = nullptr, *d_unscale = nullptr;
+  const gpq::LimbTab *d_tabs_direct = nullptr;     // (the basis owns it)
+  gpq_dev<uint64_t> d_scale, d_unscale;
 };
 
 // Everything a context builds once and only reads afterwards on the device: the transform tables of upload_tables (engine.hip) and the bridge
-// constants bridge_tables.hpp builds at first use.  ONE object per prime chain: a context's peer lane (gpq_ctx_clone) points at its parent's, so the second
-// lane costs no table memory, no table-building time, and "the peer's tables differ" is not a state the library can be in.  Built and read by the
-// one host thread that drives the context (single caller); uploads are synchronous hipMemcpy, so a launch on either lane's stream that
-// follows a build on the host sees the table.
+// constants bridge_tables.hpp builds at first use.  ONE object per prime chain, held through a shared_ptr: a context's peer lane (gpq_ctx_clone)
+// shares its parent's, so the second lane costs no table memory, no table-building time, "the peer's tables differ" is not a state the library
+// can be in, and the tables live until the last of the two is gone, in whichever order they go.  Built and read by the one host thread that
+// drives the context (single caller); uploads are synchronous hipMemcpy, so a launch on either lane's stream that follows a build
+// on the host sees the table.  Every device pointer in it is a gpq_dev: the cache's destructor is the only release there is, and a builder
+// enters its struct into a map only once every upload has succeeded.
 struct gpq_table_cache {
+  size_t device_bytes = 0;            // read-only device memory behind this cache (gpq_dev::upload); first: the owners below take their bytes off it as they go
+  // transform tables (standard form); the contexts that share the cache read them through plain pointers of the same names
+  gpq_dev<uint64_t> d_w, d_winv;
+  gpq_dev<gpq::TwS> d_ws, d_winvs;    // split-twiddle pairs for the first nsplit_tables limbs (modarith.hpp)
+  gpq_dev<gpq::LimbTab> d_tabs;
+  std::vector<gpq::LimbTab> h_tabs;   // host copy (bridge_tables.hpp derives tables with pre-scaled n^-1 from it)
   std::map<std::pair<unsigned, unsigned>, gpq_bridge_basis> bases;   // by (first limb, count), built on first use
   std::map<std::pair<unsigned, unsigned>, gpq_relin_tables> relins;  // by (dimP, dimB)
   std::map<std::pair<std::pair<unsigned, unsigned>, unsigned>, gpq_decomp_mfma> decomps;  // by ((first limb, limbs), W)
-  size_t device_bytes = 0;            // read-only device memory behind this cache and the transform tables (gpq_table_malloc)
-  uint16_t *d_error_table = nullptr;  // gpq_sample_error's 65536 coefficient pairs (enc.hip), uploaded at first use
-  // Scaled per-limb tables (ScaledInverse, bridge_tables.hpp) one of whose split pairs fails the wide class's table check (modarith.hpp:
-  // split_entry_fits_wide), with the first such limb: a context that reads the table runs that limb and those after it in the split class.
-  // Empty for every chain met so far (the failing constants are ~100 values in 2^59).
+  gpq_dev<uint16_t> d_error_table;    // gpq_sample_error's 65536 coefficient pairs (enc.hip), uploaded at first use
+  // Scaled per-limb tables (get_scaled_tabs, get_relin_front) one of whose split pairs fails the wide class's table check (modarith.hpp:
+  // split_entry_fits_wide), with the first such limb: a context that reads the table runs that limb and those after it in the split class
+  // (bridge_tables.hpp: apply_scaled_wide_limit).  Empty for every chain met so far (the failing constants are ~100 values in 2^59).
   std::map<const gpq::LimbTab *, unsigned> scaled_wide_limit;
 };
 
-struct gpq_ctx {
-  int device = 0;
-  unsigned logn = 0, n = 0, nprimes = 0;
+// The switches that decide which kernels a call runs.  A member that decides which kernels a call runs belongs HERE: the peer lane follows the
+// context it serves by one assignment (gpq_peer_lane: q->set = c->set), so a switch kept elsewhere would let the two lanes run different kernels
+// -- both bit-exact, which no parity test notices.
+struct gpq_settings {
   unsigned chunk = 32; // polynomials per fused launch group (measured: larger groups amortise launch tails; profiles/r01/v9_sweep_chunk.txt)
   unsigned limb_block = 0; // limbs per fused launch group (0 = all limbs of the slab); gpq_set_limb_block
-  // host copies in the reference's own representation (struct rns_ctx, src/poly.h:28-41)
-  std::vector<uint64_t> p, pinv_mont, pinv_barr, ninv_mont, psi;
-  std::vector<uint64_t> zetas, zetas_inv;  // [nprimes][n], Montgomery form, bit-reversed index
-  // device tables (standard form)
-  uint64_t *d_w = nullptr, *d_winv = nullptr;
-  gpq::TwS *d_ws = nullptr, *d_winvs = nullptr;   // split-twiddle pairs for the first nsplit limbs (modarith.hpp)
-  unsigned nsplit = 0;                            // leading limbs that run the split-twiddle butterflies (c < GPQ_SPLIT_CMAX)
-  unsigned nsplit_tables = 0;                     // ... and for how many limbs the pair tables exist (gpq_set_limb_classes can only lower nsplit)
-  bool low9 = false;                              // n = 2^17: strided passes over 512-coefficient rows, 9 low stages (Lane8<9>)
-  unsigned nwide = 0, nwide_max = 0;              // leading limbs with c < GPQ_WIDE_CMAX (<= nsplit): forward stages as ct_bfly_wide
-  gpq::LimbTab *d_tabs = nullptr;
-  std::vector<gpq::LimbTab> h_tabs;               // host copy (bridge_tables.hpp derives tables with pre-scaled n^-1 from it)
-  // When set, the inverse strided pass of gpq_he_mul_tensor / gpq_keyswitch reads its per-limb constants here: the same tables
-  // with n^-1 (and winv[1] n^-1) multiplied by a CRT weight, so that the limbs leave the transform already scaled for the
-  // reconstruction that follows (bridge_tables.hpp: ScaledInverse).  Internal to gpq_he_mul / gpq_he_swk.
-  const gpq::LimbTab *inv_tabs_override = nullptr;
-  gpq_table_cache *cache = nullptr;   // the lazily built bridge constants (owned unless tables_of is set)
-  const gpq_ctx *tables_of = nullptr; // a peer lane: d_w / d_winv / d_ws / d_winvs / d_tabs and `cache` are the PARENT's, borrowed for the parent's lifetime
+  unsigned nsplit = 0;                // leading limbs that run the split-twiddle butterflies (c < GPQ_SPLIT_CMAX)
+  unsigned nwide = 0;                 // leading limbs with c < GPQ_WIDE_CMAX (<= nsplit): forward stages as ct_bfly_wide
   bool bridge_mfma = true;            // matrix-core decompose / CRT (gpq_set_bridge_mfma(ctx, 0): the integer-VALU kernels)
-  unsigned char *d_redo = nullptr;    // per-coefficient "redo exactly" flags of the fast CRT path
-  size_t redo_cap = 0;
-  std::vector<void *> retired;        // outgrown d_redo buffers: a HIP graph captured earlier may still write them, so they live as long as the context
-  unsigned *d_wave_any = nullptr;     // one word per wave of the last bridge_stream.hpp launch: did it flag a coefficient (FlagScope)
   bool lazy_decompose = true;         // gpq_he_mul's own rns_decompose output in (0, 3p): the forward transforms take it (gpq_set_lazy_decompose)
   unsigned debug_force_redo = 0;      // tests (gpq_debug_force_redo)
   int nt_mode = -1;                   // slab traffic of the transform kernels with the nt cache policy: -1 by working set (nt_for), 0 never, 1 always
@@ -137,6 +189,28 @@ struct gpq_ctx {
   bool fuse_tail = false;             // gpq_set_fused_tail(ctx, 1): the relinearisation tail in one pass per coefficient (bridge_relin_tail_mfma) -- measured 2 % SLOWER
                                       // than the two-kernel form on the whole he_mul (profiles/r03/v3_fused_tail_ab.txt: both are bound by integer VALU work, not by the
                                       // 60 words per coefficient the fusion saves), kept for the parity tests and as the record of the attempt
+};
+
+// Every device allocation, stream and event below is an owner: `delete` releases all a context holds, in any order.
+struct gpq_ctx {
+  int device = 0;
+  unsigned logn = 0, n = 0, nprimes = 0;
+  gpq_settings set;
+  // host copies in the reference's own representation (struct rns_ctx, src/poly.h:28-41)
+  std::vector<uint64_t> p, pinv_mont, pinv_barr, ninv_mont, psi;
+  std::vector<uint64_t> zetas, zetas_inv;  // [nprimes][n], Montgomery form, bit-reversed index
+  std::shared_ptr<gpq_table_cache> cache;  // the read-only tables: the transform tables and the lazily built bridge constants
+  bool tables_borrowed = false;            // a peer lane: the cache is its parent's too (gpq_debug_table_bytes counts it once, for the parent)
+  // the cache's transform tables, not owned
+  const uint64_t *d_w = nullptr, *d_winv = nullptr;
+  const gpq::TwS *d_ws = nullptr, *d_winvs = nullptr;
+  const gpq::LimbTab *d_tabs = nullptr;
+  unsigned nsplit_tables = 0;                     // for how many limbs the split pair tables exist (gpq_set_limb_classes can only lower nsplit)
+  bool low9 = false;                              // n = 2^17: strided passes over 512-coefficient rows, 9 low stages (Lane8<9>)
+  unsigned nwide_max = 0;                         // the most set.nwide may be
+  gpq_dev<unsigned char> d_redo;      // per-coefficient "redo exactly" flags of the fast CRT path (its capacity: d_redo.bytes)
+  std::vector<gpq_dev<void>> retired; // outgrown scratch (gpq_dev::grow): a HIP graph captured earlier may still use it, so it lives as long as the context
+  gpq_dev<unsigned> d_wave_any;       // one word per wave of the last bridge_stream.hpp launch: did it flag a coefficient (FlagScope)
   // gpq_he_mul / gpq_he_swk over more than one launch group: every other group runs on a second stream through a PEER context (the parent's
   // read-only tables; its own scratch and flag words: nothing mutable is shared), so that the HBM-bound bridge kernels of one group run beside the issue-bound transforms
   // of the other and launch tails fill (gpq_set_overlap; bridge.hip: peer_lane).  The caller's stream orders the whole call as before.
@@ -146,21 +220,19 @@ struct gpq_ctx {
   int debug_peer_fail = 0;            // tests (gpq_debug_fail_peer): 1 = the next attempt to create the peer fails as an allocation would, 2 = the next workspace allocation does
   unsigned last_lanes = 1;            // lanes the last multi-group entry point ran on (gpq_last_lanes)
   std::set<unsigned long long> peer_warm;   // call shapes the peer has run outside a stream capture (gpq_lane_key)
-  gpq_ctx *peer = nullptr;
-  hipStream_t peer_stream = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  void *peer_ws = nullptr;
-  size_t peer_ws_bytes = 0;
-  unsigned *d_zflag = nullptr;        // per-(polynomial, limb) "output contains a residue 0" flags of gpq_ntt (tables.hpp); zero between calls
-  size_t zflag_cap = 0;
+  gpq_ctx *peer = nullptr;            // (gpq_ctx_destroy)
+  gpq_stream_own peer_stream;
+  gpq_event ev_fork, ev_join;
+  gpq_dev<void> peer_ws;
+  gpq_dev<unsigned> d_zflag;          // per-(polynomial, limb) "output contains a residue 0" flags of gpq_ntt (tables.hpp); zero between calls
   // gpq_debug_zero_watch: copies of the flag words of gpq_ntt's LAST launch group as the forward kernels left them (before ref_zero_redo) and
   // as ref_zero_redo left them (after), taken on the launch stream; [0, zwatch_cap) before, [zwatch_cap, 2 zwatch_cap) after
-  unsigned *d_zwatch = nullptr;
+  gpq_dev<unsigned> d_zwatch;
   size_t zwatch_cap = 0, zwatch_count = 0;
   // profiling
   bool prof_on = false;
   std::vector<gpq_prof_rec> prof;     // launches recorded since the last reset
-  std::vector<hipEvent_t> prof_pool;  // recycled events
+  std::vector<gpq_event> prof_pool;   // recycled events
 };
 
 // Makes `device` current for a scope and puts the caller's device back afterwards (context creation must not leave
@@ -170,6 +242,40 @@ struct DeviceScope {
   explicit DeviceScope(int device) { if (hipGetDevice(&prev) != hipSuccess) prev = -1; (void)hipSetDevice(device); }
   ~DeviceScope() { if (prev >= 0) (void)hipSetDevice(prev); }
 };
+
+template <typename T>
+template <typename U>
+int gpq_dev<T>::upload(gpq_ctx *c, const std::vector<U> &v) {
+  DeviceScope on_device(c->device);
+  hipError_t e = alloc(v.size() * sizeof(U));
+  if (e == hipSuccess) {
+    counted = &c->cache->device_bytes; *counted += bytes;
+    e = hipMemcpy(p, v.data(), bytes, hipMemcpyHostToDevice);
+  }
+  if (e == hipSuccess) return GPQ_OK;
+  reset();
+  return gpq_fail(GPQ_ERR_HIP, "uploading a table of %zu bytes: %s", v.size() * sizeof(U), hipGetErrorString(e));
+}
+template <typename T>
+void gpq_dev<T>::retire(gpq_ctx *c) {
+  if (!p) return;
+  gpq_dev<void> old;
+  old.p = p; old.bytes = bytes; old.counted = counted;
+  p = nullptr; bytes = 0; counted = nullptr;
+  c->retired.push_back(std::move(old));
+}
+template <typename T>
+int gpq_dev<T>::grow(gpq_ctx *c, hipStream_t s, size_t nbytes, bool zero_on_stream, const char *refusal) {
+  if (gpq_capturing(s)) return gpq_fail(GPQ_ERR_INVALID, "%s", refusal);
+  DeviceScope on_device(c->device);
+  gpq_dev fresh;
+  hipError_t e = fresh.alloc(nbytes);
+  if (e == hipSuccess && zero_on_stream) e = hipMemsetAsync(fresh.p, 0, nbytes, s);
+  if (e != hipSuccess) return gpq_fail(GPQ_ERR_HIP, "scratch of %zu bytes: %s", nbytes, hipGetErrorString(e));
+  retire(c);
+  *this = std::move(fresh);
+  return GPQ_OK;
+}
 
 // roctx range around a stage of the path (tracing).  The marker library is looked up at run time
 // (librocprofiler-sdk-roctx / libroctx64, normally brought in by rocprofv3 --marker-trace); without it a range costs one
@@ -188,31 +294,37 @@ struct ProfScope {
   gpq_ctx *c; hipStream_t s; gpq_prof_rec r; bool on;
   ProfScope(const gpq_ctx *cc, int kernel, hipStream_t st) : c(const_cast<gpq_ctx *>(cc)), s(st), on(cc->prof_on) {
     if (!on) return;
-    auto get = [&]() { hipEvent_t e; if (!c->prof_pool.empty()) { e = c->prof_pool.back(); c->prof_pool.pop_back(); } else (void)hipEventCreate(&e); return e; };
+    auto get = [&]() { gpq_event e; if (!c->prof_pool.empty()) { e = std::move(c->prof_pool.back()); c->prof_pool.pop_back(); } else (void)hipEventCreate(&e.h); return e; };
     r.kernel = kernel; r.a = get(); r.b = get();
     (void)hipEventRecord(r.a, s);
   }
   ~ProfScope() {
     if (!on) return;
     (void)hipEventRecord(r.b, s);
-    c->prof.push_back(r);
+    c->prof.push_back(std::move(r));
   }
   ProfScope(const ProfScope &) = delete;
   ProfScope &operator=(const ProfScope &) = delete;
 };
 
-int gpq_fail(int code, const char *fmt, ...);
 // A second context over the same primes for the peer lane: every read-only device table (twiddles, split pairs, LimbTab, the bridge's constant
-// cache) is the parent's, borrowed; its own are only the mutable words (zero flags, redo flags, wave words, scratch).  Default settings, no peer of
-// its own; must be destroyed before the parent (gpq_ctx_destroy does).
+// cache) is the parent's, shared (gpq_table_cache); its own are only the mutable words (zero flags, redo flags, wave words, scratch).  Default settings, no
+// peer of its own.
 int gpq_ctx_clone(const gpq_ctx *c, gpq_ctx **out);
 // Hoisted rotations (engine.hip; bridge.hip's gpq_he_rot_hoisted): the complete forward transform of `polys` polynomials of `dim` limbs
 // in place (slab[k][d][i], canonical in [0, p], no zero watch: only products with a key read it), and the key switch of one rotation
-// from it: c0 = invntt(X o sigma_g (*) evk0), c1 = invntt(X o sigma_g (*) evk1), with the inverse tables the context's ScaledInverse
-// selects.  `workspace`: gpq_keyswitch_workspace_bytes(c, dim, polys) (single-pass rings only).
+// from it: c0 = invntt(X o sigma_g (*) evk0), c1 = invntt(X o sigma_g (*) evk1), the inverse pass reading `inv_tabs`.
+// `workspace`: gpq_keyswitch_workspace_bytes(c, dim, polys) (single-pass rings only).
 int gpq_hoist_forward(gpq_ctx *c, uint64_t *slab, unsigned dim, unsigned polys, hipStream_t s);
 int gpq_keyswitch_rotated(gpq_ctx *c, uint64_t *c0, uint64_t *c1, const uint64_t *X, const uint64_t *evk0, const uint64_t *evk1,
-                          unsigned dim, unsigned polys, unsigned g, void *workspace, hipStream_t s);
+                          unsigned dim, unsigned polys, unsigned g, void *workspace, hipStream_t s, const gpq::LimbTab *inv_tabs);
+// gpq_he_mul_tensor / gpq_keyswitch with the per-limb table their inverse strided pass reads as an argument: nullptr = the context's own; else
+// the same table with n^-1 (and winv[1] n^-1) multiplied by a CRT weight, so that the limbs leave the transform already scaled for the
+// reconstruction that follows (bridge_tables.hpp: get_scaled_tabs).  A call that is handed such a table takes no lane of its own.
+int gpq_he_mul_tensor_scaled(gpq_ctx *c, uint64_t *d0, uint64_t *d1, uint64_t *d2, const uint64_t *a0, const uint64_t *a1, const uint64_t *b0,
+                             const uint64_t *b1, unsigned dim, unsigned batch, void *workspace, void *stream, const gpq::LimbTab *inv_tabs);
+int gpq_keyswitch_scaled(gpq_ctx *c, uint64_t *c0, uint64_t *c1, const uint64_t *x, const uint64_t *evk0, const uint64_t *evk1, unsigned dim,
+                         unsigned batch, void *workspace, void *stream, const gpq::LimbTab *inv_tabs);
 // Planned he_gemv (engine.hip; bridge.hip's gpq_gemv_inner): acc0 / acc1[polys][dim][n] = the sums over `nterms` (rotation slot, diagonal)
 // pairs (device array) of r0 / r1[slot][polys][dim][n] (*) diag[diagonal][dim][n], all in the NTT domain; canonical output, ONE launch.
 int gpq_gemv_mac(gpq_ctx *c, uint64_t *acc0, uint64_t *acc1, const uint64_t *r0, const uint64_t *r1, const uint64_t *diag,
@@ -220,13 +332,6 @@ int gpq_gemv_mac(gpq_ctx *c, uint64_t *acc0, uint64_t *acc1, const uint64_t *r0,
 // gpq_he_dec (bridge.hip): r[k] = x[k] (*) key for `polys` polynomials of `dim` limbs and ONE key slab uint64_t[dim][n] shared by all of them
 // (pointwise<true, true>: the second operand is read without the polynomial's offset); r may alias x.
 int gpq_rns_mul_shared(gpq_ctx *c, uint64_t *r, const uint64_t *x, const uint64_t *key, unsigned dim, unsigned polys, hipStream_t s);
-// hipMalloc of a read-only table, accounted in the context's table cache (gpq_debug_table_bytes)
-inline hipError_t gpq_table_malloc(gpq_ctx *c, void **p, size_t bytes) {
-  hipError_t e = hipMalloc(p, bytes);
-  if (e == hipSuccess && c->cache) c->cache->device_bytes += bytes;
-  return e;
-}
-void gpq_bridge_release(gpq_ctx *c);
 
 // Launches a kernel whose dynamic LDS may exceed 64 KB.  That needs the function attribute (ceiling `lds_max`), set once per (kernel, device):
 // per kernel through the template argument -- one flag array per kernel address -- and per device through the calling thread's current one.
@@ -270,12 +375,6 @@ struct PeerLane {
   inline int join();
   ~PeerLane() { (void)join(); }
 };
-inline void gpq_mirror_settings(gpq_ctx *q, const gpq_ctx *c) {   // whatever decides which kernels a call runs: the peer follows the context it serves
-  q->chunk = c->chunk; q->limb_block = c->limb_block; q->nsplit = c->nsplit; q->nwide = c->nwide;
-  q->bridge_mfma = c->bridge_mfma; q->lazy_decompose = c->lazy_decompose; q->debug_force_redo = c->debug_force_redo; q->nt_mode = c->nt_mode;
-  q->stream_bridge = c->stream_bridge; q->exact_crt = c->exact_crt; q->prescale = c->prescale; q->prescale_upper = c->prescale_upper;
-  q->tail_direct = c->tail_direct; q->fuse_tail = c->fuse_tail;
-}
 // What gpq_set_overlap(ctx, -1) -- the default -- allows the peer's per-group workspace to cost.  Two lanes pay through launch tails, so the gain
 // shrinks as the kernels of a group grow: +10-15 % at the reference's default shape (logn 14: 0.1 GB per group) on every device measured,
 // +0.15 ... +3.9 % by device at the headline shape (5.6 GB per group), +1.6 % for he_swk at n = 2^17 (7 GB); never a loss (profiles/r04/v13_two_lanes_ab.txt,
@@ -288,10 +387,10 @@ constexpr size_t kPeerAutoWorkspaceBytes = (size_t)16 << 30;
 // WORKSPACE that cannot be allocated declines shapes of that size only.
 template <typename Bytes>
 int gpq_peer_lane(gpq_ctx *c, hipStream_t s, unsigned long long key, Bytes bytes, PeerLane *lane) {
-  if (c->overlap == 0 || c->peer_failed || c->prof_on || c->inv_tabs_override) return GPQ_OK;
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(s, &cap) != hipSuccess) { (void)hipGetLastError(); return GPQ_OK; }
-  const bool capturing = cap != hipStreamCaptureStatusNone;
+  if (c->overlap == 0 || c->peer_failed || c->prof_on) return GPQ_OK;
+  bool query_failed = false;
+  const bool capturing = gpq_capturing(s, &query_failed);
+  if (query_failed) { (void)hipGetLastError(); return GPQ_OK; }
   if (capturing && (!c->peer || !c->peer_warm.count(key))) return GPQ_OK;     // (before bytes(): sizing a new shape may build tables, which allocates)
   // The price first, on the context itself (the peer runs the same settings over the same tables): a shape the auto mode declines, or one whose
   // workspace already failed to allocate, never creates the peer and costs nothing.
@@ -307,23 +406,23 @@ int gpq_peer_lane(gpq_ctx *c, hipStream_t s, unsigned long long key, Bytes bytes
   };
   if (!c->peer) {
     if (c->debug_peer_fail == 1) return give_up("gpq_debug_fail_peer");
-    if (!c->peer_stream && hipStreamCreateWithFlags(&c->peer_stream, hipStreamNonBlocking) != hipSuccess) return give_up("hipStreamCreateWithFlags");
-    if (!c->ev_fork && hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess) return give_up("hipEventCreateWithFlags");
-    if (!c->ev_join && hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess) return give_up("hipEventCreateWithFlags");
+    if (!c->peer_stream && hipStreamCreateWithFlags(&c->peer_stream.h, hipStreamNonBlocking) != hipSuccess) return give_up("hipStreamCreateWithFlags");
+    if (!c->ev_fork && hipEventCreateWithFlags(&c->ev_fork.h, hipEventDisableTiming) != hipSuccess) return give_up("hipEventCreateWithFlags");
+    if (!c->ev_join && hipEventCreateWithFlags(&c->ev_join.h, hipEventDisableTiming) != hipSuccess) return give_up("hipEventCreateWithFlags");
     if (gpq_ctx_clone(c, &c->peer) != GPQ_OK) { c->peer = nullptr; return give_up("peer context"); }   // last: a context with a peer has its stream and events
   }
-  gpq_mirror_settings(c->peer, c);
-  if (need > c->peer_ws_bytes) {
+  c->peer->set = c->set;                                                     // the peer follows the context it serves (gpq_settings)
+  if (need > c->peer_ws.bytes) {
     if (capturing) return GPQ_OK;
-    void *fresh = nullptr;
-    if (c->debug_peer_fail == 2 || hipMalloc(&fresh, need) != hipSuccess) {   // this shape only: smaller ones keep their second lane, nothing else is given up
+    gpq_dev<void> fresh;
+    if (c->debug_peer_fail == 2 || fresh.alloc(need) != hipSuccess) {         // this shape only: smaller ones keep their second lane, nothing else is given up
       (void)hipGetLastError();
       c->peer_ws_declined = need;
       fprintf(stderr, "gpqhe_hip: no room for a second lane's workspace of %zu bytes: shapes of this size run on one lane\n", need);
       return GPQ_OK;
     }
-    if (c->peer_ws) c->retired.push_back(c->peer_ws);             // a graph captured earlier may still use it
-    c->peer_ws = fresh; c->peer_ws_bytes = need;
+    c->peer_ws.retire(c);                                         // a graph captured earlier may still use it
+    c->peer_ws = std::move(fresh);
   }
   hipError_t e = hipEventRecord(c->ev_fork, s);
   if (e == hipSuccess) e = hipStreamWaitEvent(c->peer_stream, c->ev_fork, 0);
@@ -340,7 +439,7 @@ inline int PeerLane::join() {
   return e == hipSuccess ? (int)GPQ_OK : gpq_fail(GPQ_ERR_HIP, "joining the peer stream: %s", hipGetErrorString(e));
 }
 // Polynomials (ciphertexts) per launch group of the multi-group entry points
-inline unsigned gpq_group_size(const gpq_ctx *c, unsigned batch) { return batch < c->chunk ? batch : c->chunk; }
+inline unsigned gpq_group_size(const gpq_ctx *c, unsigned batch) { return batch < c->set.chunk ? batch : c->set.chunk; }
 // The launch groups of a two-lane entry point: `batch` items in groups of `chunk` (gpq_group_size), every other group on the peer when the
 // call gets a lane (gpq_peer_lane with the call's `key` and `bytes`).  own(k0, count) runs a group on the caller's context and stream;
 // peer(lane, k0, count) is the SAME entry point on lane.c with lane.ws and lane.s for that group's slice of the batch -- with that entry's

@@ -13,11 +13,11 @@ struct gpq_gemv_plan {
   gpq_ctx *ctx = nullptr;
   unsigned slots = 0, n1 = 0, n2 = 0, logql = 0, dimpt = 0, dim = 0, diag_bits = 0, live = 0;
   int exact = 0;
-  uint64_t *d_hat = nullptr;            // [slots][dim][n], NTT domain, words in [0, p]
+  gpq_dev<uint64_t> d_hat;              // [slots][dim][n], NTT domain, words in [0, p]
   size_t bytes = 0;
   // (rotation slot, diagonal) of the live terms of giant step i at [i * n1 ...): slot = j for gpq_gemv_inner (`full`), slot = the rank of j
   // among the live baby rotations for gpq_he_gemv_planned (`packed`)
-  uint2 *d_full = nullptr, *d_packed = nullptr;
+  gpq_dev<uint2> d_full, d_packed;
   std::vector<unsigned> nterms;         // per giant step
   std::vector<unsigned> baby;           // live baby rotations, ascending
   std::vector<unsigned char> live_diag; // per diagonal
@@ -55,9 +55,6 @@ extern "C" unsigned gpq_gemv_acc_dim(unsigned logql, unsigned diag_bits, unsigne
 extern "C" void gpq_gemv_plan_destroy(gpq_gemv_plan *p) {
   if (!p) return;
   DeviceScope on_device(p->ctx->device);
-  if (p->d_hat) (void)hipFree(p->d_hat);
-  if (p->d_full) (void)hipFree(p->d_full);
-  if (p->d_packed) (void)hipFree(p->d_packed);
   delete p;
 }
 
@@ -86,8 +83,7 @@ extern "C" int gpq_gemv_plan_create(gpq_ctx *c, gpq_gemv_plan **out, const uint6
   if (rc) return rc;
   if (!out || !diag || !logql || W < 1 || W > 32) return gpq_fail(GPQ_ERR_INVALID, "gpq_gemv_plan_create: bad arguments");
   hipStream_t s = (hipStream_t)stream;
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
+  if (gpq_capturing(s))
     return gpq_fail(GPQ_ERR_INVALID, "gpq_gemv_plan_create allocates and waits for the stream: not inside a stream capture");
   std::unique_ptr<gpq_gemv_plan, void (*)(gpq_gemv_plan *)> p(new (std::nothrow) gpq_gemv_plan(), gpq_gemv_plan_destroy);
   if (!p) return gpq_fail(GPQ_ERR_NOMEM, "out of host memory");
@@ -96,8 +92,8 @@ extern "C" int gpq_gemv_plan_create(gpq_ctx *c, gpq_gemv_plan **out, const uint6
   // the largest coefficient of every diagonal, on the device
   std::vector<unsigned> bits(slots, 0);
   {
-    unsigned *d_bits = nullptr;
-    HIP_TRY(hipMalloc((void **)&d_bits, slots * sizeof(unsigned)));
+    gpq_dev<unsigned> d_bits;
+    HIP_TRY(d_bits.alloc(slots * sizeof(unsigned)));
     hipError_t e = hipMemsetAsync(d_bits, 0, slots * sizeof(unsigned), s);
     for (unsigned k0 = 0; k0 < slots && e == hipSuccess; k0 += 65535) {
       const unsigned cnt = slots - k0 < 65535 ? slots - k0 : 65535u;
@@ -107,7 +103,6 @@ extern "C" int gpq_gemv_plan_create(gpq_ctx *c, gpq_gemv_plan **out, const uint6
     }
     if (e == hipSuccess) e = hipMemcpyAsync(bits.data(), d_bits, slots * sizeof(unsigned), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(d_bits);
     if (e != hipSuccess) return gpq_fail(GPQ_ERR_HIP, "gpq_gemv_plan_create: measuring the diagonals: %s", hipGetErrorString(e));
   }
   p->live_diag.resize(slots);
@@ -138,20 +133,20 @@ extern "C" int gpq_gemv_plan_create(gpq_ctx *c, gpq_gemv_plan **out, const uint6
       }
   if (!p->exact) { *out = p.release(); return GPQ_OK; }            // holds nothing: the entry points refuse it
   DeviceScope on_device(c->device);
-  HIP_TRY(hipMalloc((void **)&p->d_full, full.size() * sizeof(uint2)));
-  HIP_TRY(hipMalloc((void **)&p->d_packed, full.size() * sizeof(uint2)));
+  HIP_TRY(p->d_full.alloc(full.size() * sizeof(uint2)));
+  HIP_TRY(p->d_packed.alloc(full.size() * sizeof(uint2)));
   HIP_TRY(hipMemcpy(p->d_full, full.data(), full.size() * sizeof(uint2), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(p->d_packed, packed.data(), full.size() * sizeof(uint2), hipMemcpyHostToDevice));
   const size_t poly = (size_t)p->dim * c->n;
   p->bytes = (size_t)slots * poly * 8;
-  if (hipMalloc((void **)&p->d_hat, p->bytes) != hipSuccess) {
+  if (p->d_hat.alloc(p->bytes) != hipSuccess) {
     (void)hipGetLastError();
     return gpq_fail(GPQ_ERR_NOMEM, "gpq_gemv_plan_create: no room for %zu bytes of transformed diagonals", p->bytes);
   }
   {
     StageRange stage("gpq_gemv_plan_create: rns_decompose + forward transform of the diagonals");
-    for (unsigned k0 = 0; k0 < slots; k0 += c->chunk) {               // (zero diagonals too: their words are never read, but stay defined)
-      const unsigned cnt = slots - k0 < c->chunk ? slots - k0 : c->chunk;
+    for (unsigned k0 = 0; k0 < slots; k0 += c->set.chunk) {               // (zero diagonals too: their words are never read, but stay defined)
+      const unsigned cnt = slots - k0 < c->set.chunk ? slots - k0 : c->set.chunk;
       if ((rc = launch_decompose(c, p->d_hat + k0 * poly, diag + (size_t)k0 * W * c->n, W, 0, p->dim, cnt, s))) return rc;
       if ((rc = gpq_hoist_forward(c, p->d_hat + k0 * poly, p->dim, cnt, s))) return rc;
     }
@@ -163,7 +158,7 @@ extern "C" int gpq_gemv_plan_create(gpq_ctx *c, gpq_gemv_plan **out, const uint6
 
 extern "C" size_t gpq_gemv_inner_workspace_bytes(gpq_ctx *c, const gpq_gemv_plan *p, unsigned batch) {
   if (!c || !p || !batch) return 0;
-  const unsigned m = batch < c->chunk ? batch : c->chunk;
+  const unsigned m = batch < c->set.chunk ? batch : c->set.chunk;
   const size_t slab = (size_t)m * p->dim * c->n * 8;
   return align64(2 * p->n1 * slab) + align64(2 * slab);
 }
@@ -185,7 +180,7 @@ extern "C" int gpq_gemv_inner(gpq_ctx *c, uint64_t *out_c0, uint64_t *out_c1, co
     HIP_TRY(hipMemsetAsync(out_c1, 0, out_words * 8, s));
     return GPQ_OK;
   }
-  const unsigned m = batch < c->chunk ? batch : c->chunk;
+  const unsigned m = batch < c->set.chunk ? batch : c->set.chunk;
   const size_t group_slab = (size_t)m * p->dim * n;
   uint64_t *hat = (uint64_t *)workspace, *acc = (uint64_t *)((char *)workspace + align64(2 * p->n1 * group_slab * 8));
   for (unsigned k0 = 0; k0 < batch; k0 += m) {
@@ -232,7 +227,7 @@ int planned_layout(gpq_ctx *c, const gpq_gemv_plan *p, unsigned W, unsigned dimB
 extern "C" size_t gpq_he_gemv_planned_workspace_bytes(gpq_ctx *c, const gpq_gemv_plan *p, unsigned W, unsigned dimB, unsigned dimP, unsigned batch) {
   if (!c || !p || !batch || !W) return 0;
   PlannedLayout l;
-  return planned_layout(c, p, W, dimB, dimP, batch < c->chunk ? batch : c->chunk, &l) == GPQ_OK ? l.total : 0;
+  return planned_layout(c, p, W, dimB, dimP, batch < c->set.chunk ? batch : c->set.chunk, &l) == GPQ_OK ? l.total : 0;
 }
 
 extern "C" int gpq_he_gemv_planned(gpq_ctx *c, uint64_t *out_c0, uint64_t *out_c1, const uint64_t *c0, const uint64_t *c1, const gpq_gemv_plan *p,
@@ -256,7 +251,7 @@ extern "C" int gpq_he_gemv_planned(gpq_ctx *c, uint64_t *out_c0, uint64_t *out_c
   for (unsigned i = 0; i < p->n2; ++i)
     if (p->nterms[i] && (!rk0[i * n1] || !rk1[i * n1])) return gpq_fail(GPQ_ERR_INVALID, "gpq_he_gemv_planned: key %u is NULL (a live giant rotation)", i * n1);
   hipStream_t s = (hipStream_t)stream;
-  const unsigned m = batch < c->chunk ? batch : c->chunk;
+  const unsigned m = batch < c->set.chunk ? batch : c->set.chunk;
   PlannedLayout l;
   if (planned_layout(c, p, W, dimB, dimP, m, &l)) return gpq_fail(GPQ_ERR_INVALID, "gpq_he_gemv_planned: unsupported shape");
   char *w = (char *)workspace;
