@@ -122,6 +122,9 @@ SIGNATURES = {
     "gpq_evk_pack": (C.c_int, [vp, vp, vp, C.c_uint, C.c_uint, C.c_uint, vp]),
     "gpq_he_genswk_workspace_bytes": (C.c_size_t, [vp, C.c_uint, C.c_uint, C.c_uint]),
     "gpq_he_genswk": (C.c_int, [vp] * 7 + [C.c_uint] * 4 + [vp, vp]),
+    "gpq_he_genswk_batch_workspace_bytes": (C.c_size_t, [vp] + [C.c_uint] * 5),
+    "gpq_he_genswk_batch": (C.c_int, [vp] * 9 + [C.c_uint] * 6 + [vp, vp]),
+    "gpq_he_genswk_dimmul": (C.c_uint, [vp, C.c_uint, C.c_uint]),
     "gpq_he_swk_workspace_bytes": (C.c_size_t, [vp, C.c_uint, C.c_uint, C.c_uint, C.c_uint]),
     "gpq_he_swk": (C.c_int, [vp] * 7 + [C.c_uint] * 5 + [vp, vp]),
     "gpq_automorphism_index": (C.c_int, [C.c_uint, u64, vp]),

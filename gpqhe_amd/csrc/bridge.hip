@@ -6,6 +6,7 @@
 #include "bridge_kernels.hpp"
 #include "bridge_mfma.hpp"
 #include "bridge_stream.hpp"
+#include "genswk_kernels.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -815,3 +816,5 @@ extern "C" int gpq_he_genswk(gpq_ctx *c, uint64_t *evk0, uint64_t *evk1, const u
   if ((rc = gpq_evk_pack(c, evk0, p0, W, dimevk, 1, stream)) || (rc = gpq_evk_pack(c, evk1, p1c, W, dimevk, 1, stream))) return rc;   // :103-110
   return launched("gpq_he_genswk");
 }
+
+#include "bridge_genswk.hpp"   // gpq_he_genswk_batch: `count` keys per call through the CRT split of P 2^k (genswk_crt_tail)

@@ -92,7 +92,9 @@ enum { GPQ_K_STRIDED_FWD = 0, GPQ_K_STRIDED_INV, GPQ_K_CONTIG_FWD, GPQ_K_CONTIG_
        // he_dcd on the device: one workgroup per plaintext (he_dcd_lds, dcd_kernels.hpp)
        GPQ_K_DCD,
        // samplers and encryption on the device (enc_kernels.hpp): the byte-fed samplers; small_to_rns_k / small_to_big_k / enc_tail_k
-       GPQ_K_SAMPLE, GPQ_K_ENC, GPQ_K_COUNT };
+       GPQ_K_SAMPLE, GPQ_K_ENC,
+       // gpq_he_genswk_batch: the CRT recombination of a switching key mod P 2^k (genswk_crt_tail, genswk_kernels.hpp)
+       GPQ_K_GENSWK_TAIL, GPQ_K_COUNT };
 
 // Constant matrix of the matrix-core CRT fast path for one basis and result width WL (bridge_mfma.hpp)
 struct gpq_recon_mfma {
@@ -145,6 +147,14 @@ struct gpq_relin_tables {
   gpq_dev<uint64_t> d_scale, d_unscale;
 };
 
+// Constants of gpq_he_genswk_batch for one (dimP, logqL): P, P^-1 mod 2^(64 W2), M = P 2^logqL, floor(M/2), M + floor(M/2) in ONE device block
+// (bridge_genswk.hpp)
+struct gpq_genswk_tables {
+  gpq_dev<uint64_t> d_const;
+  unsigned WPw = 0, W2 = 0, LM = 0, nbits = 0, dimmul = 0;   // words of P, of 2^logqL, of the three multiples of M; bits of M; src/he-kem.c:83
+  const uint64_t *P = nullptr, *Pinv = nullptr, *M = nullptr, *Mh = nullptr, *M3h = nullptr;   // into d_const
+};
+
 // Everything a context builds once and only reads afterwards on the device: the transform tables of upload_tables (engine.hip) and the bridge
 // constants bridge_tables.hpp builds at first use.  ONE object per prime chain, held through a shared_ptr: a context's peer lane (gpq_ctx_clone)
 // shares its parent's, so the second lane costs no table memory, no table-building time, "the peer's tables differ" is not a state the library
@@ -163,6 +173,7 @@ struct gpq_table_cache {
   std::map<std::pair<unsigned, unsigned>, gpq_relin_tables> relins;  // by (dimP, dimB)
   std::map<std::pair<std::pair<unsigned, unsigned>, unsigned>, gpq_decomp_mfma> decomps;  // by ((first limb, limbs), W)
   gpq_dev<uint16_t> d_error_table;    // gpq_sample_error's 65536 coefficient pairs (enc.hip), uploaded at first use
+  std::map<std::pair<unsigned, unsigned>, gpq_genswk_tables> genswk;  // by (dimP, logqL)
   // Scaled per-limb tables (get_scaled_tabs, get_relin_front) one of whose split pairs fails the wide class's table check (modarith.hpp:
   // split_entry_fits_wide), with the first such limb: a context that reads the table runs that limb and those after it in the split class
   // (bridge_tables.hpp: apply_scaled_wide_limit).  Empty for every chain met so far (the failing constants are ~100 values in 2^59).

@@ -3,97 +3,165 @@
 #pragma once
 
 // ---- key generation, src/he-kem.c:74-170 -----------------------------------------------------------------------------
-// he_genswk (static in the reference, :74-118) with the hidden polynomial given as a host big slab of W words.  The reference's
-// samplers are called in its order (error, then uniform mod P q_L), so a seeded RNG gives the reference's own keys.
-static void genswk(he_evk_t *swk, const std::vector<uint64_t> &sp, const std::vector<uint64_t> &hs, unsigned W) {
-  SHIM_CALL();
-  forget_key_at(swk->p0.coeffs, swk->p1.coeffs);         // the host key is about to be rewritten: its device copy (if any) goes first
-  if (!sample_error || !sample_uniform) die("he_gen*k: the host program does not provide sample_error / sample_uniform (src/sample.c)");
-  gpq_ctx *c = engine();
-  const unsigned n = polyctx.n;
-  poly_mpi_t e, p1;
-  e.coeffs = (gpq_MPI *)malloc(n * sizeof(gpq_MPI));
-  p1.coeffs = (gpq_MPI *)malloc(n * sizeof(gpq_MPI));
-  for (unsigned i = 0; i < n; ++i) { e.coeffs[i] = G.mpi_new(0); p1.coeffs[i] = G.mpi_new(0); }
-  sample_error(&e);                                                                               // :87
-  sample_uniform(&p1, hectx.PqL);                                                                 // :94
-  const size_t big = (size_t)W * n, evk = (size_t)hectx.dimevk * n;
-  std::vector<uint64_t> he(big), hp(big);
-  to_slab(he.data(), &e, n, W);
-  to_slab(hp.data(), &p1, n, W);
-  for (unsigned i = 0; i < n; ++i) { G.mpi_release(e.coeffs[i]); G.mpi_release(p1.coeffs[i]); }
-  free(e.coeffs); free(p1.coeffs);
-  const unsigned logqL = G.mpi_get_nbits(hectx.q[hectx.L]) - 1;
-  if (!is_pow2(words_of(hectx.q[hectx.L], "he_gen*k: q_L must be positive"))) die("he_gen*k: q_L must be a power of two on this path");
-  DevBuf dp(big * 8), ds(big * 8), de(big * 8), dsp(big * 8), k0(evk * 8), k1(evk * 8), ws(gpq_he_genswk_workspace_bytes(c, W, hectx.dim, logqL));
-  up(dp, hp); up(ds, hs); up(de, he); up(dsp, sp);
-  if (gpq_he_genswk(c, k0.u64(), k1.u64(), dp.u64(), ds.u64(), de.u64(), dsp.u64(), W, hectx.dim, logqL, hectx.dimevk, ws.p, nullptr) != GPQ_OK)
-    die("he_genswk failed");
-  if (gpq_download(swk->p0.coeffs, k0.p, evk * 8, nullptr) != GPQ_OK || gpq_download(swk->p1.coeffs, k1.p, evk * 8, nullptr) != GPQ_OK ||
-      gpq_stream_sync(nullptr) != GPQ_OK) die("download failed");
-}
+// he_genswk (static in the reference, :74-118) for `count` keys through gpq_he_genswk_batch.  The secret is converted and packed ONCE per
+// he_gen*k call (an int8 small slab for the kernel's gather, gpq_evk_pack over the product's limbs); keys are made in groups of at most
+// kKeygenGroup, so host memory stays bounded, with two downloads per group.  The samplers are the host program's, in the reference's order
+// per key -- sample_error, then sample_uniform(P q_L) -- so a seeded RNG gives the reference's own keys; with
+// gpq_mpi_shim_set_device_samplers(1) the host's randombytes is called instead, once per sampler call with the reference's byte counts
+// (n, then n (nbits/8 + 1)), and gpq_sample_error / gpq_sample_uniform expand the group's byte buffer on the device, one launch per key
+// slice: no sampled polynomial becomes libgcrypt integers.
+} // extern "C"
+namespace {
+constexpr unsigned kKeygenGroup = 32;                       // the engine's default launch group (gpq_set_chunk)
 
-static unsigned keygen_words() {
-  SHIM_CALL();
+struct KeygenSecret {                                       // what every key of a call shares
+  unsigned W = 0, Wsk = 0, dimmul = 0, logqL = 0, nbits = 0;
+  bool small = false;                                       // every coefficient fits int8: the kernel gathers the hidden polynomial itself
+  std::unique_ptr<DevBuf> big, ntt, i8;
+};
+
+void keygen_secret(KeygenSecret &k, const poly_mpi_t *sk) {
   need_gcrypt();
   if (&hectx == nullptr || !hectx.q) die("`hectx` is not initialised (hectx_init first)");
-  return G.mpi_get_nbits(hectx.PqL) / 64 + 1;
+  gpq_ctx *c = engine();
+  const unsigned n = polyctx.n;
+  if (!is_pow2(words_of(hectx.q[hectx.L], "he_gen*k: q_L must be positive"))) die("he_gen*k: q_L must be a power of two on this path");
+  k.logqL = G.mpi_get_nbits(hectx.q[hectx.L]) - 1;
+  k.nbits = G.mpi_get_nbits(hectx.PqL);
+  k.W = k.nbits / 64 + 1;
+  if (!(k.dimmul = gpq_he_genswk_dimmul(c, hectx.dim, k.logqL))) die("he_gen*k: the modulus P q_L is outside what the engine supports");
+  const unsigned bits = max_bits(sk, n);
+  k.small = bits <= 7;
+  k.Wsk = bits / 64 + 1;
+  std::vector<uint64_t> hs((size_t)k.Wsk * n);
+  to_slab(hs.data(), sk, n, k.Wsk);
+  k.big.reset(new DevBuf(hs.size() * 8));
+  k.ntt.reset(new DevBuf((size_t)k.dimmul * n * 8));
+  up(*k.big, hs);
+  if (gpq_evk_pack(c, k.ntt->u64(), k.big->u64(), k.Wsk, k.dimmul, 1, nullptr) != GPQ_OK) die("he_gen*k: packing the secret failed");
+  if (k.small) {
+    std::vector<int8_t> h8(n);
+    for (unsigned i = 0; i < n; ++i) h8[i] = (int8_t)(int64_t)hs[i];
+    k.i8.reset(new DevBuf(n));
+    if (gpq_upload(k.i8->p, h8.data(), n, nullptr) != GPQ_OK) die("upload failed");
+  }
+  if (gpq_stream_sync(nullptr) != GPQ_OK) die("upload failed");                            // (the host vectors go out of scope)
 }
 
-// a permutation of the secret as the hidden polynomial: poly_conj / poly_rot (src/poly.c:263-283) on the device
-static std::vector<uint64_t> permuted(const std::vector<uint64_t> &hs, unsigned W, bool conj, unsigned rot) {
+// keys swk[0..count): the hidden polynomial of key j is the image of the secret under X -> X^galois[j] -- poly_conj (conj) or poly_rot by j --
+// or (galois == nullptr, count == 1) the device big slab sp of Wsp words
+void genswk_keys(he_evk_t *swk, unsigned count, const KeygenSecret &k, const uint64_t *galois, bool conj, const uint64_t *sp, unsigned Wsp) {
+  const bool device = g_device_samplers && randombytes != nullptr;
+  if (!device && (!sample_error || !sample_uniform)) die("he_gen*k: the host program does not provide sample_error / sample_uniform (src/sample.c)");
   gpq_ctx *c = engine();
-  const size_t big = (size_t)W * polyctx.n;
-  DevBuf a(big * 8), r(big * 8);
-  up(a, hs);
-  const int rc = conj ? gpq_poly_conj(c, r.u64(), a.u64(), W, 1, nullptr) : gpq_poly_rot(c, r.u64(), a.u64(), W, rot, 1, nullptr);
-  if (rc != GPQ_OK) die("poly_rot / poly_conj failed");
-  std::vector<uint64_t> out(big);
-  down(out, r);
-  return out;
+  const unsigned n = polyctx.n, W = k.W, dimevk = hectx.dimevk, nb = k.nbits / 8 + 1;
+  const size_t big = (size_t)W * n, evk = (size_t)dimevk * n;
+  for (unsigned k0 = 0; k0 < count; k0 += kKeygenGroup) {
+    const unsigned m = count - k0 < kKeygenGroup ? count - k0 : kKeygenGroup;
+    for (unsigned j = 0; j < m; ++j) forget_key_at(swk[k0 + j].p0.coeffs, swk[k0 + j].p1.coeffs);   // about to be rewritten: their device copies go first
+    DevBuf dp(m * big * 8), de((size_t)m * n), d0(m * evk * 8), d1(m * evk * 8),
+        ws(gpq_he_genswk_batch_workspace_bytes(c, W, hectx.dim, k.logqL, dimevk, m));
+    if (device) {
+      std::vector<uint8_t> bytes((size_t)m * ((size_t)n + (size_t)n * nb));
+      for (unsigned j = 0; j < m; ++j) {
+        uint8_t *at = bytes.data() + (size_t)j * ((size_t)n + (size_t)n * nb);
+        randombytes(at, n);                                                                 // sample_error, :87
+        randombytes(at + n, (size_t)n * nb);                                                // sample_uniform(P q_L), :94
+      }
+      DevBuf db(bytes.size());
+      if (gpq_upload(db.p, bytes.data(), bytes.size(), nullptr) != GPQ_OK) die("upload failed");
+      for (unsigned j = 0; j < m; ++j) {
+        const uint8_t *at = (const uint8_t *)db.p + (size_t)j * ((size_t)n + (size_t)n * nb);
+        if (gpq_sample_error(c, (int8_t *)de.p + (size_t)j * n, at, 1, nullptr) != GPQ_OK ||
+            gpq_sample_uniform(c, dp.u64() + j * big, at + n, k.nbits, W, 1, nullptr) != GPQ_OK) die("he_gen*k: the device sampler failed");
+      }
+      if (gpq_stream_sync(nullptr) != GPQ_OK) die("upload failed");                        // (`bytes` goes out of scope)
+    } else {
+      std::vector<uint64_t> hp(m * big), w(n);
+      std::vector<int8_t> he((size_t)m * n);
+      TmpPoly t(n);
+      for (unsigned j = 0; j < m; ++j) {
+        sample_error(&t.p);                                                                 // :87
+        if (max_bits(&t.p, n) > 7) die("he_gen*k: the host's sample_error gave a coefficient outside [-127, 127]");
+        to_slab(w.data(), &t.p, n, 1);
+        for (unsigned i = 0; i < n; ++i) he[(size_t)j * n + i] = (int8_t)(int64_t)w[i];
+        sample_uniform(&t.p, hectx.PqL);                                                    // :94
+        if (max_bits(&t.p, n) >= 64 * W) die("he_gen*k: the host's sample_uniform gave a coefficient wider than the modulus allows");
+        to_slab(hp.data() + j * big, &t.p, n, W);
+      }
+      up(dp, hp);
+      if (gpq_upload(de.p, he.data(), he.size(), nullptr) != GPQ_OK || gpq_stream_sync(nullptr) != GPQ_OK) die("upload failed");
+    }
+    int rc;
+    if (galois && k.small) {
+      rc = gpq_he_genswk_batch(c, d0.u64(), d1.u64(), dp.u64(), (const int8_t *)de.p, k.ntt->u64(), (const int8_t *)k.i8->p, galois + k0, nullptr, 0, W,
+                               hectx.dim, k.logqL, dimevk, m, ws.p, nullptr);
+    } else if (galois) {                                    // a secret beyond int8: its images as big slabs, permuted on the device
+      const size_t one = (size_t)k.Wsk * n;
+      DevBuf dsp(m * one * 8);
+      for (unsigned j = 0; j < m; ++j)
+        if ((conj ? gpq_poly_conj(c, dsp.u64() + j * one, k.big->u64(), k.Wsk, 1, nullptr)
+                  : gpq_poly_rot(c, dsp.u64() + j * one, k.big->u64(), k.Wsk, k0 + j, 1, nullptr)) != GPQ_OK) die("poly_rot / poly_conj failed");
+      rc = gpq_he_genswk_batch(c, d0.u64(), d1.u64(), dp.u64(), (const int8_t *)de.p, k.ntt->u64(), nullptr, nullptr, dsp.u64(), k.Wsk, W, hectx.dim,
+                               k.logqL, dimevk, m, ws.p, nullptr);
+    } else {
+      rc = gpq_he_genswk_batch(c, d0.u64(), d1.u64(), dp.u64(), (const int8_t *)de.p, k.ntt->u64(), nullptr, nullptr, sp, Wsp, W, hectx.dim, k.logqL,
+                               dimevk, m, ws.p, nullptr);
+    }
+    if (rc != GPQ_OK) die("he_genswk failed");
+    std::vector<uint64_t> h0(m * evk), h1(m * evk);
+    if (gpq_download(h0.data(), d0.p, h0.size() * 8, nullptr) != GPQ_OK || gpq_download(h1.data(), d1.p, h1.size() * 8, nullptr) != GPQ_OK ||
+        gpq_stream_sync(nullptr) != GPQ_OK) die("download failed");
+    for (unsigned j = 0; j < m; ++j) {
+      memcpy(swk[k0 + j].p0.coeffs, h0.data() + j * evk, evk * 8);
+      memcpy(swk[k0 + j].p1.coeffs, h1.data() + j * evk, evk * 8);
+    }
+  }
 }
+}  // namespace
+extern "C" {
 
 void he_genrlk(he_evk_t *rlk, const poly_mpi_t *sk) {                                              // :120-137
   SHIM_CALL();
-  const unsigned W = keygen_words(), n = polyctx.n;
+  KeygenSecret k;
+  keygen_secret(k, sk);
+  const unsigned n = polyctx.n;
   gpq_ctx *c = engine();
   printf("Generating rlk ... ");
   fflush(stdout);
-  std::vector<uint64_t> hs((size_t)W * n), s2((size_t)W * n);
-  to_slab(hs.data(), sk, n, W);
   const unsigned nbq = G.mpi_get_nbits(hectx.q[hectx.L]), dim = nbq / 59 + 1;                      // :131
-  const std::vector<uint64_t> qw = words_of(hectx.q[hectx.L], "he_genrlk: q_L must be positive");
-  {
-    DevBuf a(hs.size() * 8), r(hs.size() * 8), ws(gpq_poly_mul_general_workspace_bytes(c, dim, 1));
-    up(a, hs);
-    const int rc = is_pow2(qw) ? gpq_poly_mul(c, r.u64(), a.u64(), a.u64(), W, dim, nbq - 1, 1, ws.p, nullptr)
-                               : gpq_poly_mul_general(c, r.u64(), a.u64(), a.u64(), W, dim, qw.data(), (unsigned)qw.size(), 1, ws.p, nullptr);
-    if (rc != GPQ_OK) die("he_genrlk: poly_mul failed");
-    down(s2, r);
-  }
-  genswk(rlk, s2, hs, W);                                                                          // :132
+  const unsigned Ws = k.Wsk > nbq / 64 + 1 ? k.Wsk : nbq / 64 + 1;                                  // holds the secret and s^2 centred mod q_L
+  const size_t big = (size_t)Ws * n;
+  DevBuf a(big * 8), r(big * 8), ws(gpq_poly_mul_workspace_bytes(c, dim, 1));
+  std::vector<uint64_t> hs(big);
+  to_slab(hs.data(), sk, n, Ws);
+  up(a, hs);
+  if (gpq_poly_mul(c, r.u64(), a.u64(), a.u64(), Ws, dim, nbq - 1, 1, ws.p, nullptr) != GPQ_OK) die("he_genrlk: poly_mul failed");
+  genswk_keys(rlk, 1, k, nullptr, false, r.u64(), Ws);                                                    // :132
   printf("done.\n");
 }
 
 void he_genck(he_evk_t *ck, const poly_mpi_t *sk) {                                                // :140-154
   SHIM_CALL();
-  const unsigned W = keygen_words(), n = polyctx.n;
+  KeygenSecret k;
+  keygen_secret(k, sk);
   printf("Generating ck ... ");
   fflush(stdout);
-  std::vector<uint64_t> hs((size_t)W * n);
-  to_slab(hs.data(), sk, n, W);
-  genswk(ck, permuted(hs, W, true, 0), hs, W);
+  const uint64_t g = 2ull * polyctx.n - 1;                                                         // poly_conj, src/poly.c:277-283
+  genswk_keys(ck, 1, k, &g, true, nullptr, 0);
   printf("done.\n");
 }
 
 void he_genrk(he_evk_t *rk, const poly_mpi_t *sk) {                                                // :156-170
   SHIM_CALL();
-  const unsigned W = keygen_words(), n = polyctx.n;
+  KeygenSecret k;
+  keygen_secret(k, sk);
   printf("Generating rk ... ");
   fflush(stdout);
-  std::vector<uint64_t> hs((size_t)W * n);
-  to_slab(hs.data(), sk, n, W);
-  for (unsigned rot = 0; rot < hectx.slots; ++rot) genswk(&rk[rot], permuted(hs, W, false, rot), hs, W);
+  std::vector<uint64_t> g(hectx.slots);
+  uint64_t power = 1;
+  for (unsigned rot = 0; rot < hectx.slots; ++rot, power *= 5) g[rot] = power;                     // poly_rot, src/poly.c:266-268
+  genswk_keys(rk, hectx.slots, k, g.data(), false, nullptr, 0);
   printf("done.\n");
 }
 

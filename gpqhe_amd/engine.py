@@ -344,6 +344,32 @@ class PolyContext:
         _native.check(self.lib.gpq_he_genswk(self.h, self._ptr(evk0), self._ptr(evk1), self._ptr(p1), self._ptr(sk), self._ptr(e), self._ptr(sp), W, dimP, logqL, dimevk,
                                              self._ptr(ws), self._stream()), "gpq_he_genswk")
 
+    def he_genswk_dimmul(self, dimP, logqL):
+        """limbs of he_genswk's product (src/he-kem.c:83) for q_L = 2^logqL: what sk_ntt of he_genswk_batch is packed over"""
+        dimmul = self.lib.gpq_he_genswk_dimmul(self.h, dimP, logqL)
+        if not dimmul:
+            raise _native.GpqError("gpq_he_genswk_dimmul: " + self.lib.gpq_last_error().decode())
+        return dimmul
+
+    def he_genswk_batch(self, evk0, evk1, p1, e, sk_ntt, W, dimP, logqL, dimevk, sk_small=None, galois=None, sp=None, Wsp=0):
+        """he_genswk (src/he-kem.c:74-118) for every key of evk0 / evk1 = [count][dimevk][n] in one call, q_L = 2^logqL: p1 = the RAW
+        sample_uniform big slabs [count][W][n], e = int8 small slabs [count][n], sk_ntt = the secret as ONE NTT-domain slab [dimmul][n]
+        (evk_pack over he_genswk_dimmul limbs).  The hidden polynomials: galois = one odd g per key (5^rot mod 2^64: poly_rot, 2n - 1:
+        poly_conj) with sk_small = the int8 secret [n], gathered by the kernel; or sp = big slabs [count][Wsp][n] (he_genrlk's s^2)."""
+        torch = _torch()
+        count = e.numel() // self.n
+        nbytes = self.lib.gpq_he_genswk_batch_workspace_bytes(self.h, W, dimP, logqL, dimevk, count)
+        if not nbytes:
+            raise _native.GpqError("gpq_he_genswk_batch_workspace_bytes: " + self.lib.gpq_last_error().decode())
+        ws = torch.empty(nbytes // 8 + 8, dtype=torch.int64, device=self._dev)
+        g = None if galois is None else (C.c_uint64 * max(len(galois), 1))(*[int(v) & (2**64 - 1) for v in galois])
+        if g is not None and len(galois) != count:
+            raise ValueError("%d keys need %d Galois elements, not %d" % (count, count, len(galois)))
+        opt = lambda t: None if t is None else self._ptr(t)
+        _native.check(self.lib.gpq_he_genswk_batch(self.h, self._ptr(evk0), self._ptr(evk1), self._ptr(p1), self._ptr(e), self._ptr(sk_ntt), opt(sk_small), g,
+                                                   opt(sp), Wsp, W, dimP, logqL, dimevk, count, self._ptr(ws), self._stream()), "gpq_he_genswk_batch")
+        return ws
+
     def _key_ptrs(self, keys):
         """host array of device pointers (None stays NULL)"""
         return (C.c_void_p * len(keys))(*[None if k is None else self._ptr(k).value for k in keys])

@@ -566,6 +566,31 @@ int gpq_evk_pack(gpq_ctx *ctx, uint64_t *evk, const uint64_t *big, unsigned W, u
 size_t gpq_he_genswk_workspace_bytes(gpq_ctx *ctx, unsigned W, unsigned dimP, unsigned logqL);
 int gpq_he_genswk(gpq_ctx *ctx, uint64_t *evk0, uint64_t *evk1, const uint64_t *p1, const uint64_t *sk, const uint64_t *e,
                   const uint64_t *sp, unsigned W, unsigned dimP, unsigned logqL, unsigned dimevk, void *workspace, void *stream);
+/* `count` switching keys in one call ("Key generation on the device"): for key j the words of he_genswk (src/he-kem.c:74-118)
+ * and of gpq_he_genswk above,  swk.p0 = smod(-poly_mul(p1_j, sk, dimmul, P q_L) + e_j + P sp_j, P q_L),  swk.p1 = smod(p1_j, P q_L),
+ * each stored as rns_decompose + ntt over dimevk limbs: evk0, evk1 = uint64_t[count][dimevk][n].
+ *   p1     = [count][W][n]: the RAW gpq_sample_uniform output with nbits = the bit length of P q_L (not reduced, not centred: the
+ *            reference multiplies the raw sample, :95, and centres it afterwards, :101); 64 W > nbits
+ *   e      = small slabs [count][n] (gpq_sample_error)
+ *   sk_ntt = the secret as ONE NTT-domain slab uint64_t[dimmul][n] (gpq_evk_pack of its big slab over dimmul =
+ *            gpq_he_genswk_dimmul(ctx, dimP, logqL) limbs, :83), shared by all keys, as gpq_he_dec takes it.  The words are the
+ *            reference's also when p1 * sk wraps the dimmul-limb basis.
+ *   galois = HOST array [count] of odd g, or NULL.  Given: sp_j is the image of the secret under X -> X^g, g as gpq_automorphism_index
+ *            takes it (5^rot mod 2^64: poly_rot, src/poly.c:263-275; 2n - 1: poly_conj), gathered by the kernel from sk_small =
+ *            int8_t[n], the secret itself: coefficient t is sk[i'] for i' = t g^-1 mod 2n < n and -sk[i' - n] otherwise; a rotated
+ *            secret never exists in memory.  The values are read before the call returns.
+ *            NULL: sp = the hidden polynomials as big slabs [count][Wsp][n] (he_genrlk: s^2 centred mod q_L); sk_small is not read.
+ * Asynchronous on `stream`, no host synchronisation; the constants of (dimP, logqL) are built at the first call of that pair (which
+ * therefore runs once outside a stream capture) and stay with the context.  Keys run in launch groups of gpq_set_chunk; the words do
+ * not depend on the grouping.  workspace: gpq_he_genswk_batch_workspace_bytes (0 on error).
+ * GPQ_ERR_INVALID before anything is launched for: a null argument (outside the either/or of galois + sk_small / sp + Wsp), an even
+ * g, logqL = 0, count = 0, 64 W <= bits of P q_L, a dimP, dimevk or dimmul the context lacks, an output that overlaps an input, the
+ * other output or the workspace, the wrong current device.  GPQ_ERR_UNSUPPORTED where gpq_he_genswk returns it (W > 32, P above 32 words). */
+size_t gpq_he_genswk_batch_workspace_bytes(gpq_ctx *ctx, unsigned W, unsigned dimP, unsigned logqL, unsigned dimevk, unsigned count);
+int gpq_he_genswk_batch(gpq_ctx *ctx, uint64_t *evk0, uint64_t *evk1, const uint64_t *p1, const int8_t *e, const uint64_t *sk_ntt,
+                        const int8_t *sk_small, const uint64_t *galois, const uint64_t *sp, unsigned Wsp, unsigned W, unsigned dimP,
+                        unsigned logqL, unsigned dimevk, unsigned count, void *workspace, void *stream);
+unsigned gpq_he_genswk_dimmul(gpq_ctx *ctx, unsigned dimP, unsigned logqL);   /* src/he-kem.c:83; 0 on error */
 
 /* ---- per-kernel profile ----------------------------------------------------
  * When enabled every kernel launch of this context is bracketed by two HIP
