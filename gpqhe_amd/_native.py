@@ -140,7 +140,9 @@ SIGNATURES = {
     "gpq_gemv_plan_diag_bits": (C.c_uint, [vp]),
     "gpq_ecd_roots": (C.c_int, [vp, C.c_uint]),
     "gpq_ecd_plan_create": (C.c_int, [vp, C.POINTER(vp), C.c_uint, vp, C.c_uint]),
+    "gpq_ecd_plan_create_split": (C.c_int, [vp, C.POINTER(vp), C.c_uint, C.c_uint, vp, C.c_uint]),
     "gpq_ecd_plan_destroy": (None, [vp]),
+    "gpq_ecd_plan_set_block": (C.c_int, [vp, C.c_uint]),
     "gpq_he_ecd": (C.c_int, [vp, vp, vp, vp, C.c_uint, C.c_uint, C.c_uint, vp, vp]),
     "gpq_he_ecd_diagonals": (C.c_int, [vp, vp, vp, vp, C.c_uint, C.c_uint, vp, vp]),
     "gpq_he_dcd": (C.c_int, [vp, vp, vp, vp, C.c_double, C.c_uint, C.c_uint, vp]),

@@ -8,11 +8,14 @@
 #include "dcd_kernels.hpp"
 
 #include <cmath>
+#include <cstdint>
 #include <memory>
 #include <new>
 #include <vector>
 
 using namespace gpq;
+
+static_assert(GPQ_ECD_MAX_BLOCK_SLOTS == kEcdMaxSlots && GPQ_ECD_MAX_SLOTS == (kEcdMaxSlots << kEcdMaxSplit), "include/gpqhe_hip.h states the kernels' limits");
 
 #define HIP_TRY(expr)                                                                      \
   do {                                                                                     \
@@ -23,6 +26,7 @@ using namespace gpq;
 struct gpq_ecd_plan {
   gpq_ctx *ctx = nullptr;
   unsigned slots = 0, logslots = 0;
+  unsigned logblock = 0;           // B = 2^logblock slots per workgroup; < logslots: the two-pass kernels (gpq_ecd_plan_set_block)
   gpq_dev<double2> d_roots;        // T[0 .. 4 slots]
   gpq_dev<uint32_t> d_pow5;        // 5^j mod 4 slots
   gpq_dev<uint32_t> d_bad;         // gpq_gemv_plan_create_from_matrix's own counter ...
@@ -32,6 +36,9 @@ struct gpq_ecd_plan {
 namespace {
 bool pow2(unsigned v) { return v && !(v & (v - 1)); }
 unsigned log2u(unsigned v) { unsigned b = 0; while ((1u << b) < v) ++b; return b; }
+bool block_fits(unsigned slots, unsigned block) {             // gpq_ecd_plan_set_block's rule for a non-zero block
+  return pow2(block) && block >= 2 && block <= slots && block <= gpq::kEcdMaxSlots && slots / block <= (1u << gpq::kEcdMaxSplit);
+}
 void gemv_split(unsigned slots, unsigned *n1) {               // src/he-algo.c:51-54
   unsigned a = (unsigned)std::sqrt((double)slots);
   if (slots != a * a) a = (unsigned)std::sqrt((double)(2 * slots));
@@ -48,11 +55,30 @@ int encode(gpq_ctx *c, const gpq_ecd_plan *p, uint64_t *out, const double *src, 
   int dev = -1;
   if (hipGetDevice(&dev) == hipSuccess && dev != c->device)
     return gpq_fail(GPQ_ERR_INVALID, "%s: the context lives on device %d but the calling thread's current device is %d (gpq_set_device(gpq_ctx_device(ctx)) first)", who, c->device, dev);
-  const size_t lds = (size_t)p->slots * 16;                                // above 64 KB for many slots: gpq_launch_lds
-  EcdArgs a{src, out, p->d_roots, p->d_pow5, bad, std::ldexp(1.0, (int)logDelta), 1.0 / p->slots, p->slots, p->logslots, c->logn, W, n1};
-  const unsigned threads = (p->slots / 2 >= kEcdMaxThreads || ((size_t)W << c->logn) >= 8192) ? kEcdMaxThreads : 256u;
+  EcdArgs a{src, out, p->d_roots, p->d_pow5, bad, std::ldexp(1.0, (int)logDelta), 1.0 / p->slots, p->slots, p->logslots, c->logn, W, n1,
+            p->logblock, nullptr, nullptr};
   hipStream_t s = (hipStream_t)stream;
-  {
+  if (p->logblock < p->logslots) {
+    // slots = 2^k B: columns, blocks, slab (ecd_kernels.hpp); 32 slots bytes of hand-off memory per vector, the context's
+    if ((uintptr_t)out & 15) return gpq_fail(GPQ_ERR_INVALID, "%s: out must be 16-byte aligned for a plan of more than one block", who);
+    const size_t per = (size_t)p->slots * 16, need = 2 * per * count;
+    if (need > c->d_ecd_hand.bytes)
+      if (int rc = c->d_ecd_hand.grow(c, s, need, false, "the first gpq_he_ecd of a larger batch of more than one block allocates its hand-off memory: run it once outside stream capture")) return rc;
+    a.hand = (double2 *)c->d_ecd_hand.p;
+    a.ints = (long long *)((char *)c->d_ecd_hand.p + per * count);
+    const unsigned B = 1u << p->logblock, blocks = p->slots >> p->logblock, col_tiles = (B + kEcdColThreads - 1) / kEcdColThreads;
+    const unsigned slab_tiles = (c->n / 2 + kEcdSlabThreads - 1) / kEcdSlabThreads;
+    ProfScope prof(c, GPQ_K_ECD, s);
+    switch (p->logslots - p->logblock) {
+      case 1: hipLaunchKernelGGL(he_ecd_cols<1>, dim3(count, col_tiles), dim3(kEcdColThreads), 0, s, a); break;
+      case 2: hipLaunchKernelGGL(he_ecd_cols<2>, dim3(count, col_tiles), dim3(kEcdColThreads), 0, s, a); break;
+      default: hipLaunchKernelGGL(he_ecd_cols<3>, dim3(count, col_tiles), dim3(kEcdColThreads), 0, s, a); break;
+    }
+    if (int rc = gpq_launch_lds<&he_ecd_block>((int)(kEcdMaxSlots * 16), dim3(count, blocks), dim3(B / 2 >= kEcdMaxThreads ? kEcdMaxThreads : 256u), (size_t)B * 16, s, a)) return rc;
+    hipLaunchKernelGGL(he_ecd_slab, dim3(count, slab_tiles), dim3(kEcdSlabThreads), 0, s, a);
+  } else {
+    const size_t lds = (size_t)p->slots * 16;                              // above 64 KB for many slots: gpq_launch_lds
+    const unsigned threads = (p->slots / 2 >= kEcdMaxThreads || ((size_t)W << c->logn) >= 8192) ? kEcdMaxThreads : 256u;
     ProfScope prof(c, GPQ_K_ECD, s);
     if (int rc = gpq_launch_lds<&he_ecd_lds>((int)(kEcdMaxSlots * 16), dim3(count), dim3(threads), lds, s, a)) return rc;
   }
@@ -81,14 +107,15 @@ extern "C" void gpq_ecd_plan_destroy(gpq_ecd_plan *p) {
   delete p;
 }
 
-extern "C" int gpq_ecd_plan_create(gpq_ctx *c, gpq_ecd_plan **out, unsigned slots, const double *roots, unsigned roots_slots) {
-  if (!c || !out) return gpq_fail(GPQ_ERR_INVALID, "gpq_ecd_plan_create: null argument");
+// one body for gpq_ecd_plan_create (most = what one workgroup holds) and gpq_ecd_plan_create_split (most = kEcdMaxSlots << kEcdMaxSplit)
+static int plan_create(gpq_ctx *c, gpq_ecd_plan **out, unsigned slots, const double *roots, unsigned roots_slots, unsigned most, const char *who) {
+  if (!c || !out) return gpq_fail(GPQ_ERR_INVALID, "%s: null argument", who);
   if (!pow2(slots) || slots > c->n / 2)
-    return gpq_fail(GPQ_ERR_INVALID, "gpq_ecd_plan_create: slots = %u must be a power of two up to n/2 = %u", slots, c->n / 2);
-  if (slots > kEcdMaxSlots)
-    return gpq_fail(GPQ_ERR_INVALID, "gpq_ecd_plan_create: %u slots exceed the %u one workgroup holds in LDS", slots, kEcdMaxSlots);
+    return gpq_fail(GPQ_ERR_INVALID, "%s: slots = %u must be a power of two up to n/2 = %u", who, slots, c->n / 2);
+  if (slots > most)
+    return gpq_fail(GPQ_ERR_INVALID, "%s: %u slots exceed the %u that %u workgroup(s) hold in LDS", who, slots, most, most / kEcdMaxSlots);
   if (roots && (!pow2(roots_slots) || roots_slots < slots))
-    return gpq_fail(GPQ_ERR_INVALID, "gpq_ecd_plan_create: the root table is for %u slots: a power of two >= %u is needed", roots_slots, slots);
+    return gpq_fail(GPQ_ERR_INVALID, "%s: the root table is for %u slots: a power of two >= %u is needed", who, roots_slots, slots);
   const unsigned m4 = 4 * slots;
   std::vector<double> T(2 * (size_t)(m4 + 1));
   if (roots) {
@@ -102,8 +129,9 @@ extern "C" int gpq_ecd_plan_create(gpq_ctx *c, gpq_ecd_plan **out, unsigned slot
   uint32_t g = 1;
   for (uint32_t &v : pow5) { v = g; g = (uint32_t)((5ull * g) % m4); }
   std::unique_ptr<gpq_ecd_plan, void (*)(gpq_ecd_plan *)> p(new (std::nothrow) gpq_ecd_plan(), gpq_ecd_plan_destroy);
-  if (!p) return gpq_fail(GPQ_ERR_NOMEM, "out of host memory");
+  if (!p) return gpq_fail(GPQ_ERR_NOMEM, "%s: out of host memory", who);
   p->ctx = c; p->slots = slots; p->logslots = log2u(slots);
+  p->logblock = log2u(slots < kEcdMaxSlots ? slots : kEcdMaxSlots);
   DeviceScope on_device(c->device);
   HIP_TRY(p->d_roots.alloc(T.size() * sizeof(double)));
   HIP_TRY(p->d_pow5.alloc(pow5.size() * sizeof(uint32_t)));
@@ -115,6 +143,31 @@ extern "C" int gpq_ecd_plan_create(gpq_ctx *c, gpq_ecd_plan **out, unsigned slot
   return GPQ_OK;
 }
 
+extern "C" int gpq_ecd_plan_create(gpq_ctx *c, gpq_ecd_plan **out, unsigned slots, const double *roots, unsigned roots_slots) {
+  return plan_create(c, out, slots, roots, roots_slots, kEcdMaxSlots, "gpq_ecd_plan_create");
+}
+
+extern "C" int gpq_ecd_plan_create_split(gpq_ctx *c, gpq_ecd_plan **out, unsigned slots, unsigned block_slots, const double *roots, unsigned roots_slots) {
+  if (block_slots && pow2(slots) && !block_fits(slots, block_slots))           // before anything is allocated
+    return gpq_fail(GPQ_ERR_INVALID, "gpq_ecd_plan_create_split: %u is no power of two in 2..min(slots, %u) with at most %u blocks in %u slots", block_slots, kEcdMaxSlots, 1u << kEcdMaxSplit, slots);
+  gpq_ecd_plan *p = nullptr;
+  int rc = plan_create(c, &p, slots, roots, roots_slots, kEcdMaxSlots << kEcdMaxSplit, "gpq_ecd_plan_create_split");
+  if (rc != GPQ_OK) return rc;
+  if (block_slots) p->logblock = log2u(block_slots);
+  *out = p;
+  return GPQ_OK;
+}
+
+extern "C" int gpq_ecd_plan_set_block(gpq_ecd_plan *p, unsigned block_slots) {
+  if (!p) return gpq_fail(GPQ_ERR_INVALID, "gpq_ecd_plan_set_block: no plan");
+  const unsigned most = p->slots < kEcdMaxSlots ? p->slots : kEcdMaxSlots;
+  if (!block_slots) { p->logblock = log2u(most); return GPQ_OK; }
+  if (!block_fits(p->slots, block_slots))
+    return gpq_fail(GPQ_ERR_INVALID, "gpq_ecd_plan_set_block: %u is no power of two in 2..%u with at most %u blocks in %u slots", block_slots, most, 1u << kEcdMaxSplit, p->slots);
+  p->logblock = log2u(block_slots);
+  return GPQ_OK;
+}
+
 extern "C" int gpq_he_ecd(gpq_ctx *c, const gpq_ecd_plan *p, uint64_t *out, const double *z_dev, unsigned logDelta, unsigned W, unsigned count,
                           uint32_t *bad_dev, void *stream) {
   return encode(c, p, out, z_dev, logDelta, W, count, 0, bad_dev, stream, "gpq_he_ecd");
@@ -123,6 +176,7 @@ extern "C" int gpq_he_ecd(gpq_ctx *c, const gpq_ecd_plan *p, uint64_t *out, cons
 extern "C" int gpq_he_ecd_diagonals(gpq_ctx *c, const gpq_ecd_plan *p, uint64_t *out, const double *A_dev, unsigned logDelta, unsigned W,
                                     uint32_t *bad_dev, void *stream) {
   unsigned n1 = 1;
+  if (p && p->slots > kEcdMaxSlots) return gpq_fail(GPQ_ERR_INVALID, "gpq_he_ecd_diagonals: a %u x %u matrix (a plan above %u slots) is not taken", p->slots, p->slots, kEcdMaxSlots);
   if (p) gemv_split(p->slots, &n1);
   return encode(c, p, out, A_dev, logDelta, W, p ? p->slots : 1, n1, bad_dev, stream, "gpq_he_ecd_diagonals");
 }
@@ -138,11 +192,22 @@ extern "C" int gpq_he_dcd(gpq_ctx *c, const gpq_ecd_plan *p, double *z_dev, cons
   int dev = -1;
   if (hipGetDevice(&dev) == hipSuccess && dev != c->device)
     return gpq_fail(GPQ_ERR_INVALID, "%s: the context lives on device %d but the calling thread's current device is %d (gpq_set_device(gpq_ctx_device(ctx)) first)", who, c->device, dev);
-  const size_t lds = (size_t)p->slots * 16;                                // (the attribute is per kernel function: he_ecd_lds having it does not serve)
-  DcdArgs a{in, z_dev, p->d_roots, p->d_pow5, nu, p->slots, p->logslots, c->logn, W};
-  const unsigned threads = p->slots >= kEcdMaxThreads ? kEcdMaxThreads : 256u;     // 2 slots conversions, slots / 2 butterflies per stage
+  DcdArgs a{in, z_dev, p->d_roots, p->d_pow5, nu, p->slots, p->logslots, c->logn, W, p->logblock};
   hipStream_t s = (hipStream_t)stream;
-  {
+  if (p->logblock < p->logslots) {
+    // slots = 2^k B: blocks into z_dev, then columns in place on it (dcd_kernels.hpp): no scratch
+    if ((uintptr_t)z_dev & 15) return gpq_fail(GPQ_ERR_INVALID, "%s: z_dev must be 16-byte aligned", who);
+    const unsigned B = 1u << p->logblock, blocks = p->slots >> p->logblock, col_tiles = (B + kEcdColThreads - 1) / kEcdColThreads;
+    ProfScope prof(c, GPQ_K_DCD, s);
+    if (int rc = gpq_launch_lds<&he_dcd_block>((int)(kEcdMaxSlots * 16), dim3(count, blocks), dim3(B >= kEcdMaxThreads ? kEcdMaxThreads : 256u), (size_t)B * 16, s, a)) return rc;
+    switch (p->logslots - p->logblock) {
+      case 1: hipLaunchKernelGGL(he_dcd_cols<1>, dim3(count, col_tiles), dim3(kEcdColThreads), 0, s, a); break;
+      case 2: hipLaunchKernelGGL(he_dcd_cols<2>, dim3(count, col_tiles), dim3(kEcdColThreads), 0, s, a); break;
+      default: hipLaunchKernelGGL(he_dcd_cols<3>, dim3(count, col_tiles), dim3(kEcdColThreads), 0, s, a); break;
+    }
+  } else {
+    const size_t lds = (size_t)p->slots * 16;                              // (the attribute is per kernel function: he_ecd_lds having it does not serve)
+    const unsigned threads = p->slots >= kEcdMaxThreads ? kEcdMaxThreads : 256u;     // 2 slots conversions, slots / 2 butterflies per stage
     ProfScope prof(c, GPQ_K_DCD, s);
     if (int rc = gpq_launch_lds<&he_dcd_lds>((int)(kEcdMaxSlots * 16), dim3(count), dim3(threads), lds, s, a)) return rc;
   }
@@ -153,6 +218,7 @@ extern "C" int gpq_he_dcd(gpq_ctx *c, const gpq_ecd_plan *p, double *z_dev, cons
 extern "C" int gpq_gemv_plan_create_from_matrix(gpq_ctx *c, gpq_gemv_plan **out, const gpq_ecd_plan *p, const double *A_dev, unsigned logDelta,
                                                 unsigned logql, unsigned dimpt, void *stream) {
   if (!c || !out || !p || p->ctx != c || !A_dev) return gpq_fail(GPQ_ERR_INVALID, "gpq_gemv_plan_create_from_matrix: null argument, or a plan of another context");
+  if (p->slots > kEcdMaxSlots) return gpq_fail(GPQ_ERR_INVALID, "gpq_gemv_plan_create_from_matrix: a %u x %u matrix (a plan above %u slots) is not taken", p->slots, p->slots, kEcdMaxSlots);
   hipStream_t s = (hipStream_t)stream;
   if (gpq_capturing(s))
     return gpq_fail(GPQ_ERR_INVALID, "gpq_gemv_plan_create_from_matrix allocates and waits for the stream: not inside a stream capture");

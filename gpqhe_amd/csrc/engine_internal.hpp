@@ -235,6 +235,7 @@ struct gpq_ctx {
   gpq_stream_own peer_stream;
   gpq_event ev_fork, ev_join;
   gpq_dev<void> peer_ws;
+  gpq_dev<void> d_ecd_hand;           // gpq_he_ecd with a plan of more than one block: 32 slots bytes per vector between its three kernels (ecd.hip: encode)
   gpq_dev<unsigned> d_zflag;          // per-(polynomial, limb) "output contains a residue 0" flags of gpq_ntt (tables.hpp); zero between calls
   // gpq_debug_zero_watch: copies of the flag words of gpq_ntt's LAST launch group as the forward kernels left them (before ref_zero_redo) and
   // as ref_zero_redo left them (after), taken on the launch stream; [0, zwatch_cap) before, [zwatch_cap, 2 zwatch_cap) after

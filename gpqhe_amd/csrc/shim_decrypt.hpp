@@ -23,11 +23,11 @@ bool dec_body(struct he_pt *pt, _Complex double *z, const struct he_ct *ct, cons
   const unsigned slots = hectx.slots;
   gpq_ecd_plan *dplan = nullptr;
   if (z) {
-    if (!pow2 || logql == 0 || !polyctx.ring.zetas || !slots || (slots & (slots - 1)) || slots > 8192 || slots > n / 2 || !(ct->nu > 0) || !std::isfinite(ct->nu))
+    if (!pow2 || logql == 0 || !polyctx.ring.zetas || !slots || (slots & (slots - 1)) || slots > n / 2 || slots > GPQ_ECD_MAX_SLOTS || !(ct->nu > 0) || !std::isfinite(ct->nu))
       return false;
     if (!g_dcd_plan.plan || g_dcd_plan.slots != slots || g_dcd_plan.m != polyctx.m || g_dcd_plan.zetas != (const void *)polyctx.ring.zetas) {
       if (g_dcd_plan.plan) { (void)gpq_stream_sync(nullptr); gpq_ecd_plan_destroy(g_dcd_plan.plan); g_dcd_plan = DcdPlan(); }
-      if (gpq_ecd_plan_create(c, &g_dcd_plan.plan, slots, (const double *)polyctx.ring.zetas, polyctx.m / 4) != GPQ_OK) die("he_dec_dcd: cannot build the decoder's tables");
+      if (gpq_ecd_plan_create_split(c, &g_dcd_plan.plan, slots, 0, (const double *)polyctx.ring.zetas, polyctx.m / 4) != GPQ_OK) die("he_dec_dcd: cannot build the decoder's tables");
       g_dcd_plan.slots = slots; g_dcd_plan.m = polyctx.m; g_dcd_plan.zetas = (const void *)polyctx.ring.zetas;
     }
     dplan = g_dcd_plan.plan;

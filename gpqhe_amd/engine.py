@@ -404,9 +404,11 @@ class PolyContext:
         return GemvPlan(self, diag, slots, W, logql, dimpt)
 
     # --- he_ecd on the device (include/gpqhe_hip.h, "he_ecd on the device") ---
-    def ecd_plan(self, slots, roots=None, roots_slots=None):
-        """The encoder's tables for `slots` slots: roots = a (4 S + 1) x 2 float64 table for S >= slots slots (None: ecd_roots(slots))."""
-        return EcdPlan(self, slots, roots, roots_slots)
+    def ecd_plan(self, slots, roots=None, roots_slots=None, block=None):
+        """The encoder's tables for `slots` slots: roots = a (4 S + 1) x 2 float64 table for S >= slots slots (None: ecd_roots(slots)).
+        block = None: gpq_ecd_plan_create, at most 8192 slots; block = slots per workgroup (0: min(slots, 8192)):
+        gpq_ecd_plan_create_split, any power of two up to n/2 and 65536."""
+        return EcdPlan(self, slots, roots, roots_slots, block)
 
     def he_ecd(self, plan, out, z, logDelta=None, W=1, bad=None, Delta=None):
         """he_ecd (src/he-encode.c:107-111) of every vector of z = [count][slots] complex128 (or (re, im) float64 pairs) on the device into
@@ -670,17 +672,28 @@ class GemvPlan:
 
 class EcdPlan:
     """gpq_ecd_plan: the root table and the powers of 5 the encoder reads for `slots` slots, on the device.  `roots` = a (4 S + 1) x 2
-    float64 array for S = roots_slots >= slots slots (S is taken from the array's length when not given); None = ecd_roots(slots)."""
+    float64 array for S = roots_slots >= slots slots (S is taken from the array's length when not given); None = ecd_roots(slots).
+    block = None: at most 8192 slots, one workgroup per vector.  block = slots per workgroup (0: min(slots, 8192)): gpq_ecd_plan_create_split,
+    slots = any power of two up to n/2 and 65536, a vector of more slots than `block` split over workgroups (include/gpqhe_hip.h)."""
 
-    def __init__(self, ctx, slots, roots=None, roots_slots=None):
+    def __init__(self, ctx, slots, roots=None, roots_slots=None, block=None):
         self.lib, self.h, self.slots = ctx.lib, C.c_void_p(), slots
         if roots is not None:
             roots = np.ascontiguousarray(roots, dtype=np.float64).reshape(-1, 2)
             roots_slots = roots_slots or (roots.shape[0] - 1) // 4
             if roots.shape[0] != 4 * roots_slots + 1:
                 raise ValueError("a root table for %d slots has %d rows, not %d" % (roots_slots, 4 * roots_slots + 1, roots.shape[0]))
-        _native.check(self.lib.gpq_ecd_plan_create(ctx.h, C.byref(self.h), slots, None if roots is None else roots.ctypes.data_as(C.c_void_p),
-                                                   roots_slots or 0), "gpq_ecd_plan_create")
+        table = None if roots is None else roots.ctypes.data_as(C.c_void_p)
+        if block is None:
+            _native.check(self.lib.gpq_ecd_plan_create(ctx.h, C.byref(self.h), slots, table, roots_slots or 0), "gpq_ecd_plan_create")
+        else:
+            _native.check(self.lib.gpq_ecd_plan_create_split(ctx.h, C.byref(self.h), slots, block, table, roots_slots or 0), "gpq_ecd_plan_create_split")
+
+    def set_block(self, block_slots=0):
+        """gpq_ecd_plan_set_block: slots per workgroup for he_ecd and he_dcd on this plan (0: the default, min(slots, 8192)); a power of
+        two in 2..min(slots, 8192) with slots / block_slots <= 8.  The words never depend on it."""
+        _native.check(self.lib.gpq_ecd_plan_set_block(self.h, block_slots), "gpq_ecd_plan_set_block")
+        return self
 
     def close(self):
         if getattr(self, "h", None):

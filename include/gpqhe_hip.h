@@ -441,19 +441,37 @@ int gpq_he_gemv_planned(gpq_ctx *ctx, uint64_t *out_c0, uint64_t *out_c1, const 
  * gpq_ecd_plan_create: slots = a power of two, <= n/2 and <= 8192 (16 bytes per slot in LDS; more: GPQ_ERR_INVALID).  roots = the caller's
  *   table for roots_slots >= slots (a power of two), read by stride -- a host that has polyctx.ring.zetas passes it with roots_slots = m/4
  *   and gets the words of its own encoder under any libm; NULL = gpq_ecd_roots.  A plan belongs to its context and is destroyed before it.
+ * gpq_ecd_plan_create_split: the same plan for slots = a power of two, <= n/2 and <= 65536 (more, or no power of two: GPQ_ERR_INVALID,
+ *   nothing allocated), with block_slots as gpq_ecd_plan_set_block takes it.  A vector of more slots than the block B is shared:
+ *   slots = 2^k B, k <= 3: the k highest stages run one column per lane on global memory, the rest one block of B slots per workgroup,
+ *   and the slab is written by the whole device (he_ecd_cols, he_ecd_block, he_ecd_slab; the decoder mirrors it with he_dcd_block,
+ *   he_dcd_cols).  The same individually rounded operations in another order of execution: the words do not depend on the split.
+ *   gpq_ecd_plan_create keeps its limit of one workgroup, so a caller that relies on its refusal above 8192 slots still gets it.
  * gpq_he_ecd: z_dev = [count][slots] (re, im) pairs on the device; out = [count][W][n], W <= 32: slot i as W sign-extended words at
  *   coefficient i gap (real part) and i gap + n/2 (imaginary part), gap = n / (2 slots), zero everywhere else.  The call writes every word
- *   of `out`: the caller does not clear it.  Asynchronous on `stream`.
+ *   of `out`: the caller does not clear it.  Asynchronous on `stream`.  A plan of more than one block takes 32 slots bytes per vector of
+ *   hand-off memory from the context, allocated at the first call of a larger batch -- that call runs outside a stream capture, later
+ *   ones may be captured -- and wants `out` 16-byte aligned.
+ * gpq_ecd_plan_set_block: slots per workgroup for both directions of this plan, a tuning and test knob like gpq_set_chunk: the words
+ *   never depend on it.  0 = the default, min(slots, 8192); else a power of two with 2 <= block_slots <= min(slots, 8192) and
+ *   slots / block_slots <= 8 (anything else: GPQ_ERR_INVALID, the plan unchanged).  block_slots < slots selects the kernels for more than
+ *   one block.  Not while a call on the plan is being issued by another thread.
  * gpq_he_ecd_diagonals: A_dev = a slots x slots row-major matrix of (re, im) pairs; out[i n1 + j] = he_ecd(zrotdiag(A, i n1 + j, -i n1))
  *   (src/he-algo.c:29-43, :63-72; n1 as :51-54): the `diag` of gpq_he_gemv and gpq_gemv_plan_create, gathered by the kernel's load.
+ *   A plan above 8192 slots is refused here and by gpq_gemv_plan_create_from_matrix (GPQ_ERR_INVALID): its slots x slots matrix alone
+ *   is 4 GiB or more.
  * gpq_gemv_plan_create_from_matrix: gpq_gemv_plan_create on the diagonals of A_dev encoded into a W = 1 slab (8 n bytes per diagonal: every
  *   encodable value fits), which is released before the call returns.  A coefficient out of range fails the call with GPQ_ERR_INVALID
  *   and leaves no plan.  Waits for `stream` as gpq_gemv_plan_create does (the bad count arrives with its measurement), and for the
  *   device when it releases the slab. */
 typedef struct gpq_ecd_plan gpq_ecd_plan;
+#define GPQ_ECD_MAX_BLOCK_SLOTS 8192u /* slots one workgroup holds: gpq_ecd_plan_create's limit, and a block's */
+#define GPQ_ECD_MAX_SLOTS 65536u      /* 8 blocks: gpq_ecd_plan_create_split's limit                           */
 int gpq_ecd_roots(double *table, unsigned slots);
 int gpq_ecd_plan_create(gpq_ctx *ctx, gpq_ecd_plan **plan, unsigned slots, const double *roots, unsigned roots_slots);
+int gpq_ecd_plan_create_split(gpq_ctx *ctx, gpq_ecd_plan **plan, unsigned slots, unsigned block_slots, const double *roots, unsigned roots_slots);
 void gpq_ecd_plan_destroy(gpq_ecd_plan *plan);
+int gpq_ecd_plan_set_block(gpq_ecd_plan *plan, unsigned block_slots);
 int gpq_he_ecd(gpq_ctx *ctx, const gpq_ecd_plan *plan, uint64_t *out, const double *z_dev, unsigned logDelta, unsigned W, unsigned count,
                uint32_t *bad_dev, void *stream);
 int gpq_he_ecd_diagonals(gpq_ctx *ctx, const gpq_ecd_plan *plan, uint64_t *out, const double *A_dev, unsigned logDelta, unsigned W,
@@ -465,7 +483,9 @@ unsigned gpq_gemv_plan_diag_bits(const gpq_gemv_plan *plan);
 
 /* ---- he_dec and he_dcd on the device ("Decoding on the device") ------------------------------------------------------------
  * he_dcd, src/he-encode.c:66-74 and :114-117 with canemb, src/canemb.c:43-60: a plaintext big slab -> `slots` complex doubles, one
- * workgroup per plaintext (he_dcd_lds), on the SAME gpq_ecd_plan as the encoder (its root table and powers of 5; no plan type of its own).
+ * workgroup per plaintext (he_dcd_lds) or, for a plan of more than one block (gpq_ecd_plan_create_split above 8192 slots, or gpq_ecd_plan_set_block), one workgroup
+ * per block and then one lane per column in place on z_dev (he_dcd_block, he_dcd_cols; no scratch; z_dev 16-byte aligned), on the SAME
+ * gpq_ecd_plan as the encoder (its root table and powers of 5; no plan type of its own).
  * The doubles are the reference's bit for bit, given the same root table:
  *   - mpi_to_double (src/types.c:77-106) is `num = num * 2 + bit` in double arithmetic, neither correctly rounded nor truncating: a
  *     magnitude of more than 53 bits becomes M' 2^(L - 53) with M its top 53 bits, b the 54th and M' = M + (b & M & 1); every lower bit is

@@ -214,7 +214,7 @@ void gpq_mpi_shim_set_device_ecd(int on);
  * contract the host program's own, like he_ecd; this is a name of its own.)  The operands, their residency and the recheck are he_dec's;
  * the decoder is gpqhe_hip.h's gpq_he_dcd with the host's polyctx.ring.zetas as roots (as gpq_mpi_shim_set_device_ecd) and nu = ct->nu, so
  * the doubles are those of the reference's he_dec + he_dcd on that table, bit for bit.  Returns 1 when done; 0 -- and m untouched -- when q_l
- * is no power of two, slots > 8192 or there is no ring table: the caller then runs he_dec + he_dcd. */
+ * is no power of two or there is no ring table: the caller then runs he_dec + he_dcd.  Any slot count up to polyctx.n / 2. */
 int gpq_shim_he_dec_dcd(_Complex double *m, const struct he_ct *ct, const poly_mpi_t *sk);
 /* How a resident key is recognised: by the caller's two pointers and a fingerprint of EVERY word, limb by limb (full != 0, the
  * default: a key edited in place multiplies as edited, like the reference, which reads its key on every call), computed by the
