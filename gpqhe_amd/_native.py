@@ -156,6 +156,15 @@ SIGNATURES = {
     "gpq_he_enc_workspace_bytes": (C.c_size_t, [vp, C.c_uint, C.c_uint, C.c_int]),
     "gpq_he_enc_pk": (C.c_int, [vp] * 9 + [C.c_uint] * 4 + [vp, vp]),
     "gpq_he_enc_sk": (C.c_int, [vp] * 7 + [C.c_uint] * 4 + [vp, vp]),
+    "gpq_surf_bytes": (C.c_int, [vp, vp, C.c_size_t, vp, u64, u64, vp]),
+    "gpq_surf_bytes_host": (C.c_int, [vp, C.c_size_t, vp, u64, u64]),
+    "gpq_rng_create": (C.c_int, [C.POINTER(vp), vp]),
+    "gpq_rng_destroy": (None, [vp]),
+    "gpq_rng_seek": (C.c_int, [vp, u64, u64]),
+    "gpq_rng_tell": (C.c_int, [vp, C.POINTER(u64)]),
+    "gpq_rng_host_bytes": (C.c_int, [vp, vp, C.c_size_t]),
+    "gpq_rng_device_bytes": (C.c_int, [vp, vp, vp, C.c_size_t, vp]),
+    "gpq_debug_rng_split": (C.c_int, [C.c_size_t]),
     "gpq_gemv_plan_create_from_matrix": (C.c_int, [vp, C.POINTER(vp), vp, vp, C.c_uint, C.c_uint, C.c_uint, vp]),
     "gpq_shim_gemv_plan_cache": (None, [C.c_uint]),
     "gpq_gemv_inner_workspace_bytes": (C.c_size_t, [vp, vp, C.c_uint]),
@@ -199,6 +208,12 @@ SIGNATURES = {
     "gpq_mpi_shim_last_timing": (None, [C.POINTER(C.c_double)]),
     "gpq_mpi_shim_set_device_ecd": (None, [C.c_int]),
     "gpq_mpi_shim_set_device_samplers": (None, [C.c_int]),
+    "gpq_mpi_shim_set_device_rng": (None, [C.c_int]),
+    "gpq_randombytes": (None, [vp, C.c_size_t]),
+    "gpq_randombytes_seek": (C.c_int, [u64, u64]),
+    "gpq_randombytes_tell": (C.c_int, [C.POINTER(u64)]),
+    "gpq_randombytes_seed": (C.c_int, [vp]),
+    "gpq_randombytes_device": (C.c_int, [vp, vp, C.c_size_t, vp]),
     "gpq_shim_he_dec_dcd": (C.c_int, [vp, vp, vp]),
     "gpq_fill_rns_chain": (C.c_int, [vp, C.c_uint, vp, C.c_int]),
     "gpq_release_rns_chain": (None, [vp]),

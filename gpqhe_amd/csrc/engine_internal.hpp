@@ -94,7 +94,9 @@ enum { GPQ_K_STRIDED_FWD = 0, GPQ_K_STRIDED_INV, GPQ_K_CONTIG_FWD, GPQ_K_CONTIG_
        // samplers and encryption on the device (enc_kernels.hpp): the byte-fed samplers; small_to_rns_k / small_to_big_k / enc_tail_k
        GPQ_K_SAMPLE, GPQ_K_ENC,
        // gpq_he_genswk_batch: the CRT recombination of a switching key mod P 2^k (genswk_crt_tail, genswk_kernels.hpp)
-       GPQ_K_GENSWK_TAIL, GPQ_K_COUNT };
+       GPQ_K_GENSWK_TAIL,
+       // the reference's deterministic randombytes by position (surf_stream_k, rng_kernels.hpp): a class of its own, so that the samplers' times stay theirs
+       GPQ_K_RNG, GPQ_K_COUNT };
 
 // Constant matrix of the matrix-core CRT fast path for one basis and result width WL (bridge_mfma.hpp)
 struct gpq_recon_mfma {

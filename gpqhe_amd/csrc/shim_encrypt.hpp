@@ -8,9 +8,11 @@
 // and gpq_sample_zo / gpq_sample_error / gpq_sample_uniform expand the bytes on the device; sample_sk stays the host's.  Power-of-two q_L
 // takes gpq_he_enc_pk / gpq_he_enc_sk; any other q_L the reference's sequence over the general entry points.  The key polynomials and the
 // plaintext are resident operands like he_dec's (Operands), the written ciphertext / public key is remembered (remember_results).
+// gpq_mpi_shim_set_device_rng(1) on top of the device samplers: the same byte counts in the same order are reserved from the default stream
+// of gpq_randombytes and generated in device memory by ONE gpq_randombytes_device per call; the samplers read slices of that buffer.
 } // extern "C"
 namespace {
-bool g_device_samplers = false;
+bool g_device_samplers = false, g_device_rng = false;
 
 struct TmpPoly {                                            // a polynomial for the host's samplers to fill
   poly_mpi_t p; unsigned n;
@@ -23,7 +25,13 @@ void forget_poly(const poly_mpi_t *p) {
   for (size_t i = 0; i < g_polys.size(); ++i) if (g_polys[i].coeffs == p->coeffs) { drop_poly_slot(i); return; }
 }
 // one small polynomial (zo: kind 0, error: kind 1) as an int8 small slab on the device
-void sample_small(gpq_ctx *c, const DevBuf &dst, int kind, unsigned n, bool device) {
+// (`drawn`: the bytes are already on the device, a slice of the call's gpq_randombytes_device)
+void sample_small(gpq_ctx *c, const DevBuf &dst, int kind, unsigned n, bool device, const uint8_t *drawn = nullptr) {
+  if (drawn) {
+    const int rc = kind ? gpq_sample_error(c, (int8_t *)dst.p, drawn, 1, nullptr) : gpq_sample_zo(c, (int8_t *)dst.p, drawn, 1, nullptr);
+    if (rc != GPQ_OK) die("he_enc: the device sampler failed");
+    return;
+  }
   if (device) {
     const size_t nbytes = kind ? n : n / 4;
     std::vector<uint8_t> h(nbytes);
@@ -44,8 +52,12 @@ void sample_small(gpq_ctx *c, const DevBuf &dst, int kind, unsigned n, bool devi
   if (gpq_upload(dst.p, h.data(), n, nullptr) != GPQ_OK || gpq_stream_sync(nullptr) != GPQ_OK) die("upload failed");
 }
 // sample_uniform(q) as a RAW big slab of W words on the device
-void sample_raw(gpq_ctx *c, const DevBuf &dst, gpq_MPI q, unsigned n, unsigned W, bool device) {
+void sample_raw(gpq_ctx *c, const DevBuf &dst, gpq_MPI q, unsigned n, unsigned W, bool device, const uint8_t *drawn = nullptr) {
   const unsigned nbits = G.mpi_get_nbits(q);
+  if (drawn) {
+    if (gpq_sample_uniform(c, dst.u64(), drawn, nbits, W, 1, nullptr) != GPQ_OK) die("he_enc: the device sampler failed");
+    return;
+  }
   if (device) {
     const size_t nbytes = (size_t)n * (nbits / 8 + 1);
     std::vector<uint8_t> h(nbytes);
@@ -74,15 +86,26 @@ void enc_body(int kind, poly_mpi_t *out0, poly_mpi_t *out1, const poly_mpi_t *ke
   const unsigned nbq = G.mpi_get_nbits(q), logq = nbq - 1;
   if (logq == 0) die("he_enc: q_L = 1");
   if (polyctx.logn < 2) die("he_enc: sample_zo needs n >= 4");
-  const bool device = g_device_samplers && randombytes != nullptr;
+  const bool drawn = g_device_samplers && g_device_rng, device = drawn || (g_device_samplers && randombytes != nullptr);
   if (!device && (!sample_error || (kind == 0 ? !sample_zo : !sample_uniform)))
     die("he_enc / he_keypair: the host program does not provide sample_zo / sample_error / sample_uniform (src/sample.c)");
   const unsigned Wmin = nbq / 64 + 1;                        // holds the raw sample (nbq bits) as a non-negative value
   if (Wmin > 32) die("he_enc: modulus wider than 2047 bits");
   // the samples, in the reference's order, once per call (a repeated device pass reuses them)
   DevBuf dv(n), de0(n), de1(n);
-  if (kind == 0) { sample_small(c, dv, 0, n, device); sample_small(c, de0, 1, n, device); sample_small(c, de1, 1, n, device); }   // src/he-encrypt.c:50-56
-  else sample_small(c, de0, 1, n, device);                                                                                        // :88, src/he-kem.c:56
+  // device rng: every byte of the call at once -- zo, error, error (n/4 + 2n) resp. error, uniform (n + n (nbq / 8 + 1))
+  const size_t ndrawn = kind == 0 ? (size_t)n / 4 + 2 * (size_t)n : (size_t)n + (size_t)n * (nbq / 8 + 1);
+  std::unique_ptr<DevBuf> db;                                                                                                      // only with the device generator
+  if (drawn) {
+    db.reset(new DevBuf(ndrawn));
+    if (gpq_randombytes_device(c, (uint8_t *)db->p, ndrawn, nullptr) != GPQ_OK) die("he_enc: generating the random bytes on the device failed");
+  }
+  const uint8_t *at = drawn ? (const uint8_t *)db->p : nullptr;
+  if (kind == 0) {                                                                                                                // src/he-encrypt.c:50-56
+    sample_small(c, dv, 0, n, device, at);
+    sample_small(c, de0, 1, n, device, drawn ? at + n / 4 : nullptr);
+    sample_small(c, de1, 1, n, device, drawn ? at + n / 4 + n : nullptr);
+  } else sample_small(c, de0, 1, n, device, at);                                                                                  // :88, src/he-kem.c:56
   const int count = kind == 0 ? 3 : kind == 1 ? 2 : 1;
   const poly_mpi_t *in[3] = {key0, kind == 0 ? key1 : m, kind == 0 ? m : nullptr};
   poly_mpi_t *out[2] = {out0, out1};
@@ -147,7 +170,7 @@ void enc_body(int kind, poly_mpi_t *out0, poly_mpi_t *out1, const poly_mpi_t *ke
   auto run = [&](unsigned W, bool kept) -> bool {
     if (kind == 0) return pass(W, kept, nullptr);
     DevBuf da((size_t)W * n * 8);
-    sample_raw(c, da, q, n, W, device);                                                 // src/he-encrypt.c:89, src/he-kem.c:58
+    sample_raw(c, da, q, n, W, device, drawn ? at + n : nullptr);                                                 // src/he-encrypt.c:89, src/he-kem.c:58
     return pass(W, kept, &da);
   };
   unsigned bits = nbq;
@@ -193,3 +216,4 @@ void he_keypair(he_pk_t *pk, poly_mpi_t *sk) {                                  
 }
 
 void gpq_mpi_shim_set_device_samplers(int on) { SHIM_CALL(); g_device_samplers = on != 0; }
+void gpq_mpi_shim_set_device_rng(int on) { SHIM_CALL(); g_device_rng = on != 0; }

@@ -9,7 +9,8 @@
 // per key -- sample_error, then sample_uniform(P q_L) -- so a seeded RNG gives the reference's own keys; with
 // gpq_mpi_shim_set_device_samplers(1) the host's randombytes is called instead, once per sampler call with the reference's byte counts
 // (n, then n (nbits/8 + 1)), and gpq_sample_error / gpq_sample_uniform expand the group's byte buffer on the device, one launch per key
-// slice: no sampled polynomial becomes libgcrypt integers.
+// slice: no sampled polynomial becomes libgcrypt integers.  With gpq_mpi_shim_set_device_rng(1) as well the group's byte buffer is not
+// drawn from the host at all: ONE gpq_randombytes_device reserves the same bytes from the default stream and makes them on the device.
 } // extern "C"
 namespace {
 constexpr unsigned kKeygenGroup = 32;                       // the engine's default launch group (gpq_set_chunk)
@@ -51,7 +52,7 @@ void keygen_secret(KeygenSecret &k, const poly_mpi_t *sk) {
 // keys swk[0..count): the hidden polynomial of key j is the image of the secret under X -> X^galois[j] -- poly_conj (conj) or poly_rot by j --
 // or (galois == nullptr, count == 1) the device big slab sp of Wsp words
 void genswk_keys(he_evk_t *swk, unsigned count, const KeygenSecret &k, const uint64_t *galois, bool conj, const uint64_t *sp, unsigned Wsp) {
-  const bool device = g_device_samplers && randombytes != nullptr;
+  const bool drawn = g_device_samplers && g_device_rng, device = drawn || (g_device_samplers && randombytes != nullptr);
   if (!device && (!sample_error || !sample_uniform)) die("he_gen*k: the host program does not provide sample_error / sample_uniform (src/sample.c)");
   gpq_ctx *c = engine();
   const unsigned n = polyctx.n, W = k.W, dimevk = hectx.dimevk, nb = k.nbits / 8 + 1;
@@ -62,14 +63,18 @@ void genswk_keys(he_evk_t *swk, unsigned count, const KeygenSecret &k, const uin
     DevBuf dp(m * big * 8), de((size_t)m * n), d0(m * evk * 8), d1(m * evk * 8),
         ws(gpq_he_genswk_batch_workspace_bytes(c, W, hectx.dim, k.logqL, dimevk, m));
     if (device) {
-      std::vector<uint8_t> bytes((size_t)m * ((size_t)n + (size_t)n * nb));
-      for (unsigned j = 0; j < m; ++j) {
-        uint8_t *at = bytes.data() + (size_t)j * ((size_t)n + (size_t)n * nb);
-        randombytes(at, n);                                                                 // sample_error, :87
-        randombytes(at + n, (size_t)n * nb);                                                // sample_uniform(P q_L), :94
+      std::vector<uint8_t> bytes(drawn ? 0 : (size_t)m * ((size_t)n + (size_t)n * nb));
+      DevBuf db((size_t)m * ((size_t)n + (size_t)n * nb));
+      if (drawn) {                                                                          // the same slices of one stream, made where they are read
+        if (gpq_randombytes_device(c, (uint8_t *)db.p, (size_t)m * ((size_t)n + (size_t)n * nb), nullptr) != GPQ_OK) die("he_gen*k: generating the random bytes on the device failed");
+      } else {
+        for (unsigned j = 0; j < m; ++j) {
+          uint8_t *at = bytes.data() + (size_t)j * ((size_t)n + (size_t)n * nb);
+          randombytes(at, n);                                                               // sample_error, :87
+          randombytes(at + n, (size_t)n * nb);                                              // sample_uniform(P q_L), :94
+        }
+        if (gpq_upload(db.p, bytes.data(), bytes.size(), nullptr) != GPQ_OK) die("upload failed");
       }
-      DevBuf db(bytes.size());
-      if (gpq_upload(db.p, bytes.data(), bytes.size(), nullptr) != GPQ_OK) die("upload failed");
       for (unsigned j = 0; j < m; ++j) {
         const uint8_t *at = (const uint8_t *)db.p + (size_t)j * ((size_t)n + (size_t)n * nb);
         if (gpq_sample_error(c, (int8_t *)de.p + (size_t)j * n, at, 1, nullptr) != GPQ_OK ||

@@ -479,6 +479,13 @@ class PolyContext:
         _native.check(self.lib.gpq_sample_uniform(self.h, self._ptr(big), self._ptr(bytes_dev), nbits, W, count, self._stream()), "gpq_sample_uniform")
         return big
 
+    def surf_bytes(self, bytes_dev, pos=0, seed=None):
+        """bytes [pos, pos + len) of the reference's deterministic randombytes stream (src/rng.c:36-77) for `seed` (32 words; None: the
+        reference's) into bytes_dev, a uint8 tensor on the device at any byte address.  pos: a Python integer below 2^128."""
+        _native.check(self.lib.gpq_surf_bytes(self.h, self._ptr(bytes_dev), bytes_dev.numel(), _seed_words(seed), pos & _M64, pos >> 64, self._stream()),
+                      "gpq_surf_bytes")
+        return bytes_dev
+
     def small_to_big(self, big, small, W):
         """an int8 small slab [count][n] sign-extended into a big slab [count][W][n]"""
         _native.check(self.lib.gpq_small_to_big(self.h, self._ptr(big), self._ptr(small), W, small.numel() // self.n, self._stream()), "gpq_small_to_big")
@@ -714,6 +721,62 @@ def ecd_roots(slots):
     table = np.empty((4 * slots + 1, 2), dtype=np.float64)
     _native.check(_native.load().gpq_ecd_roots(table.ctypes.data_as(C.c_void_p), slots), "gpq_ecd_roots")
     return table
+
+
+_M64 = (1 << 64) - 1
+
+
+def _seed_words(seed):
+    if seed is None:
+        return None
+    words = np.ascontiguousarray(seed, dtype=np.uint32)
+    if words.shape != (32,):
+        raise ValueError("a seed is 32 words of 32 bits")
+    return words.ctypes.data_as(C.c_void_p)
+
+
+def surf_bytes_host(length, pos=0, seed=None):
+    """bytes [pos, pos + length) of the reference's deterministic randombytes stream on the CPU (gpq_surf_bytes_host): no device needed"""
+    out = np.empty(length, dtype=np.uint8)
+    _native.check(_native.load().gpq_surf_bytes_host(out.ctypes.data_as(C.c_void_p), length, _seed_words(seed), pos & _M64, pos >> 64), "gpq_surf_bytes_host")
+    return out
+
+
+class Rng:
+    """gpq_rng: one stream of the reference's deterministic randombytes with a position; host and device draws advance it alike."""
+
+    def __init__(self, seed=None, pos=0):
+        self.lib = _native.load()
+        h = C.c_void_p()
+        _native.check(self.lib.gpq_rng_create(C.byref(h), _seed_words(seed)), "gpq_rng_create")
+        self.h = h
+        if pos:
+            self.seek(pos)
+
+    def seek(self, pos):
+        _native.check(self.lib.gpq_rng_seek(self.h, pos & _M64, pos >> 64), "gpq_rng_seek")
+
+    def tell(self):
+        pos = (C.c_uint64 * 2)()
+        _native.check(self.lib.gpq_rng_tell(self.h, pos), "gpq_rng_tell")
+        return int(pos[0]) | (int(pos[1]) << 64)
+
+    def host_bytes(self, length):
+        out = np.empty(length, dtype=np.uint8)
+        _native.check(self.lib.gpq_rng_host_bytes(self.h, out.ctypes.data_as(C.c_void_p), length), "gpq_rng_host_bytes")
+        return out
+
+    def device_bytes(self, ctx, bytes_dev):
+        """the next bytes_dev.numel() bytes into a uint8 tensor on ctx's device, on the current stream"""
+        _native.check(self.lib.gpq_rng_device_bytes(ctx.h, self.h, ctx._ptr(bytes_dev), bytes_dev.numel(), ctx._stream()), "gpq_rng_device_bytes")
+        return bytes_dev
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.gpq_rng_destroy(self.h)
+            self.h = None
+
+    __del__ = close
 
 
 def sample_error_table():

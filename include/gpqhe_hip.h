@@ -553,6 +553,38 @@ int gpq_he_enc_pk(gpq_ctx *ctx, uint64_t *out_c0, uint64_t *out_c1, const uint64
 int gpq_he_enc_sk(gpq_ctx *ctx, uint64_t *out_c0, uint64_t *out_c1, const uint64_t *m, const uint64_t *a, const int8_t *e,
                   const uint64_t *sk_ntt, unsigned W, unsigned logq, unsigned dim, unsigned batch, void *workspace, void *stream);
 
+/* ---- random bytes on the device ("Random bytes on the device") ---------------------------------------------------------------
+ * The samplers above take the caller's bytes; these calls make the bytes the reference's default build would have drawn -- its deterministic
+ * randombytes, src/rng.c:36-77 (SUPERCOP's surf generator, -DSUPERCOP) -- where the samplers read them.  The library still invents no entropy:
+ * a stream is a function of the caller's 32-word seed and nothing else; seed == NULL is the reference's own seed (src/rng.c:36-38), public test
+ * data.  The generator runs in counter mode (a 128-bit block counter, incremented before each block of 8 bytes), so a stream is addressed by a
+ * 128-bit BYTE position (pos_lo, pos_hi): byte k is the low byte of out[7 - k % 8] of the block with counter k / 8 + 1, and the first call of
+ * the reference's randombytes(x, len) in a process returns the bytes [0, len).  A 128-bit byte position cannot overflow the block counter.
+ * The other randombytes variants of src/rng.c (RANDOM, GCRY_RANDOM, AES256) are non-deterministic or sequential and have no counterpart here.
+ * gpq_surf_bytes: bytes [pos, pos + len) of the stream into bytes_dev[0..len), device memory at any byte address; no byte outside it is
+ *   written.  Where (address - pos) % 8 == 0 every aligned 16 bytes leave as one store (a 16-byte aligned buffer filled from a position
+ *   that is a multiple of 8: the fast case); any other combination gives the same bytes more slowly.  Asynchronous on `stream`, no
+ *   allocation, no synchronisation: capturable -- and seed and position are launch arguments, so a REPLAYED graph repeats its bytes.
+ *   More than 2^30 bytes run as several launches.
+ * gpq_surf_bytes_host: the same bytes into host memory on one CPU thread (the rate of the reference's randombytes); no device needed.
+ * gpq_rng: a stream with a position.  gpq_rng_host_bytes / gpq_rng_device_bytes hand out the next len bytes and advance the position
+ *   (the device call when its launches are queued: what it reserved is spent even if a captured graph is never replayed); calls of both
+ *   kinds on one object, in any mix, give one contiguous slice.  An object serialises its callers (a mutex); the device work is ordered by
+ *   `stream` as usual.  gpq_rng_seek / gpq_rng_tell set and read the position (pos[0] low, pos[1] high).
+ * GPQ_ERR_INVALID before anything is launched or written for: a null pointer (except seed), len = 0, pos + len beyond 2^128, and for the
+ * device calls the wrong current device.
+ * gpq_debug_rng_split: tests: the bytes of one launch (a multiple of 16; 0 = the default 2^30).  Process-wide. */
+typedef struct gpq_rng gpq_rng;
+int gpq_surf_bytes(gpq_ctx *ctx, uint8_t *bytes_dev, size_t len, const uint32_t seed[32], uint64_t pos_lo, uint64_t pos_hi, void *stream);
+int gpq_surf_bytes_host(uint8_t *x, size_t len, const uint32_t seed[32], uint64_t pos_lo, uint64_t pos_hi);
+int gpq_rng_create(gpq_rng **rng, const uint32_t seed[32]);
+void gpq_rng_destroy(gpq_rng *rng);
+int gpq_rng_seek(gpq_rng *rng, uint64_t pos_lo, uint64_t pos_hi);
+int gpq_rng_tell(const gpq_rng *rng, uint64_t pos[2]);
+int gpq_rng_host_bytes(gpq_rng *rng, uint8_t *x, size_t len);
+int gpq_rng_device_bytes(gpq_ctx *ctx, gpq_rng *rng, uint8_t *bytes_dev, size_t len, void *stream);
+int gpq_debug_rng_split(size_t bytes);
+
 /* ---- general moduli: any q_l (little-endian words ql_words[0..Lq)) and any Delta (uint64_t, as hectx_init takes it,
  * src/gpqhe.h:100).  Same reference semantics, through the multiword Barrett kernel: slow-path quality, meant for parameter
  * sets outside the powers of two that the fast entry points above cover. */

@@ -16,6 +16,7 @@
 #ifndef GPQHE_HIP_COMPAT_H
 #define GPQHE_HIP_COMPAT_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -158,6 +159,29 @@ void he_enc_sk(struct he_ct *ct, const struct he_pt *pt, const poly_mpi_t *sk);
  * sample_sk stays the host's.  Without a randombytes in the program the host's samplers are used as before, without an error.
  * OPT-IN (default 0): a host whose samplers are not the reference's would get other polynomials from the same bytes. */
 void gpq_mpi_shim_set_device_samplers(int on);
+/* The process-wide default stream of the reference's deterministic randombytes (src/rng.c:36-77; gpqhe_hip.h, "random bytes on the device"):
+ * the reference's seed from byte position 0, guarded by a mutex of its own.  gpq_randombytes is the HOST path: the next xlen bytes, exactly
+ * what the reference's SUPERCOP randombytes returns call for call.  The library exports NO symbol named `randombytes` (a definition here
+ * would shadow the host program's own, whatever the link order: INTEGRATION.md); a GPQHE build that wants host and device to draw from ONE
+ * stream forwards the body of its SUPERCOP randombytes under its GPQHE_HIP guard:
+ *     void randombytes(uint8_t *x, size_t xlen) { gpq_randombytes(x, xlen); }
+ * gpq_randombytes_seek / _tell: the position as gpq_rng_seek / gpq_rng_tell take it; gpq_randombytes_seed: another seed (NULL: the
+ * reference's) and position 0.  gpq_randombytes_device: the next len bytes of the same stream into device memory (gpq_rng_device_bytes on
+ * the default stream; `ctx` e.g. gpq_mpi_shim_engine()). */
+struct gpq_ctx;
+void gpq_randombytes(uint8_t *x, size_t xlen);
+int gpq_randombytes_seek(uint64_t pos_lo, uint64_t pos_hi);
+int gpq_randombytes_tell(uint64_t pos[2]);
+int gpq_randombytes_seed(const uint32_t seed[32]);
+int gpq_randombytes_device(struct gpq_ctx *ctx, uint8_t *bytes_dev, size_t len, void *stream);
+/* on != 0, together with gpq_mpi_shim_set_device_samplers(1): he_keypair / he_enc_pk / he_enc_sk / he_genrlk / he_genck / he_genrk do not call
+ * the host's randombytes for their samplers' bytes at all.  They reserve the same byte counts, in the reference's order, from the default
+ * stream above and generate them in device memory -- one gpq_randombytes_device per encryption or per group of keys, no host buffer, no
+ * upload.  sample_sk stays the host's; a host whose randombytes forwards to gpq_randombytes draws it from the same stream, and then keys and
+ * ciphertexts are those of the reference run on that seed.  A host whose randombytes does NOT forward keeps its own stream for sample_sk and
+ * gets the sampler bytes from the default stream: another, equally valid, draw -- but not the one its own randombytes would have given.
+ * OPT-IN (default 0), different in kind like gpq_mpi_shim_set_device_ecd: the bytes are the library's stream's, not the host program's. */
+void gpq_mpi_shim_set_device_rng(int on);
 void he_conj(he_ct_t *ct, const he_evk_t *ck);                                          /* src/gpqhe.h:151  */
 void he_rot(he_ct_t *ct, const int rot, const he_evk_t *rk);                            /* src/gpqhe.h:152  */
 /* src/he-algo.c:47-113: the baby steps as one hoisted call, the whole body on the device (gpq_he_gemv) for power-of-two q_l, q_(l-1); the
