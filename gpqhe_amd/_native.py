@@ -171,6 +171,13 @@ SIGNATURES = {
     "gpq_gemv_inner": (C.c_int, [vp] * 6 + [C.c_uint] * 3 + [vp, vp]),
     "gpq_he_gemv_planned_workspace_bytes": (C.c_size_t, [vp, vp] + [C.c_uint] * 4),
     "gpq_he_gemv_planned": (C.c_int, [vp] * 8 + [C.c_uint] * 5 + [vp, vp]),
+    "gpq_gemv_multi_width": (C.c_uint, []),
+    "gpq_gemv_multi_create": (C.c_int, [vp, C.POINTER(vp), vp, C.c_uint, vp]),
+    "gpq_gemv_multi_destroy": (None, [vp]),
+    "gpq_gemv_multi_info": (C.c_int, [vp, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_size_t)]),
+    "gpq_gemv_multi_rotations": (C.c_int, [vp, vp]),
+    "gpq_he_gemv_multi_workspace_bytes": (C.c_size_t, [vp, vp] + [C.c_uint] * 4),
+    "gpq_he_gemv_multi": (C.c_int, [vp] * 8 + [C.c_uint] * 5 + [vp, vp]),
     "gpq_profile_enable": (C.c_int, [vp, C.c_int]),
     "gpq_profile_kernels": (C.c_int, []),
     "gpq_profile_kernel_name": (C.c_char_p, [C.c_int]),

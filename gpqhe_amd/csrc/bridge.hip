@@ -531,6 +531,7 @@ extern "C" int gpq_he_gemv(gpq_ctx *c, uint64_t *out_c0, uint64_t *out_c1, const
 }
 
 #include "gemv_plan.hpp"   // he_gemv for a fixed matrix: gpq_gemv_plan_*, gpq_gemv_inner, gpq_he_gemv_planned
+#include "gemv_multi.hpp"  // ... for several fixed matrices on the same ciphertexts: gpq_gemv_multi_*, gpq_he_gemv_multi
 
 // Tail of he_relin / he_swk alone (src/he-mult.c:67-77): out = smod(rdiv(poly_rns2mpi(chat, P*q_l), P) + d, q_l).
 extern "C" size_t gpq_relin_tail_workspace_bytes(gpq_ctx *c, unsigned W, unsigned dimB, unsigned dimP, unsigned batch) {

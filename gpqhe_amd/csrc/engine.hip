@@ -429,7 +429,7 @@ static const char *const kKernelNames[GPQ_K_COUNT] = {"strided_fwd", "strided_in
                                                       "bridge_decompose", "bridge_reconstruct", "bridge_relin_front", "bridge_relin_tail_fused", "bridge_exact_paths", "bridge_rescale",
                                                       "bridge_relin_tail_direct", "bridge_crt_decompose", "bridge_tail_stream",
                                                       "keyswitch_rot_mid", "automorphism_gather", "gemv_mac", "he_ecd_lds", "he_dcd_lds",
-                                                      "sample_bytes", "enc_small_tail", "genswk_crt_tail", "surf_stream"};
+                                                      "sample_bytes", "enc_small_tail", "genswk_crt_tail", "surf_stream", "gemv_mac_multi"};
 
 int check_shape(const gpq_ctx *c, unsigned dim, unsigned batch, const char *who) {
   if (!c) return gpq_fail(GPQ_ERR_INVALID, "%s: null context", who);
@@ -1053,6 +1053,28 @@ int gpq_gemv_mac(gpq_ctx *c, uint64_t *acc0, uint64_t *acc1, const uint64_t *r0,
     hipLaunchKernelGGL((gemv_mac<BT, decltype(nt)::value>), grid, dim3(256), 0, s, a);
   });
   return after_launch("gemv_mac");
+}
+
+// The same sums for up to GPQ_GEMV_MULTI_NP plans on the same rotations (ntt_kernels.hpp: gemv_mac_multi), one launch: the grid spans the
+// largest dim among the plans present, and a workgroup skips the plans that end below its limb.
+int gpq_gemv_mac_multi(gpq_ctx *c, const gpq_gemv_multi_arg *plans, const uint64_t *r0, const uint64_t *r1, const unsigned *entries,
+                       unsigned nentries, unsigned rdim, unsigned polys, hipStream_t s) {
+  constexpr int BT = GPQ_GEMV_MULTI_BT, NP = GPQ_GEMV_MULTI_NP;
+  GemvMacMultiArgs<NP> a;
+  a.tabs = c->d_tabs; a.r0 = r0; a.r1 = r1; a.entries = entries;
+  a.nentries = nentries; a.polys = polys; a.rdim = rdim; a.logn = c->logn;
+  unsigned dim = 0;
+  for (int t = 0; t < NP; ++t) {
+    a.plan[t] = {plans[t].diag, plans[t].acc0, plans[t].acc1, plans[t].dim};
+    if (plans[t].dim > dim) dim = plans[t].dim;
+  }
+  if (!dim || dim > rdim || !nentries || !polys) return gpq_fail(GPQ_ERR_INVALID, "gemv_mac_multi: no plan, no term or a plan of more limbs than the rotations");
+  const dim3 grid((polys + BT - 1) / BT, c->n >= 512 ? c->n / 512 : 1, dim);
+  ProfScope prof(c, GPQ_K_GEMV_MAC_MULTI, s);
+  with_nt(nt_for(c, (size_t)polys * nentries, rdim, 2), [&](auto nt) {
+    hipLaunchKernelGGL((gemv_mac_multi<BT, NP, decltype(nt)::value>), grid, dim3(256), 0, s, a);
+  });
+  return after_launch("gemv_mac_multi");
 }
 
 // Which butterflies a limb runs is decided by its c = p - 2^59 (modarith.hpp): the first `wide` limbs the wide-split ones, the

@@ -96,7 +96,9 @@ enum { GPQ_K_STRIDED_FWD = 0, GPQ_K_STRIDED_INV, GPQ_K_CONTIG_FWD, GPQ_K_CONTIG_
        // gpq_he_genswk_batch: the CRT recombination of a switching key mod P 2^k (genswk_crt_tail, genswk_kernels.hpp)
        GPQ_K_GENSWK_TAIL,
        // the reference's deterministic randombytes by position (surf_stream_k, rng_kernels.hpp): a class of its own, so that the samplers' times stay theirs
-       GPQ_K_RNG, GPQ_K_COUNT };
+       GPQ_K_RNG,
+       // gpq_he_gemv_multi: one giant step's inner sums for several plans on the same ciphertexts (gemv_mac_multi)
+       GPQ_K_GEMV_MAC_MULTI, GPQ_K_COUNT };
 
 // Constant matrix of the matrix-core CRT fast path for one basis and result width WL (bridge_mfma.hpp)
 struct gpq_recon_mfma {
@@ -343,6 +345,20 @@ int gpq_keyswitch_scaled(gpq_ctx *c, uint64_t *c0, uint64_t *c1, const uint64_t 
 // pairs (device array) of r0 / r1[slot][polys][dim][n] (*) diag[diagonal][dim][n], all in the NTT domain; canonical output, ONE launch.
 int gpq_gemv_mac(gpq_ctx *c, uint64_t *acc0, uint64_t *acc1, const uint64_t *r0, const uint64_t *r1, const uint64_t *diag,
                  const void *terms, unsigned nterms, unsigned dim, unsigned polys, hipStream_t s);
+// he_gemv for several plans on the same ciphertexts (engine.hip; gemv_multi.hpp's gpq_he_gemv_multi): the sums of gpq_gemv_mac for up to
+// GPQ_GEMV_MULTI_NP plans in ONE launch that reads every rotation once.  r0 / r1[union slot][polys][rdim][n]; entries (device) =
+// nentries x (1 + NP) words: the union slot, then per plan its diagonal or 0xffffffff where the plan has no live diagonal on that slot.
+// plans[t].dim = 0: nothing at position t (neither read nor written); else the plan's diagonals and sums lie over its own dim <= rdim limbs.
+// (BT, NP) = (4, 2): 118 VGPRs, no scratch -- DESIGN.md, "he_gemv for several matrices", has the other instantiations.
+#ifndef GPQ_GEMV_MULTI_BT
+#define GPQ_GEMV_MULTI_BT 4
+#endif
+#ifndef GPQ_GEMV_MULTI_NP
+#define GPQ_GEMV_MULTI_NP 2
+#endif
+struct gpq_gemv_multi_arg { const uint64_t *diag; uint64_t *acc0, *acc1; unsigned dim; };
+int gpq_gemv_mac_multi(gpq_ctx *c, const gpq_gemv_multi_arg *plans, const uint64_t *r0, const uint64_t *r1, const unsigned *entries,
+                       unsigned nentries, unsigned rdim, unsigned polys, hipStream_t s);
 // gpq_he_dec (bridge.hip): r[k] = x[k] (*) key for `polys` polynomials of `dim` limbs and ONE key slab uint64_t[dim][n] shared by all of them
 // (pointwise<true, true>: the second operand is read without the polynomial's offset); r may alias x.
 int gpq_rns_mul_shared(gpq_ctx *c, uint64_t *r, const uint64_t *x, const uint64_t *key, unsigned dim, unsigned polys, hipStream_t s);

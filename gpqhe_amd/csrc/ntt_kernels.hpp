@@ -1023,6 +1023,77 @@ __global__ __launch_bounds__(256) void gemv_mac(GemvMacArgs a) {
     }
 }
 
+// The same inner sums for up to NP plans that are applied to the SAME ciphertexts (gpq_he_gemv_multi): the transformed rotations are what
+// the plans share, so a workgroup walks the step's union of rotation slots, loads the 2 BT words of a slot once and accumulates them into
+// every plan of the group that has a live diagonal there.  entries[e] = (union slot, diagonal of plan 0, ..., diagonal of plan NP-1), a
+// diagonal of GEMV_NOT_LIVE = that plan does not read the slot in this step: uniform, scalar loads.  The plans may differ in `dim`: the
+// rotations lie over rdim >= every dim limbs per polynomial, each plan's diagonals and sums over its own; a plan whose dim is not above
+// blockIdx.z is skipped (dim = 0: no plan at this position, or no live term in this step -- nothing is stored for it).  The arithmetic is
+// gemv_mac's word for word, and the sums leave canonical, so which terms share a launch cannot change a word.
+template <int NP>
+struct GemvMacMultiArgs {
+  const LimbTab *tabs;
+  const uint64_t *r0, *r1;            // [union slot][polys][rdim][n]
+  const unsigned *entries;            // [nentries][1 + NP]
+  struct Plan {
+    const uint64_t *diag;             // [slots][dim][n]
+    uint64_t *acc0, *acc1;            // [polys][dim][n]
+    unsigned dim;
+  } plan[NP];
+  unsigned nentries, polys, rdim, logn;
+};
+template <int BT, int NP, bool NT>
+__global__ __launch_bounds__(256) void gemv_mac_multi(GemvMacMultiArgs<NP> a) {
+  const unsigned limb = blockIdx.z;
+  const PrimeK k = pin_consts(a.tabs[limb].k);
+  const unsigned i2 = 2 * (blockIdx.y * 256 + threadIdx.x);
+  if (i2 >= (1u << a.logn)) return;
+  const unsigned b0 = blockIdx.x * BT, cnt = a.polys - b0 < (unsigned)BT ? a.polys - b0 : (unsigned)BT;   // b0 < polys by the grid
+  const size_t limb_off = ((size_t)limb << a.logn) + i2, rpoly = (size_t)a.rdim << a.logn;
+  v2u64 s0[NP][BT], s1[NP][BT];
+#pragma unroll
+  for (int t = 0; t < NP; ++t)
+#pragma unroll
+    for (int b = 0; b < BT; ++b) s0[t][b] = s1[t][b] = v2u64{0, 0};
+  for (unsigned e = 0; e < a.nentries; ++e) {
+    const unsigned *ent = a.entries + (size_t)e * (1 + NP);
+    const size_t roff = ((size_t)ent[0] * a.polys + b0) * rpoly + limb_off;
+    v2u64 u[BT], v[BT];
+#pragma unroll
+    for (int b = 0; b < BT; ++b)
+      if (b < (int)cnt) {
+        u[b] = gemv_ld16<NT>(reinterpret_cast<const v2u64 *>(a.r0 + roff + b * rpoly));
+        v[b] = gemv_ld16<NT>(reinterpret_cast<const v2u64 *>(a.r1 + roff + b * rpoly));
+      }
+#pragma unroll
+    for (int t = 0; t < NP; ++t) {
+      const unsigned dg = ent[1 + t];
+      if (dg == GEMV_NOT_LIVE || limb >= a.plan[t].dim) continue;
+      const v2u64 d = *reinterpret_cast<const v2u64 *>(a.plan[t].diag + (((size_t)dg * a.plan[t].dim) << a.logn) + limb_off);
+#pragma unroll
+      for (int b = 0; b < BT; ++b)
+        if (b < (int)cnt) {
+          s0[t][b].x = csub4(s0[t][b].x + mulmod_lazy(u[b].x, d.x, k), k);
+          s0[t][b].y = csub4(s0[t][b].y + mulmod_lazy(u[b].y, d.y, k), k);
+          s1[t][b].x = csub4(s1[t][b].x + mulmod_lazy(v[b].x, d.x, k), k);
+          s1[t][b].y = csub4(s1[t][b].y + mulmod_lazy(v[b].y, d.y, k), k);
+        }
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < NP; ++t) {
+    if (limb >= a.plan[t].dim) continue;
+    const size_t poly = (size_t)a.plan[t].dim << a.logn;
+#pragma unroll
+    for (int b = 0; b < BT; ++b)
+      if (b < (int)cnt) {
+        const size_t o = (size_t)(b0 + b) * poly + limb_off;
+        *reinterpret_cast<v2u64 *>(a.plan[t].acc0 + o) = v2u64{canon4(s0[t][b].x, k), canon4(s0[t][b].y, k)};
+        *reinterpret_cast<v2u64 *>(a.plan[t].acc1 + o) = v2u64{canon4(s1[t][b].x, k), canon4(s1[t][b].y, k)};
+      }
+  }
+}
+
 // contig_pass in the 8-per-lane geometry (n = 2^17): CONTIG8_POLYS polynomials of the same limb and tile share each twiddle group.
 constexpr int CONTIG8_POLYS = 2;
 template <bool INV, typename TW, int LOW, bool NT = false>

@@ -11,6 +11,9 @@ struct LimbTab {           // per-prime scalars, array resident in HBM (read wit
   TwS ninv_s, winv1_ninv_s;  // the same two as split-twiddle constants (modarith.hpp); unset for c >= GPQ_SPLIT_CMAX
 };
 
+// gemv_mac_multi's entry tables (ntt_kernels.hpp, gemv_multi.hpp): the diagonal of a plan that reads nothing at that union slot
+constexpr unsigned GEMV_NOT_LIVE = 0xffffffffu;
+
 #define GPQ_MAX_SLABS 4
 struct PassArgs {
   const LimbTab *tabs;               // tabs[limb0 + blockIdx.z]

@@ -540,6 +540,27 @@ class PolyContext:
                                                    self._key_ptrs(rk1), W, logDelta, dimB, dimP, batch, self._ptr(ws), self._stream()), "gpq_he_gemv_planned")
         return ws
 
+    def gemv_multi(self, plans):
+        """A set of GemvPlans of this context (same slots and logql) that he_gemv_multi applies to the same ciphertexts; it borrows them."""
+        return GemvMulti(self, plans)
+
+    def he_gemv_multi(self, outs0, outs1, c0, c1, multi, rk0, rk1, W, logDelta, dimB, dimP, workspace=None):
+        """he_gemv_planned for every plan of `multi` on the same ciphertexts, with the baby rotations and their transforms shared: outs0[t] /
+        outs1[t] get what he_gemv_planned writes for plan t.  Keys outside multi.rotations() may be None."""
+        torch = _torch()
+        batch = c0.numel() // (W * self.n)
+        if len(outs0) != multi.count or len(outs1) != multi.count:
+            raise ValueError("%d plans need %d outputs, not %d and %d" % (multi.count, multi.count, len(outs0), len(outs1)))
+        ws = workspace
+        if ws is None:
+            nbytes = self.lib.gpq_he_gemv_multi_workspace_bytes(self.h, multi.h, W, dimB, dimP, batch)
+            if not nbytes:
+                raise _native.GpqError("gpq_he_gemv_multi_workspace_bytes: " + self.lib.gpq_last_error().decode())
+            ws = torch.empty(nbytes // 8 + 8, dtype=torch.int64, device=self._dev)
+        _native.check(self.lib.gpq_he_gemv_multi(self.h, self._key_ptrs(outs0), self._key_ptrs(outs1), self._ptr(c0), self._ptr(c1), multi.h, self._key_ptrs(rk0),
+                                                 self._key_ptrs(rk1), W, logDelta, dimB, dimP, batch, self._ptr(ws), self._stream()), "gpq_he_gemv_multi")
+        return ws
+
     def poly_rot(self, r, a, W, rot):
         _native.check(self.lib.gpq_poly_rot(self.h, self._ptr(r), self._ptr(a), W, rot, a.numel() // (W * self.n), self._stream()), "gpq_poly_rot")
         return r
@@ -628,6 +649,40 @@ class PolyContext:
         _native.check(self.lib.gpq_keyswitch(self.h, self._ptr(c0), self._ptr(c1), self._ptr(x), self._ptr(evk0), self._ptr(evk1),
                                              dim, batch, self._ptr(ws), self._stream()), "gpq_keyswitch")
         return c0, c1
+
+
+class GemvMulti:
+    """gpq_gemv_multi: a set of GemvPlans applied to the same ciphertexts by Context.he_gemv_multi.  `.count` plans, `.baby` rotations in the
+    union of their live baby steps, `.dim` the largest of their dims, `.bytes` of index tables on the device.  The set borrows the plans
+    (it keeps them referenced); `close()` (or leaving a `with` block) frees its tables."""
+
+    def __init__(self, ctx, plans):
+        self.lib, self.h, self.plans = ctx.lib, C.c_void_p(), list(plans)
+        self.slots = self.plans[0].slots if self.plans else 0
+        ptrs = (C.c_void_p * max(len(self.plans), 1))(*[p.h.value for p in self.plans])
+        _native.check(self.lib.gpq_gemv_multi_create(ctx.h, C.byref(self.h), ptrs, len(self.plans), ctx._stream()), "gpq_gemv_multi_create")
+        count, baby, dim, nbytes = C.c_uint(), C.c_uint(), C.c_uint(), C.c_size_t()
+        _native.check(self.lib.gpq_gemv_multi_info(self.h, C.byref(count), C.byref(baby), C.byref(dim), C.byref(nbytes)), "gpq_gemv_multi_info")
+        self.count, self.baby, self.dim, self.bytes = count.value, baby.value, dim.value, nbytes.value
+
+    def rotations(self):
+        """needed[r] for every rotation r < slots whose key he_gemv_multi reads: the union over the plans"""
+        needed = (C.c_ubyte * self.slots)()
+        _native.check(self.lib.gpq_gemv_multi_rotations(self.h, needed), "gpq_gemv_multi_rotations")
+        return [int(v) for v in needed]
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.gpq_gemv_multi_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 class GemvPlan:
@@ -809,6 +864,11 @@ def automorphism_index(logn, g):
     idx = np.empty(1 << logn, dtype=np.uint32)
     _native.check(lib.gpq_automorphism_index(logn, g, idx.ctypes.data_as(C.c_void_p)), "gpq_automorphism_index")
     return idx
+
+
+def gemv_multi_width():
+    """plans that share one gemv_mac_multi launch in he_gemv_multi (include/gpqhe_hip.h: gpq_gemv_multi_width).  No device."""
+    return int(_native.load().gpq_gemv_multi_width())
 
 
 def gemv_steps(slots):

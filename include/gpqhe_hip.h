@@ -427,6 +427,36 @@ int gpq_he_gemv_planned(gpq_ctx *ctx, uint64_t *out_c0, uint64_t *out_c1, const 
                         const uint64_t *const *rk0, const uint64_t *const *rk1, unsigned W, unsigned logDelta, unsigned dimB, unsigned dimP,
                         unsigned batch, void *workspace, void *stream);
 
+/* ---- he_gemv for several matrices: a SET of plans applied to the same ciphertexts ("he_gemv for several matrices") ----------
+ * A tall matrix of k slots rows, the four products of he_coeff2slot, several heads on one input: k plans, one ciphertext.  What k calls of
+ * gpq_he_gemv_planned repeat depends on the ciphertext alone -- the hoisted baby rotations, their rns_decompose + forward transform, and
+ * the reads of those transforms inside every giant step -- and gpq_he_gemv_multi does it once: ONE gpq_he_rot_hoisted over the union of the
+ * plans' live baby rotations, one decomposition + transform over the largest `dim`, and per giant step one gemv_mac_multi launch per group
+ * of gpq_gemv_multi_width() plans that loads every rotation word once for the group.  Behind the inner sums every plan runs what
+ * gpq_he_gemv_planned runs (inverse transform, two reconstructions over its own dim, the rotation by i n1, the wrapping sum, he_rs); the
+ * giant rotations of different plans are NOT stacked into one key switch.  out_c0[t] / out_c1[t] are word for word what
+ * gpq_he_gemv_planned writes for plans[t]: the sums leave the kernel as canonical residues of the same terms.
+ * gpq_gemv_multi_create: `count` plans (1..16; the same plan may appear twice) of this context, all exact, with the same slots and logql
+ *   (their `dim` may differ); GPQ_ERR_INVALID otherwise, or when `stream` is capturing, before anything is allocated.  The set BORROWS the
+ *   plans: they outlive it.  It holds only small index tables on the device (`bytes`), built once so that the call uploads nothing: the
+ *   diagonals stay in the plans.  `baby` = the size of the union of live baby rotations, `dim` = the largest dim among the plans.
+ * gpq_gemv_multi_rotations: needed[r] = 1 for every rotation r < slots that some plan of the set needs (the union of
+ *   gpq_gemv_plan_rotations); rk0[r] / rk1[r] may be NULL for the others.
+ * gpq_he_gemv_multi: out_c0 / out_c1 = host arrays of `count` device slabs of batch x W x n words.  Launch groups of gpq_set_chunk (the
+ *   words do not depend on the grouping).  A plan without a live diagonal writes exact zeros.  GPQ_ERR_INVALID before anything is launched
+ *   for a null argument or output, a set of another context, W words that cannot hold q_l, logDelta >= logql, an output that overlaps an
+ *   input or another output, or a NULL key of the union.  Allocates no device memory and does not synchronise. */
+typedef struct gpq_gemv_multi gpq_gemv_multi;
+unsigned gpq_gemv_multi_width(void);
+int gpq_gemv_multi_create(gpq_ctx *ctx, gpq_gemv_multi **set, const gpq_gemv_plan *const *plans, unsigned count, void *stream);
+void gpq_gemv_multi_destroy(gpq_gemv_multi *set);
+int gpq_gemv_multi_info(const gpq_gemv_multi *set, unsigned *count, unsigned *baby, unsigned *dim, size_t *bytes);
+int gpq_gemv_multi_rotations(const gpq_gemv_multi *set, unsigned char *needed);
+size_t gpq_he_gemv_multi_workspace_bytes(gpq_ctx *ctx, const gpq_gemv_multi *set, unsigned W, unsigned dimB, unsigned dimP, unsigned batch);
+int gpq_he_gemv_multi(gpq_ctx *ctx, uint64_t *const *out_c0, uint64_t *const *out_c1, const uint64_t *c0, const uint64_t *c1,
+                      const gpq_gemv_multi *set, const uint64_t *const *rk0, const uint64_t *const *rk1, unsigned W, unsigned logDelta,
+                      unsigned dimB, unsigned dimP, unsigned batch, void *workspace, void *stream);
+
 /* ---- he_ecd on the device ("Encoding on the device") ----------------------------------------------------------------------
  * he_ecd, src/he-encode.c:53-64 and :107-111 with invcanemb, src/canemb.c:62-81: `slots` complex doubles -> the plaintext polynomial as a
  * big slab, one workgroup per vector (he_ecd_lds).  The butterflies are the reference's, every double operation rounded on its own (no
