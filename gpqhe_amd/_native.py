@@ -108,6 +108,10 @@ SIGNATURES = {
     "gpq_relin_tail_overwriting": (C.c_int, [vp, vp, vp, vp, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_uint, vp, vp]),
     "gpq_he_mulpt_workspace_bytes": (C.c_size_t, [vp, C.c_uint, C.c_uint]),
     "gpq_he_mulpt": (C.c_int, [vp] * 6 + [C.c_uint] * 4 + [vp, vp]),
+    "gpq_const_pt": (C.c_int, [C.c_double, C.c_double, C.c_uint, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "gpq_he_mulpt_const_fits": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_uint, C.c_uint]),
+    "gpq_he_mulpt_const": (C.c_int, [vp] * 5 + [C.c_int64, C.c_int64] + [C.c_uint] * 5 + [vp, vp]),
+    "gpq_he_addpt_const": (C.c_int, [vp] * 5 + [C.c_int64, C.c_int64, C.c_int] + [C.c_uint] * 3 + [vp]),
     "gpq_poly_rot": (C.c_int, [vp, vp, vp, C.c_uint, C.c_uint, C.c_uint, vp]),
     "gpq_poly_conj": (C.c_int, [vp, vp, vp, C.c_uint, C.c_uint, vp]),
     "gpq_he_general_workspace_bytes": (C.c_size_t, [vp, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_uint]),
@@ -209,6 +213,8 @@ SIGNATURES = {
     "gpq_mpi_shim_resident_polys": (C.c_uint, []),
     "gpq_mpi_shim_poly_stats": (None, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "gpq_mpi_shim_forget_polys": (None, []),
+    "gpq_mpi_shim_set_const_pt": (None, [C.c_int]),
+    "gpq_mpi_shim_const_pt_stats": (None, [C.POINTER(C.c_ulong), C.POINTER(C.c_ulong)]),
     "gpq_mpi_shim_set_conversion_threads": (C.c_uint, [C.c_uint]),
     "gpq_mpi_shim_poly_bypass": (None, [C.c_int]),
     "gpq_mpi_shim_set_direct_mpi": (C.c_int, [C.c_int]),

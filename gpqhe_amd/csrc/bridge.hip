@@ -7,8 +7,10 @@
 #include "bridge_mfma.hpp"
 #include "bridge_stream.hpp"
 #include "genswk_kernels.hpp"
+#include "constpt_kernels.hpp"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
@@ -686,6 +688,79 @@ extern "C" int gpq_he_mulpt(gpq_ctx *c, uint64_t *out_c0, uint64_t *out_c1, cons
   if ((rc = gpq_mulpt_rns(c, s0, s1, sm, s0, s1, dim, batch, stream))) return rc;                                          // :179-185
   if ((rc = gpq_rns_reconstruct(c, out_c0, W, s0, dim, batch, logql, stream))) return rc;                                 // :188
   return gpq_rns_reconstruct(c, out_c1, W, s1, dim, batch, logql, stream);                                                // :189
+}
+
+// ---------------------------------------------------------------------------
+// constant plaintexts: he_const_pt's a + b x^(n/2) (constpt_kernels.hpp)
+// ---------------------------------------------------------------------------
+// src/he-encode.c:119-125 for Delta = 2^logDelta: the long double product is the double scaled by a power of two (exact), round() of it is
+// half away from zero, and double_to_mpi takes the integer as it is.
+extern "C" int gpq_const_pt(double re, double im, unsigned logDelta, int64_t *a, int64_t *b) {
+  if (!a || !b || logDelta > 1023) return gpq_fail(GPQ_ERR_INVALID, "gpq_const_pt: bad arguments");
+  int64_t out[2];
+  const double in[2] = {re, im};
+  for (int i = 0; i < 2; ++i) {
+    const double r = std::round(std::ldexp(in[i], (int)logDelta));
+    if (!std::isfinite(r) || r < -9223372036854775808.0 || r >= 9223372036854775808.0)
+      return gpq_fail(GPQ_ERR_INVALID, "gpq_const_pt: %g * 2^%u is not finite or does not fit int64_t", in[i], logDelta);
+    out[i] = (int64_t)r;
+  }
+  *a = out[0]; *b = out[1];
+  return GPQ_OK;
+}
+
+namespace {
+inline uint64_t magnitude(int64_t v) { return v < 0 ? 0 - (uint64_t)v : (uint64_t)v; }     // INT64_MIN -> 2^63
+}
+
+// The reference's he_mulpt returns smod(smod(v mod P, P), q_l) with P the product of the first `dim` primes (poly_rns2mpi, src/poly.c:109-120),
+// which is smod(v, q_l) exactly when |v| < floor(P/2).  For inputs centred mod 2^logql, |v| <= (|a| + |b|) 2^(logql-1).
+extern "C" int gpq_he_mulpt_const_fits(const gpq_ctx *c, int64_t a, int64_t b, unsigned logql, unsigned dim) {
+  if (!c || !logql || dim < 1 || dim > c->nprimes) return 0;
+  Big P{1};
+  for (unsigned d = 0; d < dim; ++d) mul_small(P, c->p[d]);
+  shr1(P);                                                                      // floor(P/2)
+  const u128h sum = (u128h)magnitude(a) + magnitude(b);                          // < 2^65
+  const unsigned sh = logql - 1, ws = sh >> 6, bs = sh & 63;
+  Big lhs(ws + 3, 0);
+  const uint64_t w[3] = {(uint64_t)sum, (uint64_t)(sum >> 64), 0};
+  for (unsigned i = 0; i < 3; ++i) lhs[ws + i] = bs ? (w[i] << bs) | (i ? w[i - 1] >> (64 - bs) : 0) : w[i];
+  return cmp_big(lhs, P) < 0;
+}
+
+extern "C" int gpq_he_mulpt_const(gpq_ctx *c, uint64_t *out_c0, uint64_t *out_c1, const uint64_t *c0, const uint64_t *c1, int64_t a, int64_t b,
+                                  unsigned W, unsigned logql, unsigned dim, unsigned logDelta, unsigned batch, unsigned *bad_dev, void *stream) {
+  int rc = check(c, dim, batch, "gpq_he_mulpt_const");
+  if (rc) return rc;
+  if (!out_c0 || !out_c1 || !c0 || !c1 || W < 1 || W > 64 || logql < 1 || logql > 64 * W || logDelta >= logql || c->logn < 1 || batch > 32767)
+    return gpq_fail(GPQ_ERR_INVALID, "gpq_he_mulpt_const: bad arguments (1 <= logql <= 64 W, logDelta < logql)");
+  if (!gpq_he_mulpt_const_fits(c, a, b, logql, dim))
+    return gpq_fail(GPQ_ERR_INVALID, "gpq_he_mulpt_const: (|a| + |b|) 2^%u reaches half the basis of %u limbs: he_mulpt's words are not the closed form", logql - 1, dim);
+  const unsigned s = logDelta < 64 ? logDelta : 0;                               // wider shifts: the plain product, then gpq_he_rs
+  MulptConstArgs k{out_c0, out_c1, c0, c1, magnitude(a), magnitude(b), a < 0, b < 0, W, c->logn, s, logql, bad_dev};
+  {
+    ProfScope prof(c, GPQ_K_MULPT_CONST, (hipStream_t)stream);
+    const unsigned threads = b ? c->n >> 1 : c->n;
+    const dim3 grid((threads + 255) / 256, 2 * batch), block(256);
+    if (b) hipLaunchKernelGGL(he_mulpt_const<true>, grid, block, 0, (hipStream_t)stream, k);
+    else hipLaunchKernelGGL(he_mulpt_const<false>, grid, block, 0, (hipStream_t)stream, k);
+  }
+  if ((rc = launched("gpq_he_mulpt_const"))) return rc;
+  return logDelta >= 64 ? gpq_he_rs(c, out_c0, out_c1, W, logDelta, logql - logDelta, batch, stream) : GPQ_OK;   // src/he-rescale.c:33-54
+}
+
+extern "C" int gpq_he_addpt_const(gpq_ctx *c, uint64_t *out_c0, uint64_t *out_c1, const uint64_t *c0, const uint64_t *c1, int64_t a, int64_t b,
+                                  int sub, unsigned W, unsigned logql, unsigned batch, void *stream) {
+  int rc = check(c, 1, batch, "gpq_he_addpt_const");
+  if (rc) return rc;
+  if (!out_c0 || !out_c1 || !c0 || !c1 || W < 1 || W > 64 || logql < 1 || logql > 64 * W || c->logn < 1 || batch > 32767)
+    return gpq_fail(GPQ_ERR_INVALID, "gpq_he_addpt_const: bad arguments (1 <= logql <= 64 W)");
+  AddptConstArgs k{out_c0, out_c1, c0, c1, a, b, sub ? 1u : 0u, W, c->logn, logql};
+  {
+    ProfScope prof(c, GPQ_K_ADDPT_CONST, (hipStream_t)stream);
+    hipLaunchKernelGGL(he_addpt_const, dim3((c->n + 255) / 256, 2 * batch), dim3(256), 0, (hipStream_t)stream, k);
+  }
+  return launched("gpq_he_addpt_const");
 }
 
 // he_dec, src/he-encrypt.c:105-125, for q_l = 2^logql: m = smod(poly_mul(c1, sk, dim, q_l) + c0, q_l) for `batch` ciphertexts and ONE key.

@@ -37,6 +37,7 @@ struct Gcry {
   unsigned (*mpi_scan)(MPI *, int, const void *, size_t, size_t *);
   void (*mpi_snatch)(MPI, MPI);
   void (*mpi_set_bit)(MPI, unsigned);
+  int (*mpi_cmp_ui)(MPI, unsigned long);
   void *(*xmalloc)(size_t);
   void (*xfree)(void *);
   bool ok = false;
@@ -123,6 +124,7 @@ void need_gcrypt() {
   G.mpi_scan = (unsigned (*)(MPI *, int, const void *, size_t, size_t *))get("gcry_mpi_scan");
   G.mpi_snatch = (void (*)(MPI, MPI))get("gcry_mpi_snatch");
   G.mpi_set_bit = (void (*)(MPI, unsigned))get("gcry_mpi_set_bit");
+  G.mpi_cmp_ui = (int (*)(MPI, unsigned long))get("gcry_mpi_cmp_ui");
   G.xmalloc = (void *(*)(size_t))get("gcry_malloc");
   G.xfree = (void (*)(void *))get("gcry_free");
   G.ok = true;

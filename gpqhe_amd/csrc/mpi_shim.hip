@@ -329,6 +329,119 @@ static void rescale_common(he_ct_t *ct, bool divide) {
   if (divide) { ct->nu /= hectx.Delta; ct->B = ct->B / hectx.Delta + hectx.bnd.Brs; }             // :37-38
 }
 
+// ---- constant plaintexts ---------------------------------------------------------------------------------------------------------
+// he_const_pt (src/he-encode.c:119-125) writes m[0] and m[n/2] of a plaintext that is 0 elsewhere, and the reference's algorithms
+// (he_inv, he_sqrt, he_sigmoid, he_log, he_exp_taylor, he_cmp*, he_coeff2slot) multiply and add such plaintexts between all their he_mul
+// calls.  For q_l = 2^k the product and the sums with a + b x^(n/2) are closed forms on the ciphertext's words alone (constpt_kernels.hpp):
+// the plaintext is then no operand -- neither converted nor uploaded nor kept resident -- and the call is one launch.  Same words as the
+// dense path (he_mulpt: for centred inputs, which the kernel checks); gpq_mpi_shim_set_const_pt(0) keeps every plaintext dense.
+static bool g_const_pt_on = true;
+static unsigned long g_const_taken = 0, g_const_fell_back = 0;
+void gpq_mpi_shim_set_const_pt(int on) { SHIM_CALL(); g_const_pt_on = on != 0; }
+void gpq_mpi_shim_const_pt_stats(unsigned long *taken, unsigned long *fell_back) {
+  SHIM_CALL();
+  if (taken) *taken = g_const_taken;
+  if (fell_back) *fell_back = g_const_fell_back;
+}
+
+static bool mpi_is_zero(MPI m, bool direct) {
+  const MpiView *v = (const MpiView *)m;
+  if (direct && !(v->flags & 4)) {
+    for (int j = 0; j < v->nlimbs; ++j) if (v->d[j]) return false;
+    return true;
+  }
+  return G.mpi_cmp_ui(m, 0) == 0;
+}
+// A candidate in O(1): m[1] is zero and m[0], m[n/2] have at most 63 bits.  A dense plaintext leaves here, at its first look.
+static bool const_pt_candidate(const poly_mpi_t *m, unsigned n, int64_t *a, int64_t *b) {
+  if (n < 4 || !mpi_is_zero(m->coeffs[1], mpi_direct())) return false;
+  int64_t v[2];
+  for (int k = 0; k < 2; ++k) {
+    MPI x = m->coeffs[k ? n / 2 : 0];
+    const unsigned nb = G.mpi_get_nbits(x);
+    if (nb > 63) return false;
+    uint64_t mag = 0;
+    if (nb) {
+      unsigned char buf[8];
+      size_t nw = 0;
+      if (G.mpi_print(FMT_USG, buf, sizeof buf, &nw, x)) die("gcry_mpi_print failed");
+      for (size_t i = 0; i < nw; ++i) mag = mag << 8 | buf[i];
+    }
+    v[k] = G.mpi_is_neg(x) ? -(int64_t)mag : (int64_t)mag;
+  }
+  *a = v[0]; *b = v[1];
+  return true;
+}
+// The rest of the scan -- is every other coefficient zero? -- cut into the conversion threads' ranges; a range stops at the first non-zero
+// coefficient anyone found.  The tasks ride with the conversions of the call (Operands::prepare / recheck take them as `side` tasks): when
+// every operand is resident the device already works on the candidate's closed form while the host scans, as it does for the operands.
+struct ConstScan {
+  const poly_mpi_t *m;
+  unsigned n, parts;
+  bool direct;
+  std::atomic<bool> dense{false};
+  std::function<void(unsigned)> job;
+  ConstScan(const poly_mpi_t *m_, unsigned n_) : m(m_), n(n_), parts(convert_threads(n_)), direct(mpi_direct()) {
+    job = [this](unsigned t) {
+      const unsigned per = (n + parts - 1) / parts, lo = t * per, hi = lo + per < n ? lo + per : n, h = n / 2;
+      for (unsigned i = lo; i < hi && !dense.load(std::memory_order_relaxed); ++i)
+        if (i != 0 && i != h && !mpi_is_zero(m->coeffs[i], direct)) dense.store(true, std::memory_order_relaxed);
+    };
+  }
+};
+static bool all_operands_resident(const poly_mpi_t *const in[], int count, unsigned n, unsigned W) {
+  if (!poly_cache_on(n)) return false;
+  for (int i = 0; i < count; ++i) {
+    const PolySlot *s = resident_poly(in[i], n, W);
+    if (!s || !s->trusted) return false;
+  }
+  return true;
+}
+
+// he_mulpt by a + b x^(n/2), q_l = 2^logql, on the ciphertext's two polynomials alone.  The caller's integers may be anything, and the closed
+// form is he_mulpt's words for centred ones only: the kernel counts the others, the count comes back with the first bytes of the download,
+// and a non-zero count leaves `dest` untouched (it may be `src`) and returns 0 -- the caller runs the dense path.  -1: the plaintext has
+// another non-zero coefficient after all (nothing was written either); 1: done.
+static int mulpt_const(gpq_ctx *c, struct he_ct *dest, const struct he_ct *src, const struct he_pt *pt, int64_t ca, int64_t cb, unsigned n, unsigned logql, unsigned dim) {
+  static hipEvent_t counted = nullptr;
+  if (!counted && hipEventCreateWithFlags(&counted, hipEventDisableTiming) != hipSuccess) die("hipEventCreate failed");
+  const unsigned W = (logql + 1) / 64 + 1;
+  const size_t big = (size_t)W * n;
+  HostBuf s0(big * 8), s1(big * 8), t0s(big * 8), t1s(big * 8), count(8);
+  DevBuf d0(big * 8), d1(big * 8), o0(big * 8), o1(big * 8), bad(8);
+  const DevBuf *dd[2] = {&d0, &d1}, *oo[2] = {&o0, &o1};
+  const HostBuf *ss[2] = {&s0, &s1}, *ts[2] = {&t0s, &t1s};
+  const poly_mpi_t *in[2] = {&src->c0, &src->c1};
+  ConstScan scan(&pt->m, n);
+  const bool later = all_operands_resident(in, 2, n, W);
+  Operands ops(2, in, dd, ss, n, W);
+  if (later) ops.prepare(true); else ops.prepare(true, scan.parts, &scan.job);
+  // (on the ways out before download_convert: the copies queued into / out of this call's page-locked buffers land before the buffers return to the pool)
+  if (scan.dense.load()) { (void)gpq_stream_sync(nullptr); return -1; }
+  auto device_work = [&]() {
+    if (hipMemsetAsync(bad.p, 0, 4, nullptr) != hipSuccess) die("device memset failed");
+    if (gpq_he_mulpt_const(c, o0.u64(), o1.u64(), ops.x[0], ops.x[1], ca, cb, W, logql, dim, 0, 1, (unsigned *)bad.p, nullptr) != GPQ_OK) die("he_mulpt failed");
+    if (hipMemcpyAsync(count.p, bad.p, 4, hipMemcpyDeviceToHost, nullptr) != hipSuccess || hipEventRecord(counted, nullptr) != hipSuccess) die("download failed");
+    download_issue(ts, oo, 2, n, W);
+  };
+  device_work();
+  if (ops.resident) {
+    const bool again = ops.recheck(later ? scan.parts : 0, later ? &scan.job : nullptr);
+    if (scan.dense.load()) { (void)gpq_stream_sync(nullptr); return -1; }
+    if (again) {
+      if (ops.misfits) die("coefficient does not fit the big slab");
+      device_work();
+    }
+  }
+  if (hipEventSynchronize(counted) != hipSuccess) die("download failed");
+  if (*(volatile unsigned *)count.p) { (void)gpq_stream_sync(nullptr); return 0; }
+  poly_mpi_t *out[2] = {&dest->c0, &dest->c1};
+  std::vector<uint64_t> oprints((size_t)2 * ops.nt, 0);
+  download_convert(out, ts, 2, n, W, oprints.data());
+  remember_results(out, oo, 2, n, W, oprints);
+  return 1;
+}
+
 // src/he-mult.c:159-196
 void he_mulpt(struct he_ct *dest, const struct he_ct *src, const struct he_pt *pt) {
   SHIM_CALL();
@@ -341,6 +454,16 @@ void he_mulpt(struct he_ct *dest, const struct he_ct *src, const struct he_pt *p
   const bool pow2 = is_pow2(qw);
   const unsigned logql = G.mpi_get_nbits(hectx.q[l]) - 1;
   const unsigned dim = (unsigned)((logql + 1 + log2(pt->nu) + polyctx.logn) / 59u + 1);        // :169, evaluated in double as there
+  int64_t ca, cb;
+  if (g_const_pt_on && pow2 && logql >= 1 && const_pt_candidate(&pt->m, n, &ca, &cb) && gpq_he_mulpt_const_fits(c, ca, cb, logql, dim)) {
+    const int took = mulpt_const(c, dest, src, pt, ca, cb, n, logql, dim);
+    if (took >= 0) ++g_const_taken;
+    if (took > 0) {
+      dest->l = l; dest->nu = nu; dest->B = B;                                                  // :162-164
+      return;
+    }
+    if (took == 0) ++g_const_fell_back;
+  }
   unsigned bits = max_bits(&pt->m, n);
   if (logql + 1 > bits) bits = logql + 1;
   const unsigned W = bits / 64 + 1;

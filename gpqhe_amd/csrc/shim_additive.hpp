@@ -23,8 +23,6 @@ static void additive(he_ct_t *ct, const he_ct_t *a, const he_ct_t *b, const he_p
   const bool pow2 = is_pow2(qw);
   const unsigned nbq = kind == 5 ? 2 : G.mpi_get_nbits(hectx.q[l]), logql = nbq - 1;
   poly_mpi_t *out[2] = {&ct->c0, &ct->c1};
-  const int count = kind >= 4 ? 2 : kind < 2 ? 4 : 3;
-  const poly_mpi_t *in[4] = {&a->c0, &a->c1, kind < 2 ? &b->c0 : kind < 4 ? &pt->m : nullptr, kind < 2 ? &b->c1 : nullptr};
   if (logql == 0 && kind != 5) {                            // q_l = 1: mpi_smod leaves -1 everywhere (see he_rs)
     for (int k = 0; k < 2; ++k)
       for (unsigned i = 0; i < n; ++i) { G.mpi_set_ui(out[k]->coeffs[i], 1); G.mpi_neg(out[k]->coeffs[i], out[k]->coeffs[i]); }
@@ -32,63 +30,88 @@ static void additive(he_ct_t *ct, const he_ct_t *a, const he_ct_t *b, const he_p
     return;
   }
   const unsigned Wout = kind == 5 ? 64 : logql / 64 + 1;    // the results are centred mod q_l (a copy keeps every word)
-  auto pass = [&](unsigned W, bool kept) -> bool {
-    if (W > 32) die("he_add: coefficients wider than 2047 bits");
-    const size_t big = (size_t)W * n;
-    HostBuf s0(big * 8), s1(big * 8), s2(count > 2 ? big * 8 : 8), s3(count > 3 ? big * 8 : 8), t0s(big * 8), t1s(big * 8);
-    DevBuf d0(big * 8), d1(big * 8), d2(count > 2 ? big * 8 : 8), d3(count > 3 ? big * 8 : 8), o0(big * 8), o1(big * 8), scratch(192 * 8);
-    const DevBuf *dd[4] = {&d0, &d1, &d2, &d3}, *oo[2] = {&o0, &o1};
-    const HostBuf *ss[4] = {&s0, &s1, &s2, &s3}, *ts[2] = {&t0s, &t1s};
-    Operands ops(count, in, dd, ss, n, W);
-    ops.prepare(kept);
-    auto device_work = [&]() {
-      int rc;
-      if (kind == 5) {
-        if (hipMemcpyAsync(o0.p, ops.x[0], big * 8, hipMemcpyDeviceToDevice, nullptr) != hipSuccess ||
-            hipMemcpyAsync(o1.p, ops.x[1], big * 8, hipMemcpyDeviceToDevice, nullptr) != hipSuccess) die("device copy failed");
-        download_issue(ts, oo, 2, n, W);
-        return;
-      }
-      if (kind == 4) {
-        rc = gpq_big_addsub(c, o0.u64(), ops.x[0], nullptr, W, 1, 2, nullptr);
-        if (rc == GPQ_OK) rc = gpq_big_addsub(c, o1.u64(), ops.x[1], nullptr, W, 1, 2, nullptr);
-      } else {
-        rc = gpq_big_addsub(c, o0.u64(), ops.x[0], ops.x[2], W, 1, kind & 1, nullptr);              // c0 (+/-) the other c0 or the plaintext
-        if (rc == GPQ_OK && kind < 2) rc = gpq_big_addsub(c, o1.u64(), ops.x[1], ops.x[3], W, 1, kind & 1, nullptr);
-        else if (rc == GPQ_OK && hipMemcpyAsync(o1.p, ops.x[1], big * 8, hipMemcpyDeviceToDevice, nullptr) != hipSuccess) die("device copy failed");   // c1 mod q, :92, :115
-      }
-      if (rc == GPQ_OK)                                                                              // mpi_smod of both, :43-44 ...
-        rc = pow2 ? gpq_he_rs(c, o0.u64(), o1.u64(), W, 0, logql, 1, nullptr)
-                  : gpq_he_rs_general(c, o0.u64(), o1.u64(), W, 1ull, qw.data(), (unsigned)qw.size(), 1, scratch.p, nullptr);
-      if (rc != GPQ_OK) die("he_add failed");
-      download_issue(ts, oo, 2, n, Wout < W ? Wout : W);
-    };
-    device_work();
-    if (ops.resident && ops.recheck()) {
-      if (ops.misfits) { (void)gpq_stream_sync(nullptr); return false; }   // (as in mpi_shim.hip: queued copies land before the buffers return to the pool)
+  // cpt: he_addpt / he_subpt by he_const_pt's plaintext (mpi_shim.hip, "constant plaintexts") -- the two integers ride in the launch and the
+  // plaintext is no operand.  Returns false when the plaintext turns out to have another non-zero coefficient: nothing was written then.
+  auto attempt = [&](const bool cpt, const int64_t ca, const int64_t cb) -> bool {
+    const int count = kind >= 4 || cpt ? 2 : kind < 2 ? 4 : 3;
+    const poly_mpi_t *in[4] = {&a->c0, &a->c1, kind < 2 ? &b->c0 : kind < 4 ? &pt->m : nullptr, kind < 2 ? &b->c1 : nullptr};
+    bool dense = false;
+    auto pass = [&](unsigned W, bool kept) -> bool {
+      if (W > 32) die("he_add: coefficients wider than 2047 bits");
+      const size_t big = (size_t)W * n;
+      HostBuf s0(big * 8), s1(big * 8), s2(count > 2 ? big * 8 : 8), s3(count > 3 ? big * 8 : 8), t0s(big * 8), t1s(big * 8);
+      DevBuf d0(big * 8), d1(big * 8), d2(count > 2 ? big * 8 : 8), d3(count > 3 ? big * 8 : 8), o0(big * 8), o1(big * 8), scratch(192 * 8);
+      const DevBuf *dd[4] = {&d0, &d1, &d2, &d3}, *oo[2] = {&o0, &o1};
+      const HostBuf *ss[4] = {&s0, &s1, &s2, &s3}, *ts[2] = {&t0s, &t1s};
+      ConstScan scan(cpt ? &pt->m : nullptr, n);
+      const bool later = cpt && kept && all_operands_resident(in, count, n, W);   // the scan rides with the check of the resident copies
+      Operands ops(count, in, dd, ss, n, W);
+      if (cpt && !later) ops.prepare(kept, scan.parts, &scan.job); else ops.prepare(kept);
+      // (on every way out before download_convert: the copies queued into / out of this pass's page-locked buffers land before the buffers return to the pool)
+      if (scan.dense.load()) { (void)gpq_stream_sync(nullptr); dense = true; return true; }
+      auto device_work = [&]() {
+        int rc;
+        if (kind == 5) {
+          if (hipMemcpyAsync(o0.p, ops.x[0], big * 8, hipMemcpyDeviceToDevice, nullptr) != hipSuccess ||
+              hipMemcpyAsync(o1.p, ops.x[1], big * 8, hipMemcpyDeviceToDevice, nullptr) != hipSuccess) die("device copy failed");
+          download_issue(ts, oo, 2, n, W);
+          return;
+        }
+        if (cpt) {                                            // the sum, c1's copy and both mpi_smod in one launch
+          if (gpq_he_addpt_const(c, o0.u64(), o1.u64(), ops.x[0], ops.x[1], ca, cb, kind & 1, W, logql, 1, nullptr) != GPQ_OK) die("he_addpt failed");
+          download_issue(ts, oo, 2, n, Wout < W ? Wout : W);
+          return;
+        }
+        if (kind == 4) {
+          rc = gpq_big_addsub(c, o0.u64(), ops.x[0], nullptr, W, 1, 2, nullptr);
+          if (rc == GPQ_OK) rc = gpq_big_addsub(c, o1.u64(), ops.x[1], nullptr, W, 1, 2, nullptr);
+        } else {
+          rc = gpq_big_addsub(c, o0.u64(), ops.x[0], ops.x[2], W, 1, kind & 1, nullptr);              // c0 (+/-) the other c0 or the plaintext
+          if (rc == GPQ_OK && kind < 2) rc = gpq_big_addsub(c, o1.u64(), ops.x[1], ops.x[3], W, 1, kind & 1, nullptr);
+          else if (rc == GPQ_OK && hipMemcpyAsync(o1.p, ops.x[1], big * 8, hipMemcpyDeviceToDevice, nullptr) != hipSuccess) die("device copy failed");   // c1 mod q, :92, :115
+        }
+        if (rc == GPQ_OK)                                                                              // mpi_smod of both, :43-44 ...
+          rc = pow2 ? gpq_he_rs(c, o0.u64(), o1.u64(), W, 0, logql, 1, nullptr)
+                    : gpq_he_rs_general(c, o0.u64(), o1.u64(), W, 1ull, qw.data(), (unsigned)qw.size(), 1, scratch.p, nullptr);
+        if (rc != GPQ_OK) die("he_add failed");
+        download_issue(ts, oo, 2, n, Wout < W ? Wout : W);
+      };
       device_work();
+      if (ops.resident) {
+        const bool again = ops.recheck(later ? scan.parts : 0, later ? &scan.job : nullptr);
+        if (scan.dense.load()) { (void)gpq_stream_sync(nullptr); dense = true; return true; }
+        if (again) {
+          if (ops.misfits) { (void)gpq_stream_sync(nullptr); return false; }   // (as in mpi_shim.hip: queued copies land before the buffers return to the pool)
+          device_work();
+        }
+      }
+      const unsigned Wdown = Wout < W ? Wout : W;
+      std::vector<uint64_t> oprints((size_t)2 * ops.nt, 0);
+      download_convert(out, ts, 2, n, Wdown, oprints.data());
+      remember_results(out, oo, 2, n, Wdown, oprints);
+      return true;
+    };
+    bool done = false;
+    if ((pow2 || kind == 5) && poly_cache_on(n)) {            // wrapping sums are harmless below a power of two; any other q_l measures its operands first
+      unsigned W = 0;
+      bool all = true;
+      for (int i = 0; i < count && all; ++i) {
+        const PolySlot *k = resident_poly(in[i], n, 0);
+        if (!k || !k->trusted || (W && k->W != W)) all = false; else W = k->W;
+      }
+      if (all && (W >= Wout || kind == 5)) done = pass(W, true);
     }
-    const unsigned Wdown = Wout < W ? Wout : W;
-    std::vector<uint64_t> oprints((size_t)2 * ops.nt, 0);
-    download_convert(out, ts, 2, n, Wdown, oprints.data());
-    remember_results(out, oo, 2, n, Wdown, oprints);
-    return true;
+    if (!done) {
+      unsigned bits = nbq;
+      for (int i = 0; i < count; ++i) { const unsigned bi = max_bits(in[i], n); if (bi > bits) bits = bi; }
+      pass((bits + 1) / 64 + 1, false);                       // one bit of headroom: the sum of two such integers still fits
+    }
+    return !dense;
   };
-  bool done = false;
-  if ((pow2 || kind == 5) && poly_cache_on(n)) {            // wrapping sums are harmless below a power of two; any other q_l measures its operands first
-    unsigned W = 0;
-    bool all = true;
-    for (int i = 0; i < count && all; ++i) {
-      const PolySlot *k = resident_poly(in[i], n, 0);
-      if (!k || !k->trusted || (W && k->W != W)) all = false; else W = k->W;
-    }
-    if (all && (W >= Wout || kind == 5)) done = pass(W, true);
-  }
-  if (!done) {
-    unsigned bits = nbq;
-    for (int i = 0; i < count; ++i) { const unsigned bi = max_bits(in[i], n); if (bi > bits) bits = bi; }
-    pass((bits + 1) / 64 + 1, false);                       // one bit of headroom: the sum of two such integers still fits
-  }
+  int64_t ca = 0, cb = 0;
+  const bool candidate = (kind == 2 || kind == 3) && g_const_pt_on && pow2 && logql >= 1 && const_pt_candidate(&pt->m, n, &ca, &cb);
+  if (candidate && attempt(true, ca, cb)) ++g_const_taken;
+  else attempt(false, 0, 0);
   ct->l = l; ct->nu = nu; ct->B = B;
 }
 void he_add(he_ct_t *ct, const he_ct_t *ct1, const he_ct_t *ct2) { additive(ct, ct1, ct2, nullptr, 0); }

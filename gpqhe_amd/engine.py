@@ -334,6 +334,30 @@ class PolyContext:
         _native.check(self.lib.gpq_he_mulpt_general(self.h, self._ptr(out_c0), self._ptr(out_c1), self._ptr(c0), self._ptr(c1), self._ptr(m), W, qw, L, dim,
                                                     batch, self._ptr(ws), self._stream()), "gpq_he_mulpt_general")
 
+    @staticmethod
+    def const_pt(re, im, logDelta):
+        """(a, b) of he_const_pt (src/he-encode.c:119-125) for Delta = 2^logDelta: the plaintext is a + b x^(n/2).  Host only."""
+        a, b = C.c_int64(), C.c_int64()
+        _native.check(_native.load().gpq_const_pt(float(re), float(im), logDelta, C.byref(a), C.byref(b)), "gpq_const_pt")
+        return a.value, b.value
+
+    def he_mulpt_const_fits(self, a, b, logql, dim):
+        """does the constant path give he_mulpt's words for inputs centred mod 2^logql on `dim` limbs?"""
+        return bool(self.lib.gpq_he_mulpt_const_fits(self.h, a, b, logql, dim))
+
+    def he_mulpt_const(self, out_c0, out_c1, c0, c1, a, b, W, logql, dim, logDelta=0, bad=None):
+        """he_mulpt by a + b x^(n/2) and, logDelta != 0, he_rs (src/he-mult.c:159-196, src/he-rescale.c:33-54) in one pass over the big slabs;
+        out may be the input.  bad: None or a zeroed int32 device tensor that counts input coefficients not centred mod 2^logql."""
+        batch = c0.numel() // (W * self.n)
+        _native.check(self.lib.gpq_he_mulpt_const(self.h, self._ptr(out_c0), self._ptr(out_c1), self._ptr(c0), self._ptr(c1), a, b, W, logql, dim, logDelta,
+                                                  batch, self._ptr(bad) if bad is not None else None, self._stream()), "gpq_he_mulpt_const")
+
+    def he_addpt_const(self, out_c0, out_c1, c0, c1, a, b, W, logql, sub=False):
+        """he_addpt / he_subpt (src/he-add.c:80-123) with the plaintext a + b x^(n/2) in one launch; out may be the input."""
+        batch = c0.numel() // (W * self.n)
+        _native.check(self.lib.gpq_he_addpt_const(self.h, self._ptr(out_c0), self._ptr(out_c1), self._ptr(c0), self._ptr(c1), a, b, 1 if sub else 0, W, logql,
+                                                  batch, self._stream()), "gpq_he_addpt_const")
+
     def he_genswk(self, evk0, evk1, p1, sk, e, sp, W, dimP, logqL, dimevk):
         """src/he-kem.c:74-118 from host-sampled p1 / e and the hidden polynomial sp; q_L = 2^logqL."""
         torch = _torch()

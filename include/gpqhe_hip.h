@@ -360,6 +360,37 @@ int gpq_he_mulpt(gpq_ctx *ctx, uint64_t *out_c0, uint64_t *out_c1, const uint64_
 int gpq_poly_rot(gpq_ctx *ctx, uint64_t *r, const uint64_t *a, unsigned W, unsigned rot, unsigned batch, void *stream);
 int gpq_poly_conj(gpq_ctx *ctx, uint64_t *r, const uint64_t *a, unsigned W, unsigned batch, void *stream);
 
+/* ---- constant plaintexts ("Constant plaintexts") ------------------------------------------------------------------
+ * he_const_pt (src/he-encode.c:119-125) writes two integers, m[0] = a and m[n/2] = b, into a plaintext that is 0 elsewhere.  The product of
+ * a ciphertext polynomial c with a + b x^h (h = n/2) in Z[x]/(x^n + 1) is the closed form
+ *   v[k] = a c[k] - b c[k+h] (k < h),   v[k] = a c[k] + b c[k-h] (k >= h)
+ * and the reference's he_mulpt returns smod(smod(v mod P, P), q_l), P = the product of the first `dim` primes: smod(v, q_l) exactly when
+ * |v| < floor(P/2).  Inputs centred mod 2^logql (what every call of this library returns) give |v| <= (|a| + |b|) 2^(logql-1), so
+ *   fits(a, b, logql, dim)  <=>  (|a| + |b|) 2^(logql-1) < floor(P_dim / 2)
+ * is what the host can decide; with the reference's dim (src/he-mult.c:168) it holds for every |re|, |im| up to about n.  No workspace;
+ * asynchronous on `stream` and capturable. */
+
+/* he_const_pt's two integers (src/he-encode.c:119-125) for Delta = 2^logDelta, where every step of the reference's
+ * expression is exact: round-half-away-from-zero of re * 2^logDelta and im * 2^logDelta.  GPQ_ERR_INVALID if either
+ * is not finite or does not fit int64_t.  Host only, no device call. */
+int gpq_const_pt(double re, double im, unsigned logDelta, int64_t *a, int64_t *b);
+
+/* 1 when the constant path gives he_mulpt's words for inputs centred mod 2^logql on `dim` limbs (condition above), else 0 */
+int gpq_he_mulpt_const_fits(const gpq_ctx *ctx, int64_t a, int64_t b, unsigned logql, unsigned dim);
+
+/* he_mulpt (src/he-mult.c:159-196) by the plaintext a + b x^(n/2), then -- logDelta != 0 -- he_rs (src/he-rescale.c:33-54):
+ * the words of gpq_he_mulpt [+ gpq_he_rs(W, logDelta, logql - logDelta)] for centred inputs.  !fits -> GPQ_ERR_INVALID,
+ * outputs untouched.  out may be the input of the same polynomial; no other overlap.  bad_dev: NULL or a device counter, to which
+ * the call adds the number of input coefficients that are not centred mod 2^logql (the outputs are the closed form regardless).
+ * 1 <= logql <= 64 W, logDelta < logql.  One launch for logDelta <= 63; beyond, the plain product followed by gpq_he_rs. */
+int gpq_he_mulpt_const(gpq_ctx *ctx, uint64_t *out_c0, uint64_t *out_c1, const uint64_t *c0, const uint64_t *c1,
+                       int64_t a, int64_t b, unsigned W, unsigned logql, unsigned dim, unsigned logDelta,
+                       unsigned batch, unsigned *bad_dev, void *stream);
+
+/* he_addpt (sub = 0) / he_subpt (sub = 1) with that plaintext, src/he-add.c:80-123, any W-word inputs: one launch.  In place allowed. */
+int gpq_he_addpt_const(gpq_ctx *ctx, uint64_t *out_c0, uint64_t *out_c1, const uint64_t *c0, const uint64_t *c1,
+                       int64_t a, int64_t b, int sub, unsigned W, unsigned logql, unsigned batch, void *stream);
+
 /* ---- hoisted rotations and he_gemv --------------------------------------------------------------------------------------------
  * sigma of the automorphism X -> X^g (g odd) in the NTT domain, in the reference's forward output order (bit-reversed):
  *   NTT(poly_rot(a, rot))[j] = NTT(a)[idx[j]] (mod p) with g = 5^rot mod 2n (g = 2n - 1 for poly_conj), where

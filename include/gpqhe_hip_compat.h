@@ -265,6 +265,14 @@ void gpq_mpi_shim_poly_stats(uint64_t *confirmed, uint64_t *stale);
 void gpq_mpi_shim_forget_polys(void);
 /* testing: while on, calls neither consult nor update the resident polynomials (which stay as they are) */
 void gpq_mpi_shim_poly_bypass(int on);
+/* Constant plaintexts: he_mulpt / he_addpt / he_subpt recognise a plaintext that is zero except at coefficients 0 and n/2 (what
+ * he_const_pt writes, src/he-encode.c:119-125) with at most 63 bits there, at a level whose q_l is a power of two, and then run the
+ * closed form on the ciphertext's words in one launch (gpq_he_mulpt_const / gpq_he_addpt_const): the plaintext is neither converted nor
+ * uploaded nor kept resident.  he_mulpt also requires gpq_he_mulpt_const_fits at the reference's dim, and falls back to the dense path
+ * when the kernel finds an input coefficient that is not centred mod q_l.  Same words either way; default on, 0 turns recognition off. */
+void gpq_mpi_shim_set_const_pt(int on);
+/* calls that took the constant path / he_mulpt calls among them that fell back to the dense path */
+void gpq_mpi_shim_const_pt_stats(unsigned long *taken, unsigned long *fell_back);
 /* Host threads converting between libgcrypt integers and slabs: default min(hardware threads, 16), at most 64.  Only before the first
  * MPI-typed call of the process; returns the number in use. */
 unsigned gpq_mpi_shim_set_conversion_threads(unsigned threads);
