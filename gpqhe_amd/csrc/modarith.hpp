@@ -141,19 +141,50 @@ __device__ __forceinline__ uint64_t mulmod_lazy(uint64_t a, uint64_t w, const Pr
 // x - m if x >= m else x, for m = p, 2p, 4p: compare, select the addend (-m or 0), one 64-bit add = 4 VALU instructions.
 // Written as `x >= m ? x - m : x` (or with `0 - m` the compiler can see through) it becomes compare, select, v_sub_co,
 // v_subb_co: 5 instructions and a carry hazard.  The negated moduli come from the table so that they stay opaque.
-__device__ __forceinline__ uint64_t csub_by(uint64_t x, uint64_t m, uint64_t neg_m) { return x + (x >= m ? neg_m : (uint64_t)0); }
-__device__ __forceinline__ uint64_t csub1(uint64_t x, const PrimeK &k) { return csub_by(x, k.p, k.np); }
-__device__ __forceinline__ uint64_t csub2(uint64_t x, const PrimeK &k) { return csub_by(x, k.p2, k.np2); }
-__device__ __forceinline__ uint64_t csub4(uint64_t x, const PrimeK &k) { return csub_by(x, k.p4, k.np4); }
-__device__ __forceinline__ uint64_t csub3(uint64_t x, const PrimeK &k) { return csub_by(x, k.p3, k.np3); }
+//
+// That select form is what GPQ_CSUB_MASKED=0 builds (the A/B parent of profiles/r20).  The default is the same value in 2 VALU
+// instructions: the two selects exist only because the add runs in every lane.  The compare goes to an SGPR pair (a ballot: the
+// compiler's own v_cmp_le_u64, so its hazard recognizer sees it), and ONE asm statement narrows the wave's lane mask to the lanes that
+// compared true (s_and_saveexec_b64), adds -m under it (v_lshl_add_u64) and puts the mask back (s_mov_b64): the two scalar
+// instructions do not issue on the VALU port.  Lanes that compared false keep x; with no lane true the add runs under an empty mask.
+//   - The mask is restored inside the statement that narrowed it, from the value that statement saved, never from -1: partial waves,
+//     lanes that returned early and lanes outside a divergent branch stay off, and no compiler-scheduled instruction runs narrowed.
+//   - m and -m are SCALAR operands ("s"): uniform per wave, as the LimbTab constants of a block are -- every caller today.  A value
+//     that varies by lane would be read from the first active lane only: such a caller needs the select form.
+//   - Plain asm, not volatile (see pin_consts); it declares scc, which s_and_saveexec writes, and touches no memory.
+//   - Wait states: SALU write of EXEC -> VALU, VALU write of an SGPR pair -> SALU read, SALU write of EXEC behind a VALU: none on gfx9
+//     (what the compiler emits around a divergent `if`); -m sits in SGPRs loaded at kernel entry, and v_cmpx / VCC are not involved.
+#ifndef GPQ_CSUB_MASKED
+#define GPQ_CSUB_MASKED 1
+#endif
+// MASKED = false is the select form as a property of the call site: the 7-mad class (plain twiddles: ct_bfly / gs_bfly / gs_last on
+// uint64_t, TwTraits<uint64_t>) keeps it, because mulpt_mid8 of that class goes from 100 VGPRs to 168 with spills under the masked form.
+template <bool MASKED = true>
+__device__ __forceinline__ uint64_t csub_by(uint64_t x, uint64_t m, uint64_t neg_m) {
+#if GPQ_CSUB_MASKED
+  if constexpr (MASKED) {
+    const uint64_t take = __builtin_amdgcn_ballot_w64(x >= m);
+    uint64_t save;
+    asm("s_and_saveexec_b64 %1, %2\n\tv_lshl_add_u64 %0, %0, 0, %3\n\ts_mov_b64 exec, %1" : "+v"(x), "=&s"(save) : "s"(take), "s"(neg_m) : "scc");
+    return x;
+  }
+#endif
+  return x + (x >= m ? neg_m : (uint64_t)0);
+}
+template <bool MASKED = true> __device__ __forceinline__ uint64_t csub1(uint64_t x, const PrimeK &k) { return csub_by<MASKED>(x, k.p, k.np); }
+template <bool MASKED = true> __device__ __forceinline__ uint64_t csub2(uint64_t x, const PrimeK &k) { return csub_by<MASKED>(x, k.p2, k.np2); }
+template <bool MASKED = true> __device__ __forceinline__ uint64_t csub4(uint64_t x, const PrimeK &k) { return csub_by<MASKED>(x, k.p4, k.np4); }
+template <bool MASKED = true> __device__ __forceinline__ uint64_t csub3(uint64_t x, const PrimeK &k) { return csub_by<MASKED>(x, k.p3, k.np3); }
 
 // value < 8p -> [0,p)
+template <bool MASKED = true>
 __device__ __forceinline__ uint64_t canon8(uint64_t x, const PrimeK &k) {
-  return csub1(csub2(csub4(x, k), k), k);
+  return csub1<MASKED>(csub2<MASKED>(csub4<MASKED>(x, k), k), k);
 }
 // value < 4p -> [0,p)
+template <bool MASKED = true>
 __device__ __forceinline__ uint64_t canon4(uint64_t x, const PrimeK &k) {
-  return csub1(csub2(x, k), k);
+  return csub1<MASKED>(csub2<MASKED>(x, k), k);
 }
 
 // Cooley-Tukey butterfly of src/ntt.c:45-49 in lazy form.
@@ -161,7 +192,7 @@ __device__ __forceinline__ uint64_t canon4(uint64_t x, const PrimeK &k) {
 //   x' = xs + t < 8p,  y' = xs + 4p - t in (0, 8p).
 __device__ __forceinline__ void ct_bfly(uint64_t &x, uint64_t &y, uint64_t w, const PrimeK &k) {
   const uint64_t t = mulmod_raw_t<GPQ_PIN_CT>(y, w, k);
-  const uint64_t xs = csub4(x, k);
+  const uint64_t xs = csub4<false>(x, k);
   x = xs + t;
   y = xs + k.p4 - t;
 }
@@ -171,7 +202,7 @@ __device__ __forceinline__ void ct_bfly(uint64_t &x, uint64_t &y, uint64_t w, co
 __device__ __forceinline__ void gs_bfly(uint64_t &x, uint64_t &y, uint64_t w, const PrimeK &k) {
   const uint64_t v = x + y;
   const uint64_t d = x + k.p4 - y;  // (0, 8p)
-  x = csub4(v, k);
+  x = csub4<false>(v, k);
   y = mulmod_raw_t<GPQ_PIN_GS>(d, w, k);
 }
 

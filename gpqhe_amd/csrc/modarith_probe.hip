@@ -98,6 +98,24 @@ __global__ __launch_bounds__(256) void modprobe_kernel(int op, PrimeK k0, const 
   }
 }
 
+// The conditional subtraction under lane masks that the one-call-per-lane kernel above never produces (csub_by's masked form narrows and
+// restores the wave's lane mask itself): any workgroup size, so that a wave can start partly off; lanes at or past count return early;
+// lanes with on[i] == 0 stay outside the divergent branch that subtracts.  out0 is written inside the branch, out1 behind it by every
+// lane that did not return: a mask restored too wide or left too narrow shows as a word written, or not written, where the caller's
+// fill says otherwise.  mul = 1 .. 4 picks csub1 .. csub4.
+__global__ __launch_bounds__(256) void modprobe_csub_lanes_kernel(int mul, PrimeK k0, const uint64_t *__restrict__ xs, const unsigned char *__restrict__ on,
+                                                                  uint64_t *__restrict__ out0, uint64_t *__restrict__ out1, size_t count) {
+  const PrimeK k = pin_consts(k0);
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  uint64_t x = xs[i];
+  if (on[i]) {
+    x = mul == 1 ? csub1(x, k) : mul == 2 ? csub2(x, k) : mul == 3 ? csub3(x, k) : csub4(x, k);
+    out0[i] = x;
+  }
+  out1[i] = x;
+}
+
 }  // namespace
 
 extern "C" {
@@ -135,6 +153,38 @@ int gpq_modprobe_run(int op, uint64_t p, const uint64_t *x, const uint64_t *y, c
   if (e == hipSuccess && out1) e = hipMemcpy(out1, dev[5], bytes, hipMemcpyDeviceToHost);
   for (int j = 0; j < 6; ++j)
     if (dev[j]) (void)hipFree(dev[j]);
+  return (int)e;
+}
+
+// csub<mul> on blocks x threads lanes (threads <= 256, any value: 96 gives a second wave that starts half off), of which lanes
+// >= count return early and lanes with on[i] == 0 skip the subtraction.  x, on, out0 and out1 are host arrays of blocks * threads
+// entries; out0 and out1 are uploaded as given and downloaded again, so the caller sees which words the kernel wrote.
+int gpq_modprobe_run_csub_lanes(int mul, uint64_t p, const uint64_t *x, const unsigned char *on, uint64_t *out0, uint64_t *out1, size_t count,
+                                unsigned threads, unsigned blocks) {
+  if (mul < 1 || mul > 4 || !x || !on || !out0 || !out1 || p <= (1ull << 59) || p - (1ull << 59) >= GPQ_FOLD_CMAX) return (int)hipErrorInvalidValue;
+  if (!threads || threads > 256 || !blocks || blocks > 65535 || count > (size_t)threads * blocks) return (int)hipErrorInvalidValue;
+  const size_t cap = (size_t)threads * blocks, bytes = cap * sizeof(uint64_t);
+  uint64_t *dx = nullptr, *d0 = nullptr, *d1 = nullptr;
+  unsigned char *don = nullptr;
+  hipError_t e = hipMalloc((void **)&dx, bytes);
+  if (e == hipSuccess) e = hipMalloc((void **)&d0, bytes);
+  if (e == hipSuccess) e = hipMalloc((void **)&d1, bytes);
+  if (e == hipSuccess) e = hipMalloc((void **)&don, cap);
+  if (e == hipSuccess) e = hipMemcpy(dx, x, bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d0, out0, bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d1, out1, bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(don, on, cap, hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(modprobe_csub_lanes_kernel, dim3(blocks), dim3(threads), 0, 0, mul, make_prime_k(p), dx, don, d0, d1, count);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(out0, d0, bytes, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(out1, d1, bytes, hipMemcpyDeviceToHost);
+  if (dx) (void)hipFree(dx);
+  if (d0) (void)hipFree(d0);
+  if (d1) (void)hipFree(d1);
+  if (don) (void)hipFree(don);
   return (int)e;
 }
 

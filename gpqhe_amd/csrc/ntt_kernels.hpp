@@ -152,8 +152,8 @@ template <> struct LastK<TwS> {
 __device__ __forceinline__ void gs_last(uint64_t &x, uint64_t &y, const LastK<uint64_t> &t, const PrimeK &k) {
   const uint64_t s = x + y;                 // < 8p
   const uint64_t d = x + k.p4 - y;          // (0, 8p)
-  x = canon4(mulmod_lazy(s, t.ninv, k), k);
-  y = canon4(mulmod_lazy(d, t.winv1_ninv, k), k);
+  x = canon4<false>(mulmod_lazy(s, t.ninv, k), k);
+  y = canon4<false>(mulmod_lazy(d, t.winv1_ninv, k), k);
 }
 __device__ __forceinline__ void gs_last(uint64_t &x, uint64_t &y, const LastK<TwS> &t, const PrimeK &k) {   // in: x,y < 3p
   const uint64_t s = x + y;                 // < 6p
@@ -164,16 +164,16 @@ __device__ __forceinline__ void gs_last(uint64_t &x, uint64_t &y, const LastK<Tw
 
 // Per twiddle type: the table pointers of a launch and the lazy ranges the butterflies keep.
 template <typename TW> struct TwTraits;
-template <> struct TwTraits<uint64_t> {
+template <> struct TwTraits<uint64_t> {    // the 7-mad class: select-form subtractions (csub_by, modarith.hpp)
   __device__ static __forceinline__ const uint64_t *table(const PassArgs &a, bool inv) { return inv ? a.winv : a.w; }
-  __device__ static __forceinline__ uint64_t canon_fwd(uint64_t x, const PrimeK &k) { return canon8(x, k); }   // forward data < 8p
-  __device__ static __forceinline__ uint64_t canon_inv(uint64_t x, const PrimeK &k) { return canon4(x, k); }   // inverse data < 4p
+  __device__ static __forceinline__ uint64_t canon_fwd(uint64_t x, const PrimeK &k) { return canon8<false>(x, k); }   // forward data < 8p
+  __device__ static __forceinline__ uint64_t canon_inv(uint64_t x, const PrimeK &k) { return canon4<false>(x, k); }   // inverse data < 4p
   // into the inverse range from a value < 4p / < 8p
   __device__ static __forceinline__ uint64_t inv_from4(uint64_t x, const PrimeK &) { return x; }
-  __device__ static __forceinline__ uint64_t inv_from8(uint64_t x, const PrimeK &k) { return csub4(x, k); }
+  __device__ static __forceinline__ uint64_t inv_from8(uint64_t x, const PrimeK &k) { return csub4<false>(x, k); }
   // a forward-range value as the left (< 2p) / right (< 4p) operand of a variable*variable mulmod_lazy
-  __device__ static __forceinline__ uint64_t left(uint64_t x, const PrimeK &k) { return csub2(csub4(x, k), k); }
-  __device__ static __forceinline__ uint64_t right(uint64_t x, const PrimeK &k) { return csub4(x, k); }
+  __device__ static __forceinline__ uint64_t left(uint64_t x, const PrimeK &k) { return csub2<false>(csub4<false>(x, k), k); }
+  __device__ static __forceinline__ uint64_t right(uint64_t x, const PrimeK &k) { return csub4<false>(x, k); }
 };
 template <> struct TwTraits<TwS> {
   __device__ static __forceinline__ const TwS *table(const PassArgs &a, bool inv) { return inv ? a.winvs : a.ws; }
@@ -876,7 +876,7 @@ __device__ __forceinline__ void keyswitch_back(S &s, const PassArgs &a, uint64_t
 // until the multiplies lost their trailing add; with the looser budget of three waves the scheduler then spreads to 168 registers and
 // spills 22 of them: 9 % slower with 7.7 % fewer instructions.  Stated, the budget gives 122 registers and no spill.  At LOW = 9 (135
 // before; 168 with 26 spilled on the wide limbs after) it gives 128 with 5 spilled, and the n = 2^17 key switch runs 3.4 % faster than
-// with three waves (profiles/r09/v1_n17_lib_ab.txt).
+// with three waves (profiles/r09/v1_n17_lib_ab.txt).  With the masked conditional subtraction (r20): 124 registers and no spill at LOW = 8, 128 with 3 spilled at LOW = 9.
 template <typename TW, int LOW, bool TWO = true, bool NT = false>
 __global__ __launch_bounds__(CONTIG_WAVES * 64, TWO ? 4 : 3) void keyswitch_mid8x2(KeyswitchArgs ka, unsigned first) {
   using TT = TwTraits<TW>;

@@ -3,14 +3,14 @@
     hipcc <the Makefile's FLAGS> --cuda-device-only -S engine.hip -o parent.s     (in the parent's tree, and in this one -> new.s)
     python tools/codeobj_ab.py parent.s new.s [more pairs ...] > profiles/rNN/vK_codeobj_ab.txt
 
-Kernels whose name contains "mid8" (the fused middles of ntt_kernels.hpp) are compared by resources and instruction counts, one row each;
-scalar instructions may differ there and are listed.  Every other kernel must have the same instruction sequence, opcodes and operands.
+Kernels whose name contains "mid8" or "strided_pass" (the fused middles and the strided passes of ntt_kernels.hpp: the he_mul core) are compared
+by resources and instruction counts, one row each; scalar instructions may differ there and are listed.  Every other kernel must have the same instruction sequence, opcodes and operands.
 Exit status 1 when a kernel is missing on one side, a sequence differs, or a count of a mid8 kernel does."""
 import re, subprocess, sys
 
 META = (".vgpr_count", ".vgpr_spill_count", ".group_segment_fixed_size", ".private_segment_fixed_size")
 COUNTS = (("valu", r"v_"), ("mad64", r"v_mad_u64_u32"), ("ds", r"ds_"), ("vmem", r"global_|buffer_"), ("scratch", r"scratch_"), ("branch", r"s_cbranch|s_branch"),
-          ("salu", r"s_"))
+          ("cndmask", r"v_cndmask"), ("salu", r"s_"))
 
 
 def kernels(path):
@@ -42,7 +42,7 @@ def main():
             if sym not in a or sym not in b:
                 bad += 1
                 rows.append("MISSING in %s: %s" % ("parent" if sym not in a else "new", name))
-            elif "mid8" not in sym:
+            elif "mid8" not in sym and "strided_pass" not in sym:
                 if a[sym] == b[sym]:
                     same += 1
                 else:
