@@ -590,14 +590,6 @@ extern "C" int gpq_relin_tail_overwriting(gpq_ctx *c, uint64_t *out, uint64_t *c
   return relin_tail(c, one_place(out), chat, one_place(d), W, dimP, dimB, logql, batch, workspace, s, mode);
 }
 
-// The relinearisation tail as one pass per coefficient (default) or as front + CRT kernels with Q's residues in memory between them;
-// bit-identical (tests run both).
-extern "C" int gpq_set_fused_tail(gpq_ctx *c, int on) {
-  if (!c) return gpq_fail(GPQ_ERR_INVALID, "gpq_set_fused_tail: null context");
-  c->set.fuse_tail = on != 0;
-  return GPQ_OK;
-}
-
 // gpq_he_mul / gpq_he_swk let their inverse transforms hand the CRT kernels limbs already multiplied by (P/p_d)^-1 (default on); off = the
 // CRT kernels do that multiplication themselves.  Same results (tests run both).
 extern "C" int gpq_set_prescale(gpq_ctx *c, int on) {      // 0: off, 1: the CRT weights only, 2: also w_j on the limbs above P for the relinearisation front, 3 (default): the one-product tail

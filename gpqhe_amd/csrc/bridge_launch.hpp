@@ -241,13 +241,6 @@ int crt_decompose_stream(gpq_ctx *c, gpq_bridge_basis *bA, uint64_t *out, const 
   return GPQ_OK;
 }
 
-template <int KS, int WL>
-int launch_relin_tail_t(const RelinTailArgs &a, size_t lds, hipStream_t s) {
-  unsigned blocks = 256 * GPQ_TAIL_WAVES;                  // 4-wave workgroups, GPQ_TAIL_WAVES per CU (registers; their tables fit the LDS twice), persistent over the groups
-  if (blocks > (a.f.total_groups + 3) / 4) blocks = (a.f.total_groups + 3) / 4;
-  return gpq_launch_lds<&bridge_relin_tail_mfma<KS, WL>>((int)kMfmaLdsMax, dim3(blocks), dim3(256), lds, s, a);
-}
-
 template <int KS>
 int launch_relin_front_t(const RelinFrontArgs &a, size_t lds, hipStream_t s) {
   unsigned per_cu = (unsigned)((160 * 1024) / lds);

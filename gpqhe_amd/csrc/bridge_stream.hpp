@@ -26,9 +26,6 @@
 #ifndef GPQ_STREAM_STORE_AUX
 #define GPQ_STREAM_STORE_AUX 2 /* ... and of the streamed stores (results the next kernel reads from HBM anyway: the slabs are far larger than the caches): another -8 % */
 #endif
-#ifndef GPQ_STREAM_PROBE
-#define GPQ_STREAM_PROBE 0     /* 1: no MFMA; 2: also no column folding (timing probes of where the streaming kernels' time goes; wrong results) */
-#endif
 
 namespace gpq {
 
@@ -106,19 +103,6 @@ __device__ __forceinline__ void crt_steps(v16i (&acc)[2][NT], StepRegs (&ring)[R
       for (int q = 0; q < NT; ++q) bf[(s + 1) & 1][q] = bl[((size_t)(s + 1) * NT + q) * 64];
     }
     const v4i A0 = frag_even(x, 0x80808080u), A1 = frag_odd(x, 0x80808080u);
-#if GPQ_STREAM_PROBE >= 1    /* timing probe (wrong results): no matrix-core work, the fragments are folded into one accumulator register */
-#pragma unroll
-    for (int q = 0; q < NT; ++q) {
-      if (s == 0) {
-#pragma unroll
-        for (int e = 0; e < 16; ++e) { acc[0][q][e] = 0; acc[1][q][e] = 0; }
-      }
-      acc[0][q][0] ^= A0[0] ^ A0[1] ^ A0[2] ^ A0[3] ^ bf[s & 1][q][0];
-      acc[1][q][0] ^= A1[0] ^ A1[1] ^ A1[2] ^ A1[3];
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    continue;
-#endif
 #pragma unroll
     for (int q = 0; q < NT; ++q) {
       const v4i b = bf[s & 1][q];
@@ -467,11 +451,7 @@ __global__ __launch_bounds__(512) void bridge_tail_stream(TailStreamArgs a) {
   __syncthreads();
   const unsigned lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const unsigned r = lane & 31, h = lane >> 5, lane16 = r * 16;
-#if GPQ_STREAM_PROBE >= 3     /* timing probe: read the slabs as if every group's limbs were contiguous (512 bytes per limb, group after group) */
-  const unsigned lg = a.logn - 6, sh = 9, sh_out = a.logn + 3;
-#else
-  const unsigned lg = a.logn - 6, sh = a.logn + 3, sh_out = sh;
-#endif
+  const unsigned lg = a.logn - 6, sh = a.logn + 3;
   const unsigned nwaves = gridDim.x * 8, pw = blockIdx.x * 8 + wave;
   const uint64_t tkf0 = a.tkc[WL], tkf1 = a.tkc[WL + 1];
   const uint64_t dkf0 = DCRT ? a.dkc[WL] : 0, dkf1 = DCRT ? a.dkc[WL + 1] : 0;
@@ -479,16 +459,10 @@ __global__ __launch_bounds__(512) void bridge_tail_stream(TailStreamArgs a) {
   const BufRsrc rs_c = slab_rsrc(a.chat, a.chat_bytes), rs_d = slab_rsrc(DCRT ? a.dhat : a.chat, DCRT ? a.dhat_bytes : 0);
   auto chat_of = [&](unsigned g) {                         // byte offsets inside the slabs (< 4 GB: the host checks)
     const unsigned poly = g >> lg, coef0 = (g & ((1u << lg) - 1)) << 6;
-#if GPQ_STREAM_PROBE >= 3
-    return (g * a.dimB) << 9;
-#endif
     return ((poly * a.dimB) << sh) + coef0 * 8;
   };
   auto dhat_of = [&](unsigned g) {
     const unsigned poly = g >> lg, coef0 = (g & ((1u << lg) - 1)) << 6;
-#if GPQ_STREAM_PROBE >= 3
-    return (g * a.dimA) << 9;
-#endif
     return ((poly * a.dimA) << sh) + coef0 * 8;
   };
   StepRegs ring[R];
@@ -524,10 +498,6 @@ __global__ __launch_bounds__(512) void bridge_tail_stream(TailStreamArgs a) {
     uint64_t Q[14];
     int64_t carry = 0;
     uint64_t borrow = 0, prev = 0, cr = 0;
-#if GPQ_STREAM_PROBE >= 2
-#pragma unroll
-    for (int j = 0; j < 14; ++j) Q[j] = (uint64_t)(unsigned)acc[j & 1][j % NT][0] + P[j] + (DCRT ? PD[j] : 0);
-#else
 #pragma unroll
     for (int j = 0; j < WL; ++j) {
       int64_t L, H;
@@ -545,7 +515,6 @@ __global__ __launch_bounds__(512) void bridge_tail_stream(TailStreamArgs a) {
       prev = v;
       if (j % 4 == 3) __builtin_amdgcn_sched_barrier(0);                              // a row tile of accumulators at a time
     }
-#endif
     if (DCRT) {
 #pragma unroll
       for (int j = 0; j < 14; ++j) {
@@ -559,7 +528,7 @@ __global__ __launch_bounds__(512) void bridge_tail_stream(TailStreamArgs a) {
 #pragma unroll
       for (int j = 0; j < 14; j += 2) {
         v4u v = v4u{0, 0, 0, 0};
-        if (ad && j + h < a.W) v = __builtin_amdgcn_raw_buffer_load_b128(rs_ad, (h << sh_out) + lane16, (unsigned)j << sh_out, 0);
+        if (ad && j + h < a.W) v = __builtin_amdgcn_raw_buffer_load_b128(rs_ad, (h << sh) + lane16, (unsigned)j << sh, 0);
         pair_from_load(v, dd[j], dd[j + 1]);
       }
 #pragma unroll
@@ -576,21 +545,15 @@ __global__ __launch_bounds__(512) void bridge_tail_stream(TailStreamArgs a) {
     const size_t flag_at = ((size_t)poly << a.logn) + coef0;
     if (a.force) ambiguous = ambiguous || (coef0 + 2 * r + h) % a.force == 0;
     __builtin_amdgcn_raw_buffer_store_b8((unsigned char)ambiguous, window_rsrc(a.redo + flag_at), 2 * r + h, 0, 0);
-#if GPQ_STREAM_PROBE != 4 && GPQ_STREAM_PROBE != 5
     if (a.tie) __builtin_amdgcn_raw_buffer_store_b8((unsigned char)0, window_rsrc(a.tie + flag_at), 2 * r + h, 0, 0);
     if (a.amb_clear) __builtin_amdgcn_raw_buffer_store_b8((unsigned char)0, window_rsrc(a.amb_clear + flag_at), 2 * r + h, 0, 0);
-#endif
     any |= __builtin_amdgcn_ballot_w64(ambiguous) != 0;
     const BufRsrc rs_out = window_rsrc(a.out.at(poly, (size_t)a.W << a.logn) + coef0);
 #pragma unroll
     for (int j = 0; j < 14; j += 2) {
       const v4u o = pair_for_store(Q[j], Q[j + 1]);
-#if GPQ_STREAM_PROBE == 5
-      if (o[0] == 0x12345678u && j + h < a.W)
-#else
       if (j + h < a.W)
-#endif
-        __builtin_amdgcn_raw_buffer_store_b128(o, rs_out, (h << sh_out) + lane16, (unsigned)j << sh_out, GPQ_STREAM_STORE_AUX);        // (W <= 14: the host checks)
+        __builtin_amdgcn_raw_buffer_store_b128(o, rs_out, (h << sh) + lane16, (unsigned)j << sh, GPQ_STREAM_STORE_AUX);        // (W <= 14: the host checks)
     }
   }
   if (lane == 0) a.wave_any[pw] = any;

@@ -1,5 +1,5 @@
 // bridge_tail.hpp -- host fragment of bridge.hip: the relinearisation tail of he_mul / he_swk (src/he-mult.c:67-77, src/he-automorphism.c:68-76)
-// for q_l = 2^logql.  relin_tail() routes a call to one of four flows; tail_prescale_mode() tells the key switch before it which weights to leave on.
+// for q_l = 2^logql.  relin_tail() routes a call to one of three flows; tail_prescale_mode() tells the key switch before it which weights to leave on.
 #pragma once
 namespace {
 
@@ -40,7 +40,7 @@ int tail_prescale_mode(gpq_ctx *c, unsigned dimP, unsigned dimB, const LimbTab *
   if ((rc = get_basis(c, 0, dimP, &bp)) || (rc = get_basis(c, dimP, dimB - dimP, &bq)) || (rc = get_relin(c, dimP, dimB, &rt))) return rc;
   if (c->set.bridge_mfma && c->logn >= 6 && (rc = get_relin_front(c, dimP, dimB, rt, bp, bq))) return rc;
   bool product = false;
-  if (!c->set.fuse_tail && (rc = tail_product_tables(c, dimP, dimB, rt, bp, bq, &product))) return rc;
+  if ((rc = tail_product_tables(c, dimP, dimB, rt, bp, bq, &product))) return rc;
   if (product && rt->d_tabs_direct) { *tabs = rt->d_tabs_direct; *mode = 3; return GPQ_OK; }
   if (c->set.bridge_mfma && c->logn >= 6 && rt->d_bfrag && rt->d_tabs_w && c->set.prescale_upper) { *tabs = rt->d_tabs_w; *mode = 2; return GPQ_OK; }
   *mode = 1;
@@ -120,16 +120,16 @@ int tail_stream(const Tail &t, const TailD *dh, FlagScope *scope, bool *done, un
 }
 
 // The masked exact finish on the coefficients a fast kernel flagged: r of the ambiguous ones (amb), their round bits, Q's exact CRT of the
-// flagged ones (c->d_redo) into `out`, bridge_addround.  `front` re-runs the front on the flagged groups for Q's residues: first where it also
-// writes flags / amb (one-product tail), after the round bits where the one-pass kernel wrote them.  scope: the launch that wrote the masks;
-// prescaled: chat's limbs of P carry CRT weights; fuse_post: all behind the front in ONE launch (bridge_fallback_tail_post).
-int tail_exact_finish(const Tail &t, const RelinFrontArgs &front, bool front_first, const FlagScope &scope, bool prescaled, bool fuse_post) {
+// flagged ones (c->d_redo) into `out`, bridge_addround.  `front` re-runs the front on the flagged groups first: Q's residues, flags and amb
+// of those groups (chat's weights are off them: plain limbs).  scope: the launch that wrote the masks; fuse_post: all behind the front in
+// ONE launch (bridge_fallback_tail_post).
+int tail_exact_finish(const Tail &t, const RelinFrontArgs &front, const FlagScope &scope, bool fuse_post) {
   gpq_ctx *c = t.c;
   const TailWs &w = t.w;
   int rc;
-  if (front_first && (rc = launch_relin_front(c, t.rt->KS, front, t.rt->lds_bytes, t.s))) return rc;
+  if ((rc = launch_relin_front(c, t.rt->KS, front, t.rt->lds_bytes, t.s))) return rc;
   ReconExtra only_amb;
-  only_amb.only = w.amb; only_amb.prescaled = prescaled; only_amb.scope = scope;
+  only_amb.only = w.amb; only_amb.scope = scope;
   RoundFixArgs rf{w.r, t.bp->d_phalf, w.amb, w.flags, t.tp.Wr, c->logn, scope};
   ReconExtra q;
   q.prescaled = true; q.exact_only = true; q.only = c->d_redo; q.big_b = t.out.b; q.split = t.out.split; q.scope = scope;
@@ -146,7 +146,6 @@ int tail_exact_finish(const Tail &t, const RelinFrontArgs &front, bool front_fir
   }
   if ((rc = launch_reconstruct(c, t.bp, w.r, t.tp.Wr, t.chat, t.dimB, 0, t.polys, 0, false, nullptr, t.s, -1, only_amb))) return rc;
   launch_masked(t, bridge_roundfix, scope, rf);
-  if (!front_first && (rc = launch_relin_front(c, t.rt->KS, front, t.rt->lds_bytes, t.s))) return rc;
   if ((rc = launch_reconstruct(c, t.bq, t.out.a, t.W, w.qhat, t.tp.cnt, 0, t.polys, t.logql, true, w.tie, t.s, -1, q))) return rc;
   launch_masked(t, bridge_addround, scope, ar);
   return GPQ_OK;
@@ -195,8 +194,8 @@ int tail_product(Tail t, const TailD *dh, unsigned rs, bool *rs_done) {
   if (!fuse_pre) launch_masked(t, bridge_limb_scale, scope, un);      // weights off the flagged groups
   // the exact sequence on the flagged groups: front (re-run, writing its flags), r for its ambiguous ones, round bits, Q, finish
   RelinFrontArgs f{t.chat, t.w.qhat, (const v4i *)t.rt->d_bfrag, t.rt->d_lk, t.rt->d_pk, t.rt->d_tkp, t.rt->d_kf, t.w.flags, t.w.amb,
-                   t.dimB, t.dimP, t.tp.cnt, c->logn, t.rt->NT, gpp, gpp * t.polys, c->d_redo, 1u, 0u, 0u, scope};
-  if ((rc = tail_exact_finish(t, f, true, scope, false, fuse_post))) return rc;
+                   t.dimB, t.dimP, t.tp.cnt, c->logn, t.rt->NT, gpp, gpp * t.polys, c->d_redo, 0u, 0u, scope};
+  if ((rc = tail_exact_finish(t, f, scope, fuse_post))) return rc;
   if (rs && rs_done && streamed) {
     launch_masked(t, bridge_rescale_masked, scope, RescaleMaskedArgs{t.out, c->d_redo, t.W, c->logn, rs, t.logql - rs, scope});
     *rs_done = true;
@@ -204,42 +203,7 @@ int tail_product(Tail t, const TailD *dh, unsigned rs, bool *rs_done) {
   return GPQ_OK;
 }
 
-// Q's CRT matrix for the front's one-pass form, or null where that form does not run (gpq_set_fused_tail, in place, shape, LDS)
-int tail_one_pass_tables(const Tail &t, gpq_recon_mfma **tq) {
-  gpq_ctx *c = t.c;
-  *tq = nullptr;
-  const unsigned need = (t.logql + 63) / 64;
-  const int WLf = width_for(need, {7, 14});
-  const bool can_fuse = c->set.fuse_tail && !t.in_place && !c->set.exact_crt && need <= 14 && need + 1 < (unsigned)t.bq->WP && t.bq->pbits >= 160 && t.tp.cnt >= 4 &&
-                        t.tp.cnt <= 4 * RELIN_TAIL_MAXTILES && (t.rt->KS == 2 || t.rt->KS == 4);
-  if (!can_fuse) return GPQ_OK;
-  gpq_recon_mfma *q;
-  if (int rc = get_recon_mfma(c, t.bq, WLf, &q)) return rc;
-  if (q->d_bfrag && q->KS + 1 == t.rt->NT && t.rt->lds_bytes + (size_t)q->KS * ((8 * WLf + 14 + 31) / 32) * 1024 <= kMfmaLdsMax) *tq = q;
-  return GPQ_OK;
-}
-
-// Flow 2, the front in one pass per coefficient (bridge_relin_tail_mfma): front and CRT of Q without the round trip of Q's residues
-int tail_front_one_pass(const Tail &t, RelinFrontArgs f, const gpq_recon_mfma *tq, bool prescaled) {
-  gpq_ctx *c = t.c;
-  const int WLf = width_for((t.logql + 63) / 64, {7, 14});
-  const size_t lds = t.rt->lds_bytes + (size_t)tq->KS * ((8 * WLf + 14 + 31) / 32) * 1024;
-  RelinTailArgs ft{f, (const v4i *)tq->d_bfrag, tq->d_kc, tq->d_pm, c->d_redo, t.w.tie, t.out, t.dbig, t.W, t.logql, tq->KS};
-  int rc;
-  {
-    ProfScope prof(c, GPQ_K_RELIN_TAIL_FUSED, t.s);
-    if (t.rt->KS == 2 && WLf == 7) rc = launch_relin_tail_t<2, 7>(ft, lds, t.s);
-    else if (t.rt->KS == 2) rc = launch_relin_tail_t<2, 14>(ft, lds, t.s);
-    else if (WLf == 7) rc = launch_relin_tail_t<4, 7>(ft, lds, t.s);
-    else rc = launch_relin_tail_t<4, 14>(ft, lds, t.s);
-  }
-  if (rc) return rc;
-  // the few coefficients it flagged: round bits settled exactly, Q's residues made for their groups, exact CRT, finish
-  f.only = c->d_redo;
-  return tail_exact_finish(t, f, false, kNoScope, prescaled, false);
-}
-
-// Flow 3, the matrix-core front as two kernels: the exact kernels only see the coefficients whose rounding the fixed-point estimates cannot
+// Flow 2, the matrix-core front as two kernels: the exact kernels only see the coefficients whose rounding the fixed-point estimates cannot
 // decide.  The one finish that is NOT tail_exact_finish: Q's CRT may take the fast path, which then finishes the tail itself.
 int tail_front(const Tail &t, const RelinFrontArgs &f, bool prescaled) {
   gpq_ctx *c = t.c;
@@ -264,7 +228,7 @@ int tail_front(const Tail &t, const RelinFrontArgs &f, bool prescaled) {
   return GPQ_OK;
 }
 
-// Flow 4, the integer-VALU exact tail: r = x mod P as words, its residues over the limbs above P, the exact division, Q's CRT, the finish
+// Flow 3, the integer-VALU exact tail: r = x mod P as words, its residues over the limbs above P, the exact division, Q's CRT, the finish
 int tail_exact(const Tail &t, bool prescaled) {
   gpq_ctx *c = t.c;
   const TailWs &w = t.w;
@@ -302,8 +266,8 @@ int relin_tail(gpq_ctx *c, Two<uint64_t> out, const uint64_t *chat, Two<const ui
   if (W > (unsigned)bq->WP + 1) return gpq_fail(GPQ_ERR_UNSUPPORTED, "relin: W=%u words exceed the quotient basis", W);
   Tail t{c, s, bp, bq, rt, tp, TailWs(ws, tp, W, (size_t)polys << c->logn), out, chat, dbig, W, dimP, dimB, logql, polys,
          (dbig.a && dbig.a == out.a) || (dbig.b && dbig.b == out.b)};
-  // The flag bytes (c->d_redo) get their final size HERE, before a flow runs: the two flows that copy the pointer into argument blocks (one-product
-  // tail, one-pass front) never grow it; the others reach it only through launch_reconstruct, which sizes it before reading it.  A growth after
+  // The flag bytes (c->d_redo) get their final size HERE, before a flow runs: the flow that copies the pointer into argument blocks (the one-product
+  // tail) never grows it; the others reach it only through launch_reconstruct, which sizes it before reading it.  A growth after
   // such a copy once left bridge_limb_scale with the outgrown buffer -- stale flags, reads past its end (tools/soak_bridge.py, seed 23).
   const size_t flag_bytes = (size_t)polys << c->logn;
   if (chat_prescaled == 3) {
@@ -326,15 +290,12 @@ int relin_tail(gpq_ctx *c, Two<uint64_t> out, const uint64_t *chat, Two<const ui
   }
   if (c->set.bridge_mfma && c->logn >= 6 && (rc = get_relin_front(c, dimP, dimB, rt, bp, bq))) return rc;
   if (c->set.bridge_mfma && c->logn >= 6 && rt->d_bfrag) {
-    gpq_recon_mfma *tq;
-    if ((rc = tail_one_pass_tables(t, &tq))) return rc;
     // the front makes Q's (pre-scaled) residues and the round bits from chat; wsc: the limbs above P arrive multiplied by w_j -- the w-scaled tables
     const unsigned gpp = c->n >> 6;
     const bool wsc = chat_prescaled == 2;
     const RelinFrontArgs f{chat, t.w.qhat, (const v4i *)(wsc ? rt->d_bfrag_w : rt->d_bfrag), rt->d_lk, wsc ? rt->d_pk_w : rt->d_pk, wsc ? rt->d_tkp_w : rt->d_tkp, rt->d_kf,
-                           t.w.flags, t.w.amb, dimB, dimP, tp.cnt, c->logn, rt->NT, gpp, gpp * polys, nullptr, 0u, chat_prescaled ? 1u : 0u, wsc ? 1u : 0u};
-    if (tq && (rc = ensure_redo(c, flag_bytes, s))) return rc;
-    rc = tq ? tail_front_one_pass(t, f, tq, chat_prescaled != 0) : tail_front(t, f, chat_prescaled != 0);
+                           t.w.flags, t.w.amb, dimB, dimP, tp.cnt, c->logn, rt->NT, gpp, gpp * polys, nullptr, chat_prescaled ? 1u : 0u, wsc ? 1u : 0u};
+    rc = tail_front(t, f, chat_prescaled != 0);
   } else {
     if (chat_prescaled == 2) return gpq_fail(GPQ_ERR_INVALID, "relin_tail: w-scaled limbs need the matrix-core front");
     rc = tail_exact(t, chat_prescaled != 0);

@@ -426,7 +426,7 @@ namespace {
 
 static const char *const kKernelNames[GPQ_K_COUNT] = {"strided_fwd", "strided_inv", "contig_fwd", "contig_inv",
                                                       "tensor_mid", "keyswitch_mid", "pointwise", "small_ntt", "reference_redo",
-                                                      "bridge_decompose", "bridge_reconstruct", "bridge_relin_front", "bridge_relin_tail_fused", "bridge_exact_paths", "bridge_rescale",
+                                                      "bridge_decompose", "bridge_reconstruct", "bridge_relin_front", "bridge_exact_paths", "bridge_rescale",
                                                       "bridge_relin_tail_direct", "bridge_crt_decompose", "bridge_tail_stream",
                                                       "keyswitch_rot_mid", "automorphism_gather", "gemv_mac", "he_ecd_lds", "he_dcd_lds",
                                                       "sample_bytes", "enc_small_tail", "genswk_crt_tail", "surf_stream", "gemv_mac_multi",

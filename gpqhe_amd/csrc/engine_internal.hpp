@@ -77,9 +77,9 @@ using gpq_stream_own = gpq_handle<hipStream_t, hipStreamDestroy>;
 struct gpq_prof_rec { int kernel = 0; gpq_event a, b; };
 enum { GPQ_K_STRIDED_FWD = 0, GPQ_K_STRIDED_INV, GPQ_K_CONTIG_FWD, GPQ_K_CONTIG_INV, GPQ_K_TENSOR_MID,
        GPQ_K_KEYSWITCH_MID, GPQ_K_POINTWISE, GPQ_K_SMALL, GPQ_K_REFERENCE,
-       // the MPI <-> RNS bridge (bridge.hip): rns_decompose, the CRT fast paths, the relinearisation front, its one-pass form, the exact /
+       // the MPI <-> RNS bridge (bridge.hip): rns_decompose, the CRT fast paths, the relinearisation front, the exact /
        // masked kernels (bridge_reconstruct, bridge_roundfix, bridge_addround, bridge_exactdiv), he_rs
-       GPQ_K_DECOMPOSE, GPQ_K_RECONSTRUCT, GPQ_K_RELIN_FRONT, GPQ_K_RELIN_TAIL_FUSED, GPQ_K_BRIDGE_EXACT, GPQ_K_RESCALE, GPQ_K_RELIN_TAIL_DIRECT,
+       GPQ_K_DECOMPOSE, GPQ_K_RECONSTRUCT, GPQ_K_RELIN_FRONT, GPQ_K_BRIDGE_EXACT, GPQ_K_RESCALE, GPQ_K_RELIN_TAIL_DIRECT,
        // bridge_stream.hpp: CRT(d2hat) -> rns_decompose in one kernel; the one-product tail with its addend's CRT in the same kernel
        GPQ_K_CRT_DECOMPOSE, GPQ_K_TAIL_STREAM,
        // gpq_he_rot_hoisted: the key switch of one rotation from the shared NTT-domain input (keyswitch_rot_mid8x2, two-pass rings); the plain
@@ -203,9 +203,6 @@ struct gpq_settings {
   bool prescale = true;               // gpq_he_mul / gpq_he_swk: inverse passes write limbs pre-multiplied by (P/p_d)^-1 for the CRT kernels (gpq_set_prescale)
   bool prescale_upper = true;         // ... and the limbs above P by w_j for the relinearisation front
   bool tail_direct = true;            // ... or every limb by the weights of the whole basis: the relinearisation tail as ONE product (bridge_tables.hpp: get_tail_direct)
-  bool fuse_tail = false;             // gpq_set_fused_tail(ctx, 1): the relinearisation tail in one pass per coefficient (bridge_relin_tail_mfma) -- measured 2 % SLOWER
-                                      // than the two-kernel form on the whole he_mul (profiles/r03/v3_fused_tail_ab.txt: both are bound by integer VALU work, not by the
-                                      // 60 words per coefficient the fusion saves), kept for the parity tests and as the record of the attempt
 };
 
 // Every device allocation, stream and event below is an owner: `delete` releases all a context holds, in any order.

@@ -115,11 +115,6 @@ class PolyContext:
         """matrix-core (default) or integer-VALU rns_decompose; both are exact, the tests compare them"""
         _native.check(self.lib.gpq_set_bridge_mfma(self.h, 1 if on else 0), "gpq_set_bridge_mfma")
 
-    def set_fused_tail(self, on):
-        """with set_prescale(2): relinearisation tail in one pass per coefficient (1) or as front + CRT kernels (0, the default: the
-        one-pass form measured 2 % slower); both exact, the tests compare them"""
-        _native.check(self.lib.gpq_set_fused_tail(self.h, 1 if on else 0), "gpq_set_fused_tail")
-
     PRESCALE_DEFAULT = 3
 
     def set_prescale(self, mode):

@@ -271,9 +271,6 @@ int gpq_debug_split_entry_fits_wide(uint64_t p, uint64_t x, uint64_t y);
  * `before` 1 = flagged, `after` all 0), returning the number of words of that group (at most `capacity` are written), -1 without a watch. */
 int gpq_debug_zero_watch(gpq_ctx *ctx, int on);
 long gpq_debug_zero_flags(gpq_ctx *ctx, unsigned *before, unsigned *after, size_t capacity);
-/* With gpq_set_prescale(ctx, 2): the tail of he_relin / he_swk as two kernels with Q's residues in memory between them (0, default) or in one pass per coefficient (1:
- * measured 2 % slower on the whole he_mul -- both forms are bound by integer VALU work); same results. */
-int gpq_set_fused_tail(gpq_ctx *ctx, int on);
 /* gpq_he_mul / gpq_he_swk: the inverse transforms hand the kernels that follow limbs already multiplied by their CRT weights -- 3 (default): the key
  * switch's limbs carry the weights of its WHOLE basis and the relinearisation tail is one product (quotient, rounding and centring together);
  * 2: (P/p_d)^-1 on the limbs of each basis and w_j = P^-1 (Pi'/p_j)^-1 on the limbs above P for the relinearisation front; 1: the former only;

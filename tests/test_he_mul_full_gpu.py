@@ -75,7 +75,7 @@ def test_he_swk_matches_reference_semantics(engine_ctx, oracle_ctx, logn, logqL,
     assert big_to_ints(to_host(out1), W, n)[0] == e1
 
 
-@pytest.mark.parametrize("mfma", [True, False, "fused", "direct"])      # matrix-core front + CRT, integer-VALU kernels, the one-pass tail (gpq_set_fused_tail), the one-product tail
+@pytest.mark.parametrize("mfma", [True, False, "direct"])      # matrix-core front + CRT, integer-VALU kernels, the one-product tail
 @pytest.mark.parametrize("logqL", [120, 200, 438, 610])
 def test_relin_tail_rounding_ties_and_wrap_corner(engine_ctx, oracle_ctx, logqL, mfma):
     """mpi_rdiv rounds up only when the remainder is strictly above floor(P/2) (src/types.c:124): key-switch
@@ -87,7 +87,6 @@ def test_relin_tail_rounding_ties_and_wrap_corner(engine_ctx, oracle_ctx, logqL,
     dimP, dimA, dimB, dimevk = probe.he_dims(logqL, logqL)       # dimP = 3 (VALU tail only), 4, 8, 11 (matrix-core front)
     g, o = engine_ctx(logn, dimevk), oracle_ctx(logn, dimevk)
     g.set_bridge_mfma(bool(mfma))
-    g.set_fused_tail(mfma == "fused")
     n, W, ql = g.n, (logqL + 64) // 64, 1 << logqL
     P = ref.RnsBasis(o.p[:dimP]).P
     PiB = ref.RnsBasis(o.p[:dimB]).P
@@ -121,7 +120,6 @@ def test_relin_tail_rounding_ties_and_wrap_corner(engine_ctx, oracle_ctx, logqL,
         assert big_to_ints(to_host(inplace), W, n)[0] == exp[0]
     finally:
         g.set_bridge_mfma(True)
-        g.set_fused_tail(False)
 
 
 def test_he_mul_by_one_is_identity_full_size(engine_ctx):
@@ -489,10 +487,9 @@ def test_he_mul_squaring_path_equals_the_general_path(engine_ctx):
 
 
 @pytest.mark.parametrize("logn,logq,batch", [(13, 438, 3), (16, 850, 2), (14, 300, 2)])
-def test_one_pass_relinearisation_tail_equals_the_two_kernel_form(engine_ctx, logn, logq, batch):
-    """gpq_set_fused_tail(ctx, 1): bridge_relin_tail_mfma (front + CRT of Q in one pass per coefficient, Q's residues never in memory)
-    against the default two-kernel tail on dense random ciphertexts, whole he_mul and he_swk (c1 without addend), at the headline
-    shape too: identical words."""
+def test_prescale_levels_3_2_0_1_give_identical_words_for_he_mul_and_he_swk(engine_ctx, logn, logq, batch):
+    """gpq_set_prescale(ctx, 3 / 2 / 0 / 1): the one-product tail against the matrix-core front on w-scaled, plain and CRT-weighted limbs,
+    on dense random ciphertexts, whole he_mul and he_swk (c1 without addend), at the headline shape too: identical words."""
     torch = _torch()
     probe = engine_ctx(logn, 20)
     dimP, dimA, dimB, dimevk = probe.he_dims(logq, logq)
@@ -514,8 +511,7 @@ def test_one_pass_relinearisation_tail_equals_the_two_kernel_form(engine_ctx, lo
         # ... and with / without the inverse transforms pre-multiplying their output by the CRT weights (gpq_set_prescale)
         # (0 = no scaling, 1 = the CRT weights on the limbs of each basis, 2 = also w_j on the limbs above P for the relinearisation front)
         #  3 = every limb of the key switch by the weights of its whole basis: the relinearisation tail as ONE product)
-        for fused, prescale in ((False, 3), (False, 2), (True, 2), (False, 0), (True, 0), (False, 1), (True, 1)):
-            g.set_fused_tail(fused)
+        for prescale in (3, 2, 0, 1):
             g.set_prescale(prescale)
             o0, o1 = torch.empty_like(cts[0]), torch.empty_like(cts[0])
             g.he_mul(o0, o1, *cts, rlk[0], rlk[1], W, logq, dimA, dimB, dimP)
@@ -524,7 +520,6 @@ def test_one_pass_relinearisation_tail_equals_the_two_kernel_form(engine_ctx, lo
             torch.cuda.synchronize()
             outs.append((o0, o1, s0, s1))
     finally:
-        g.set_fused_tail(False)
         g.set_prescale(3)
     for other in outs[1:]:
         for a, b in zip(outs[0], other):

@@ -1,8 +1,7 @@
 """Which kernels the relinearisation tail launches on each of its routes, and that every route writes the reference's words.
 
-relin_tail (gpqhe_amd/csrc/bridge_tail.hpp) is a router over four flows -- the one-product tail (as a stream, or as one matrix product),
-the matrix-core front in its two-kernel and its one-pass form, the integer-VALU exact tail -- plus the un-weighting fall-back of the
-one-product tail.  Each case below reaches one route by the smallest shape that does, compares every output word with the restated
+relin_tail (gpqhe_amd/csrc/bridge_tail.hpp) is a router over three flows -- the one-product tail (as a stream, or as one matrix product),
+the matrix-core front, the integer-VALU exact tail -- plus the un-weighting fall-back of the one-product tail.  Each case below reaches one route by the smallest shape that does, compares every output word with the restated
 reference (oracle/bigint_ref), and pins the number of profiled launches per class (gpq_profile_collect: one record per ProfScope).  The
 counts do not depend on the data: the masked kernels are launched whether or not a coefficient is flagged.  They were recorded from the
 build BEFORE the tail was split into flow functions, and each is the sum of the launches its comment names."""
@@ -16,7 +15,7 @@ from oracle import bigint_ref as ref
 
 pytestmark = pytest.mark.gpu
 
-CLASSES = ("bridge_tail_stream", "bridge_relin_tail_direct", "bridge_relin_tail_fused", "bridge_relin_front", "bridge_reconstruct",
+CLASSES = ("bridge_tail_stream", "bridge_relin_tail_direct", "bridge_relin_front", "bridge_reconstruct",
            "bridge_exact_paths", "bridge_rescale", "bridge_decompose", "bridge_crt_decompose")
 
 
@@ -41,32 +40,29 @@ def _profiled(g, call):
 # ---------------------------------------------------------------------------
 # the bare tail: n = 2^7, one polynomial, dims of he_dims(logqL, logqL)
 # ---------------------------------------------------------------------------
-# route: (logqL, fused tail, overwriting entry point, in place, launches per class)
+# route: (logqL, overwriting entry point, in place, launches per class)
 BARE = {
     # dimP = 3: no matrix-core front (it needs 4 limbs of P).  exact: r (full-width CRT), bridge_exactdiv, the exact kernel behind Q's fast
     # CRT, bridge_addround; decompose: r over the limbs above P; reconstruct: Q's fast CRT
-    "valu": (120, False, False, False, {"bridge_exact_paths": 4, "bridge_decompose": 1, "bridge_reconstruct": 1}),
+    "valu": (120, False, False, {"bridge_exact_paths": 4, "bridge_decompose": 1, "bridge_reconstruct": 1}),
     # front: bridge_relin_front_mfma; exact: r of the ambiguous coefficients, bridge_roundfix, the exact kernel behind Q's fast CRT,
     # bridge_addround; reconstruct: Q's fast CRT finishing into `out`
-    "front": (200, False, False, False, {"bridge_relin_front": 1, "bridge_exact_paths": 4, "bridge_reconstruct": 1}),
+    "front": (200, False, False, {"bridge_relin_front": 1, "bridge_exact_paths": 4, "bridge_reconstruct": 1}),
     # the same launches with Q parked in the workspace (qc) and bridge_addround finishing every coefficient
-    "front in place": (200, False, False, True, {"bridge_relin_front": 1, "bridge_exact_paths": 4, "bridge_reconstruct": 1}),
-    # fused: bridge_relin_tail_mfma; exact: r of the ambiguous coefficients, bridge_roundfix, the front re-run on the flagged groups, Q's
-    # exact CRT, bridge_addround
-    "one pass": (438, True, False, False, {"bridge_relin_tail_fused": 1, "bridge_exact_paths": 5}),
+    "front in place": (200, False, True, {"bridge_relin_front": 1, "bridge_exact_paths": 4, "bridge_reconstruct": 1}),
     # stream: bridge_tail_stream<6, 0, false, 3> (the weights go on outside the profile); exact: bridge_limb_scale, the front re-run,
     # bridge_fallback_tail_post<8, 16> (P is an 8-word basis, Pi' a 16-word one: r, its round bit, Q's exact CRT and the finish in one launch)
-    "product": (438, False, True, False, {"bridge_tail_stream": 1, "bridge_exact_paths": 3}),
+    "product": (438, True, False, {"bridge_tail_stream": 1, "bridge_exact_paths": 3}),
     # the product cannot run over its own addend: exact: bridge_limb_scale on every coefficient, then the "front" route's four;
     # front and reconstruct as there
-    "product in place": (438, False, True, True, {"bridge_relin_front": 1, "bridge_exact_paths": 5, "bridge_reconstruct": 1}),
+    "product in place": (438, True, True, {"bridge_relin_front": 1, "bridge_exact_paths": 5, "bridge_reconstruct": 1}),
 }
 
 
 @pytest.mark.parametrize("route", list(BARE))
 def test_bare_tail_routes(engine_ctx, oracle_ctx, route):
     torch = _torch()
-    logqL, fused, overwriting, in_place, want = BARE[route]
+    logqL, overwriting, in_place, want = BARE[route]
     logn = 7
     dimP, dimA, dimB, dimevk = engine_ctx(logn, 12).he_dims(logqL, logqL)
     g, o = engine_ctx(logn, dimevk), oracle_ctx(logn, dimevk)
@@ -78,16 +74,10 @@ def test_bare_tail_routes(engine_ctx, oracle_ctx, route):
     d = to_device(ints_to_big(dvals, W))
     out = d if in_place else torch.empty(W * n, dtype=torch.int64, device="cuda")
     tail = g.relin_tail_overwriting if overwriting else g.relin_tail
-    try:
-        g.set_fused_tail(fused)
-        got = _profiled(g, lambda: tail(out, to_device(chat), d, W, logqL, dimB, dimP))
-    finally:
-        g.set_fused_tail(False)
+    got = _profiled(g, lambda: tail(out, to_device(chat), d, W, logqL, dimB, dimP))
     print("%s: %s" % (route, got))
     assert big_to_ints(to_host(out), W, n)[0] == exp
     assert got == want
-    if route == "one pass":
-        assert "bridge_relin_tail_fused" in got              # (not another route's counts pinned under this name)
     if route == "product in place":
         assert "bridge_relin_tail_direct" not in got and "bridge_tail_stream" not in got and "bridge_relin_front" in got
 

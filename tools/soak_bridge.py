@@ -92,12 +92,11 @@ for it in range(N):
     h = gpqhe_amd.PolyContext(logn, max(dimevk, 20)) if fresh else g
     h.set_chunk(chunk); h.set_stream_bridge(True); h.set_lazy_decompose(True); h.debug_force_redo(force); h.set_overlap(lanes)
     # a quarter of the time one of the older kernel families instead of the default (every setting must give the same words, also from a fresh
-    # context, after growth, on a side stream): prescale 0 / 1 / 2 (+ the fused tail), the integer-VALU bridge, the exact CRT everywhere
-    other = rng.choice((None, None, None, "prescale0", "prescale1", "prescale2", "prescale2+fused", "valu", "exact", "nostream"))
+    # context, after growth, on a side stream): prescale 0 / 1 / 2, the integer-VALU bridge, the exact CRT everywhere
+    other = rng.choice((None, None, None, "prescale0", "prescale1", "prescale2", "valu", "exact", "nostream"))
     if other == "prescale0": h.set_prescale(0)
     elif other == "prescale1": h.set_prescale(1)
     elif other == "prescale2": h.set_prescale(2)
-    elif other == "prescale2+fused": h.set_prescale(2); h.set_fused_tail(True)
     elif other == "valu": h.set_bridge_mfma(False)
     elif other == "exact": h.set_exact_crt(True)
     elif other == "nostream": h.set_stream_bridge(False)
@@ -113,7 +112,7 @@ for it in range(N):
     else:
         got = run(h, cts, rlk, W, logql, (dimP, dimA, dimB))
     g.debug_force_redo(0); g.set_chunk(32); g.set_overlap(True)
-    g.set_prescale(3); g.set_fused_tail(False); g.set_bridge_mfma(True); g.set_exact_crt(False); g.set_stream_bridge(True)
+    g.set_prescale(3); g.set_bridge_mfma(True); g.set_exact_crt(False); g.set_stream_bridge(True)
     bad = [i for i, (a, b) in enumerate(zip(want, got)) if not torch.equal(a, b)]
     if bad:
         print("MISMATCH at config %d: logn %d logqL %d logql %d dims %s batch %d chunk %d force %d lanes %d fresh %d settings %s outputs %s" % (it, logn, logqL, logql, (dimP, dimA, dimB), batch, chunk, force, lanes + 1, fresh, other, bad), flush=True)
