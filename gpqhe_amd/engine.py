@@ -112,7 +112,8 @@ class PolyContext:
         return big
 
     def set_bridge_mfma(self, on):
-        """matrix-core (default) or integer-VALU rns_decompose; both are exact, the tests compare them"""
+        """matrix-core (default) or integer-VALU rns_decompose (off: also the CRT sum and the tail on the integer VALU); read by every call that
+        decomposes or reconstructs -- the he_mul / he_swk / he_rot_hoisted / he_gemv family, he_mulpt, poly_mul, he_dec, he_enc_*, he_genswk*, gemv plans; same words"""
         _native.check(self.lib.gpq_set_bridge_mfma(self.h, 1 if on else 0), "gpq_set_bridge_mfma")
 
     PRESCALE_DEFAULT = 3
@@ -120,20 +121,25 @@ class PolyContext:
     def set_prescale(self, mode):
         """he_mul / he_swk: what the inverse transforms pre-multiply for the kernels behind them -- 3 (default, also True): the weights of the
         key switch's whole basis, the relinearisation tail is one product; 2: per-basis CRT weights + w_j for the relinearisation front;
-        1: per-basis CRT weights; 0 / False: nothing.  All exact; the tests compare them."""
+        1: per-basis CRT weights; 0 / False: nothing.  All exact; the tests compare them.  Two-pass rings only; he_rot_hoisted and, through it,
+        he_gemv / he_gemv_planned / he_gemv_multi make the same choice.  Calls without a key switch do not read it."""
         mode = self.PRESCALE_DEFAULT if mode is True else int(mode)
         _native.check(self.lib.gpq_set_prescale(self.h, mode), "gpq_set_prescale")
 
     def set_stream_bridge(self, on):
-        """he_mul / he_swk: the fused streaming bridge kernels (default) or round 3's separate kernels; same words"""
+        """he_mul / he_swk, and the tail of every rotation of he_rot_hoisted / he_gemv / he_gemv_planned / he_gemv_multi: the fused streaming bridge
+        kernels (default) or round 3's separate kernels; same words.  Calls without a key switch do not read it."""
         _native.check(self.lib.gpq_set_stream_bridge(self.h, 1 if on else 0), "gpq_set_stream_bridge")
 
     def set_lazy_decompose(self, on):
-        """he_mul: its internal rns_decompose output may stay in (0, 3p) for the forward transforms (default) or be canonical; same results"""
+        """he_mul and he_swk (so also he_rot_hoisted of one rotation and the giant steps of the he_gemv family) on two-pass rings: their
+        rns_decompose output may stay in (0, 3p) for the forward transforms (default) or be canonical; same results.  The hoisted decomposition
+        of he_rot_hoisted and the plans are always canonical."""
         _native.check(self.lib.gpq_set_lazy_decompose(self.h, 1 if on else 0), "gpq_set_lazy_decompose")
 
     def set_overlap(self, on):
-        """he_mul / he_swk / tensor / key switch over several launch groups: -1 = two lanes when affordable (default), 0 / False = one, 1 / True = two; same words"""
+        """he_mul / he_swk / tensor / key switch over several launch groups: -1 = two lanes when affordable (default), 0 / False = one, 1 / True = two; same words.
+        he_rot_hoisted and the he_gemv family keep their groups in order on the caller's stream whatever this says."""
         v = -1 if (on is not True and on is not False and int(on) < 0) else (1 if on else 0)
         _native.check(self.lib.gpq_set_overlap(self.h, v), "gpq_set_overlap")
 
@@ -154,7 +160,8 @@ class PolyContext:
         _native.check(self.lib.gpq_set_nt_policy(self.h, int(mode)), "gpq_set_nt_policy")
 
     def debug_force_redo(self, every):
-        """tests: the streaming bridge kernels also flag every coefficient whose index is a multiple of `every` (0: off)"""
+        """tests: the streaming bridge kernels (he_mul's CRT -> decompose, the one-product tail of he_mul / he_swk / he_rot_hoisted / he_gemv*) also
+        flag every coefficient whose index is a multiple of `every` (0: off)"""
         _native.check(self.lib.gpq_debug_force_redo(self.h, int(every)), "gpq_debug_force_redo")
 
     def debug_zero_watch(self, on=True):
@@ -170,6 +177,8 @@ class PolyContext:
         return before, after
 
     def set_exact_crt(self, on):
+        """tests: the full-width CRT kernel for every coefficient of every reconstruction (rns_reconstruct, poly_mul, he_mulpt, he_dec, he_enc_*,
+        gemv_inner, the relinearisation tail of the he_mul / he_swk / he_rot_hoisted / he_gemv family); same words"""
         _native.check(self.lib.gpq_set_exact_crt(self.h, 1 if on else 0), "gpq_set_exact_crt")
 
     def poly_mul(self, r, a, b, W, dim, logq):

@@ -224,11 +224,18 @@ int gpq_rns_reconstruct(gpq_ctx *ctx, uint64_t *big, unsigned Wout, const uint64
                         unsigned logq, void *stream);
 /* gpq_rns_reconstruct takes a low-word fast path when q is a power of two shorter than P and redoes the
  * (rare) coefficients whose rounding it cannot decide with the exact full-width kernel; this forces the
- * exact kernel for everything (used by the tests to cross-check the two). */
+ * exact kernel for everything (used by the tests to cross-check the two).
+ * Reaches every call that reconstructs: gpq_rns_reconstruct itself, gpq_poly_mul, gpq_he_mulpt, gpq_he_dec, gpq_he_enc_pk / _sk, gpq_gemv_inner
+ * and the plans' inner sums, and the relinearisation tail of gpq_he_mul / gpq_he_mul_rs / gpq_he_swk / gpq_he_rot_hoisted / gpq_he_gemv /
+ * gpq_he_gemv_planned / gpq_he_gemv_multi, which then leaves the one-product tail for the matrix-core front.  Same words
+ * (tests/test_settings_derived_gpu.py, tests/test_settings_bridge_calls_gpu.py). */
 int gpq_set_exact_crt(gpq_ctx *ctx, int on);
 /* gpq_he_mul / gpq_he_swk: 1 (default) = the bridge as streaming kernels (gpqhe_amd/csrc/bridge_stream.hpp): poly_rns2mpi(d2) -> rns_decompose
  * (src/he-mult.c:140, :59) in one kernel, and the relinearisation tail (:67-77) as one product that makes its addend d0 / d1 (:139, :141) from the
- * limbs on the spot -- d0, d1, d2 never exist as words; 0 = round 3's separate CRT, decompose and tail kernels.  Same words (the tests run both). */
+ * limbs on the spot -- d0, d1, d2 never exist as words; 0 = round 3's separate CRT, decompose and tail kernels.  Same words (the tests run both).
+ * The streaming tail is also the tail of gpq_he_rot_hoisted, gpq_he_gemv, gpq_he_gemv_planned and gpq_he_gemv_multi (every rotation goes through it),
+ * so the switch reaches them as it reaches gpq_he_swk; the CRT -> decompose kernel is gpq_he_mul's alone.  The calls without a key switch
+ * (gpq_he_mulpt, gpq_poly_mul, gpq_he_dec, gpq_he_enc_*, gpq_he_genswk*, the gemv plans) do not read it. */
 int gpq_set_stream_bridge(gpq_ctx *ctx, int on);
 /* gpq_he_mul / gpq_he_swk / gpq_he_mul_tensor / gpq_keyswitch over more than one launch group (batch > gpq_set_chunk's group): with two LANES every
  * other group runs on a second, internal stream through an internal peer context, so that the launch tails of one group fill with the other's
@@ -239,7 +246,10 @@ int gpq_set_stream_bridge(gpq_ctx *ctx, int on);
  * pairs, per-limb constants, bridge constants: gpq_debug_table_bytes) and owns only its flag words and scratch.  GAIN: +10-15 % at the reference's default shape (logn 14) on every device measured; at the headline
  * shape it depends on the device (+0.15 % ... +3.9 %: a group's kernels are long, the lanes share one power cap); never a loss.  If the peer cannot
  * be created the context continues on one lane; if a workspace cannot be allocated, shapes of that size do (one line on stderr, no error).  Not taken while gpq_profile is on.
- * gpq_last_lanes: the lanes (1 or 2) the last such call on this context ran on. */
+ * gpq_last_lanes: the lanes (1 or 2) the last such call on this context ran on.
+ * Only gpq_he_mul, gpq_he_mul_rs, gpq_he_swk, gpq_he_mul_tensor and gpq_keyswitch split their groups over the lanes.  gpq_he_rot_hoisted and the
+ * gpq_he_gemv family run their launch groups in order on the caller's stream (their inner gpq_he_swk calls see one group each); they give the
+ * same words on a context with the setting on. */
 int gpq_set_overlap(gpq_ctx *ctx, int on);
 unsigned gpq_last_lanes(const gpq_ctx *ctx);
 /* Tests: 1 = the next attempt to create the peer lane fails as an allocation would (the call runs on one lane, one line on stderr, and the context
@@ -251,13 +261,17 @@ int gpq_debug_fail_peer(gpq_ctx *ctx, int on);
  * every table pointer of the peer IS the context's. */
 size_t gpq_debug_table_bytes(const gpq_ctx *ctx, int which);
 /* gpq_he_mul: 1 (default) = its internal rns_decompose launches leave residues in (0, 3p), which the forward transforms behind them accept;
- * 0 = canonical residues.  Same results. */
+ * 0 = canonical residues.  Same results.  Read by gpq_he_mul / gpq_he_mul_rs and gpq_he_swk on two-pass rings (logn > 12), hence by the
+ * single-rotation path of gpq_he_rot_hoisted and the giant steps of the gpq_he_gemv family, which are gpq_he_swk calls.  The hoisted decomposition
+ * of gpq_he_rot_hoisted (two rotations or more), the plans and the calls without a key switch always produce canonical residues. */
 int gpq_set_lazy_decompose(gpq_ctx *ctx, int on);
 /* Cache policy of the slab loads / stores of the transform kernels (gpq_ntt, gpq_invntt, gpq_poly_mul_rns, gpq_mulpt_rns, gpq_he_mul_tensor,
  * gpq_keyswitch and everything built on them): -1 (default) = non-temporal when a launch group's slabs exceed the Infinity Cache (288 MiB is the
  * threshold), the default policy when they fit; 0 = never; 1 = always.  Never changes a word. */
 int gpq_set_nt_policy(gpq_ctx *ctx, int mode);
-/* Tests: the streaming kernels also flag every coefficient whose index is a multiple of `every` for the exact kernels behind them (0 = off). */
+/* Tests: the streaming kernels also flag every coefficient whose index is a multiple of `every` for the exact kernels behind them (0 = off).
+ * The streaming kernels are gpq_he_mul's CRT -> decompose and the one-product tail, so this reaches the tail of gpq_he_mul / gpq_he_mul_rs /
+ * gpq_he_swk / gpq_he_rot_hoisted / gpq_he_gemv / gpq_he_gemv_planned / gpq_he_gemv_multi where that tail runs; nothing else reads it. */
 int gpq_debug_force_redo(gpq_ctx *ctx, unsigned every);
 /* Tests (host only, no device needed): the check every split-twiddle pair (x, y) = (p - w, p - w 2^31 mod p) of a limb must pass before the limb
  * may run the wide-split butterflies -- for every multiplicand up to 8p - 1 the 92-bit sum of the split multiply, with its injected constant
@@ -274,10 +288,15 @@ long gpq_debug_zero_flags(gpq_ctx *ctx, unsigned *before, unsigned *after, size_
 /* gpq_he_mul / gpq_he_swk: the inverse transforms hand the kernels that follow limbs already multiplied by their CRT weights -- 3 (default): the key
  * switch's limbs carry the weights of its WHOLE basis and the relinearisation tail is one product (quotient, rounding and centring together);
  * 2: (P/p_d)^-1 on the limbs of each basis and w_j = P^-1 (Pi'/p_j)^-1 on the limbs above P for the relinearisation front; 1: the former only;
- * 0: neither.  Same results. */
+ * 0: neither.  Same results.  Two-pass rings (logn > 12) only; smaller rings never pre-multiply.  gpq_he_rot_hoisted makes the same choice
+ * for its permuted key switch and tail (gpq_he_gemv, gpq_he_gemv_planned and gpq_he_gemv_multi rotate through it), and gpq_relin_tail_overwriting
+ * takes the one-product tail only under 3.  The calls without a key switch do not read it. */
 int gpq_set_prescale(gpq_ctx *ctx, int on);
 /* rns_decompose is a product of the coefficients' bytes with a fixed matrix (256^k mod p_j) and runs on the matrix cores
- * (v_mfma_i32_32x32x32_i8, exact) by default; 0 selects the integer-VALU kernel instead (the tests cross-check the two). */
+ * (v_mfma_i32_32x32x32_i8, exact) by default; 0 selects the integer-VALU kernel instead (the tests cross-check the two).
+ * 0 also turns off the matrix-core CRT sum of gpq_rns_reconstruct and the matrix-core tails (the relinearisation tail becomes the integer-VALU
+ * one).  Every call that decomposes or reconstructs reads it: the gpq_he_mul / gpq_he_swk / gpq_he_rot_hoisted / gpq_he_gemv* family, gpq_he_mulpt,
+ * gpq_poly_mul, gpq_he_dec, gpq_he_enc_*, gpq_he_genswk*, gpq_gemv_plan_create*.  Same words for all of them. */
 int gpq_set_bridge_mfma(gpq_ctx *ctx, int on);
 
 /* poly_mul, src/poly.c:84-107 (decl src/poly.h:86-87), q = 2^logq, on big slabs of W words. */
