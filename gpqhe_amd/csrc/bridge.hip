@@ -384,7 +384,7 @@ int hoist_plan(gpq_ctx *c, unsigned W, unsigned dimB, unsigned dimP, unsigned nr
 extern "C" size_t gpq_he_rot_hoisted_workspace_bytes(gpq_ctx *c, unsigned W, unsigned dimB, unsigned dimP, unsigned nrot, unsigned batch) {
   if (!c || !nrot || !batch) return 0;
   HoistPlan h;
-  return hoist_plan(c, W, dimB, dimP, nrot, batch < c->set.chunk ? batch : c->set.chunk, &h) == GPQ_OK ? h.total : 0;
+  return hoist_plan(c, W, dimB, dimP, nrot, gpq_group_size(c, batch), &h) == GPQ_OK ? h.total : 0;
 }
 
 extern "C" int gpq_he_rot_hoisted(gpq_ctx *c, uint64_t *out_c0, uint64_t *out_c1, const uint64_t *c0, const uint64_t *c1,
@@ -400,12 +400,11 @@ extern "C" int gpq_he_rot_hoisted(gpq_ctx *c, uint64_t *out_c0, uint64_t *out_c1
   const size_t n = c->n, bigpoly = (size_t)W * n;
   {   // every rotation reads c0 / c1 again after earlier rotations wrote their outputs: no overlap anywhere among the four ranges
     const size_t in_words = (size_t)batch * bigpoly, out_words = (size_t)nrot * in_words;
-    auto overlap = [](const uint64_t *a, size_t na, const uint64_t *b, size_t nb) { return a < b + nb && b < a + na; };
-    if (overlap(out_c0, out_words, out_c1, out_words) || overlap(out_c0, out_words, c0, in_words) || overlap(out_c0, out_words, c1, in_words) ||
-        overlap(out_c1, out_words, c0, in_words) || overlap(out_c1, out_words, c1, in_words))
+    if (ranges_overlap(out_c0, out_words, out_c1, out_words) || ranges_overlap(out_c0, out_words, c0, in_words) || ranges_overlap(out_c0, out_words, c1, in_words) ||
+        ranges_overlap(out_c1, out_words, c0, in_words) || ranges_overlap(out_c1, out_words, c1, in_words))
       return gpq_fail(GPQ_ERR_INVALID, "gpq_he_rot_hoisted: the outputs alias each other or an input");
   }
-  const unsigned m = batch < c->set.chunk ? batch : c->set.chunk;
+  const unsigned m = gpq_group_size(c, batch);
   HoistPlan hp;
   if ((rc = hoist_plan(c, W, dimB, dimP, nrot, m, &hp))) return rc;
   char *w = (char *)workspace;
@@ -481,6 +480,24 @@ void gemv_plan(gpq_ctx *c, unsigned W, unsigned slots, unsigned dimB, unsigned d
   g->ws = align64(ws > wm ? ws : wm);
   g->total = g->r + g->mpt + g->p + g->g + g->ws;
 }
+
+// The two steps every he_gemv call shares, plan or no plan (gemv_plan.hpp's driver calls them per launch group and per plan).
+// One giant step's centred sum P joins the output (:80-84): he_rot by `shift` straight into out the first time, into G and a wrapping sum afterwards.
+int gemv_add_giant(gpq_ctx *c, uint64_t *out_c0, uint64_t *out_c1, const uint64_t *P0, const uint64_t *P1, uint64_t *G0, uint64_t *G1, bool first,
+                   unsigned shift, const uint64_t *const *rk0, const uint64_t *const *rk1, unsigned W, unsigned logql, unsigned dimB, unsigned dimP,
+                   unsigned batch, void *ws, void *stream) {
+  int rc;
+  if ((rc = gpq_he_rot_hoisted(c, first ? out_c0 : G0, first ? out_c1 : G1, P0, P1, &shift, rk0 + shift, rk1 + shift, 1, W, logql, dimB, dimP, batch, ws, stream))) return rc;
+  if (first) return GPQ_OK;
+  if ((rc = gpq_big_addsub(c, out_c0, out_c0, G0, W, batch, 0, stream))) return rc;
+  return gpq_big_addsub(c, out_c1, out_c1, G1, W, batch, 0, stream);
+}
+// The sum of the giant steps leaves the call: centred (the adds' mpi_smod), then he_rs by Delta (:87, src/he-rescale.c:33-54).
+int gemv_close(gpq_ctx *c, uint64_t *out_c0, uint64_t *out_c1, unsigned W, unsigned logDelta, unsigned logql, unsigned batch, void *stream) {
+  int rc = gpq_he_rs(c, out_c0, out_c1, W, 0, logql, batch, stream);
+  if (rc || !logDelta) return rc;
+  return gpq_he_rs(c, out_c0, out_c1, W, logDelta, logql - logDelta, batch, stream);
+}
 }  // namespace
 
 extern "C" size_t gpq_he_gemv_workspace_bytes(gpq_ctx *c, unsigned W, unsigned slots, unsigned dimB, unsigned dimP, unsigned dimpt, unsigned batch) {
@@ -523,12 +540,9 @@ extern "C" int gpq_he_gemv(gpq_ctx *c, uint64_t *out_c0, uint64_t *out_c1, const
     if ((rc = gpq_he_rs(c, P0, P1, W, 0, logql, batch, stream))) return rc;                                            // centred: he_rot decomposes it
     const unsigned shift = i * n1;
     if (!rk0[shift] || !rk1[shift]) return gpq_fail(GPQ_ERR_INVALID, "gpq_he_gemv: key %u is NULL", shift);
-    uint64_t *g0 = i ? G0 : out_c0, *g1 = i ? G1 : out_c1;                                                              // :80-84
-    if ((rc = gpq_he_rot_hoisted(c, g0, g1, P0, P1, &shift, rk0 + shift, rk1 + shift, 1, W, logql, dimB, dimP, batch, ws, stream))) return rc;
-    if (i && ((rc = gpq_big_addsub(c, out_c0, out_c0, G0, W, batch, 0, stream)) || (rc = gpq_big_addsub(c, out_c1, out_c1, G1, W, batch, 0, stream)))) return rc;
+    if ((rc = gemv_add_giant(c, out_c0, out_c1, P0, P1, G0, G1, i == 0, shift, rk0, rk1, W, logql, dimB, dimP, batch, ws, stream))) return rc;
   }
-  if ((rc = gpq_he_rs(c, out_c0, out_c1, W, 0, logql, batch, stream))) return rc;                                      // the adds' mpi_smod
-  if (logDelta && (rc = gpq_he_rs(c, out_c0, out_c1, W, logDelta, logql - logDelta, batch, stream))) return rc;         // :87, src/he-rescale.c:33-54
+  if ((rc = gemv_close(c, out_c0, out_c1, W, logDelta, logql, batch, stream))) return rc;
   return launched("gpq_he_gemv");
 }
 
@@ -770,8 +784,7 @@ extern "C" int gpq_he_dec(gpq_ctx *c, uint64_t *m, const uint64_t *c0, const uin
   if (!m || !c0 || !c1 || !sk_ntt || !workspace || !logql) return gpq_fail(GPQ_ERR_INVALID, "gpq_he_dec: bad arguments (q_l must be 2^logql, logql > 0)");
   if (W < 1 || 64ull * W <= logql) return gpq_fail(GPQ_ERR_INVALID, "gpq_he_dec: %u words cannot hold a centred coefficient mod 2^%u (64 W > logql)", W, logql);
   const size_t big = (size_t)batch * W * c->n, key = (size_t)dim << c->logn;
-  auto overlap = [](const uint64_t *a, size_t na, const uint64_t *b, size_t nb) { return a < b + nb && b < a + na; };
-  if (overlap(m, big, c0, big) || overlap(m, big, c1, big) || overlap(m, big, sk_ntt, key))
+  if (ranges_overlap(m, big, c0, big) || ranges_overlap(m, big, c1, big) || ranges_overlap(m, big, sk_ntt, key))
     return gpq_fail(GPQ_ERR_INVALID, "gpq_he_dec: the output aliases an input");
   StageRange stage("gpq_he_dec");
   uint64_t *x = (uint64_t *)workspace;

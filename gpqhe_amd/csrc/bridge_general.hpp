@@ -129,7 +129,7 @@ int relin_tail_general(gpq_ctx *c, uint64_t *out, const uint64_t *chat, const ui
 }  // namespace
 
 extern "C" size_t gpq_he_general_workspace_bytes(gpq_ctx *c, unsigned W, unsigned dimA, unsigned dimB, unsigned dimP, unsigned batch) {
-  const unsigned m = batch < c->set.chunk ? batch : c->set.chunk;
+  const unsigned m = gpq_group_size(c, batch);
   GenPlan gp;
   gpq_bridge_basis *bA;
   if (gen_plan(c, W, dimP, dimB, m, &gp) != GPQ_OK || get_basis(c, 0, dimA ? dimA : 1, &bA) != GPQ_OK) return 0;
@@ -181,7 +181,7 @@ extern "C" int gpq_he_mul_general(gpq_ctx *c, uint64_t *out_c0, uint64_t *out_c1
   if (int rcm = check_modulus(ql_words, Lq, W)) return rcm;
   hipStream_t s = (hipStream_t)stream;
   const size_t n = c->n, bigpoly = (size_t)W * n;
-  const unsigned m = batch < c->set.chunk ? batch : c->set.chunk;
+  const unsigned m = gpq_group_size(c, batch);
   GenPlan gp;
   gpq_bridge_basis *bA;
   if ((rc = gen_plan(c, W, dimP, dimB, m, &gp)) || (rc = get_basis(c, 0, dimA, &bA))) return rc;
@@ -229,7 +229,7 @@ extern "C" int gpq_he_swk_general(gpq_ctx *c, uint64_t *out_c0, uint64_t *out_c1
   if (int rcm = check_modulus(ql_words, Lq, W)) return rcm;
   hipStream_t s = (hipStream_t)stream;
   const size_t n = c->n, bigpoly = (size_t)W * n;
-  const unsigned m = batch < c->set.chunk ? batch : c->set.chunk;
+  const unsigned m = gpq_group_size(c, batch);
   char *w = (char *)workspace;
   uint64_t *sB = (uint64_t *)w; w += align64((size_t)m * 3 * dimB * n * 8);
   void *wsK = w; w += align64(gpq_keyswitch_workspace_bytes(c, dimB, m));

@@ -275,6 +275,8 @@ int check(const gpq_ctx *c, unsigned dim, unsigned batch, const char *who) {
     return gpq_fail(GPQ_ERR_INVALID, "%s: the context lives on device %d but the calling thread's current device is %d (gpq_set_device(gpq_ctx_device(ctx)) first)", who, c->device, dev);
   return GPQ_OK;
 }
+// [a, a + na) and [b, b + nb) share a word
+bool ranges_overlap(const uint64_t *a, size_t na, const uint64_t *b, size_t nb) { return a < b + nb && b < a + na; }
 int launched(const char *who) {
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? GPQ_OK : gpq_fail(GPQ_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(e));

@@ -1,12 +1,14 @@
 // gemv_multi.hpp -- he_gemv for SEVERAL fixed matrices on the same ciphertexts (include/gpqhe_hip.h, "he_gemv for several matrices"): the plan
-// set and the call.  Part of bridge.hip's translation unit, after gemv_plan.hpp (it uses that file's plan_usable, ranges_overlap and
-// inner_finish); the kernel is gemv_mac_multi in ntt_kernels.hpp, launched by engine.hip's gpq_gemv_mac_multi.
+// set and the call.  Part of bridge.hip's translation unit, after gemv_plan.hpp (it uses that file's plan_usable and its driver gemv_call);
+// the kernel is gemv_mac_multi in ntt_kernels.hpp, launched by engine.hip's gpq_gemv_mac_multi.
 //
 // What the plans of a set share depends only on the ciphertext: the hoisted baby rotations, their rns_decompose + forward transform, and
-// the reads of those transforms inside every giant step.  All of it runs once, over the union of the plans' live baby rotations and the
-// largest `dim`; everything behind the inner sums (inverse transform, reconstruction, giant rotation, wrapping sum, he_rs) runs per plan
-// exactly as gpq_he_gemv_planned runs it.  Nothing new to prove: a residue of a rotation does not depend on how many limbs lie next to it,
-// and the sums leave gemv_mac_multi as canonical residues of the same terms, so output t is gpq_he_gemv_planned's for plans[t] word for word.
+// the reads of those transforms inside every giant step.  gemv_call runs the first two once, over the union of the plans' live baby
+// rotations and the largest `dim`, and everything behind the inner sums (inverse transform, reconstruction, giant rotation, wrapping sum,
+// he_rs) per plan: the code gpq_he_gemv_planned runs, not a copy of it.  This file adds the third: one gemv_mac_multi launch per giant step
+// and group of NP plans, where the planned call launches gemv_mac.  So only the inner sums have anything to prove, and it is little: a
+// residue of a rotation does not depend on how many limbs lie next to it, and the sums leave gemv_mac_multi as canonical residues of the
+// same terms, so output t is gpq_he_gemv_planned's for plans[t] word for word.
 #pragma once
 
 struct gpq_gemv_multi {
@@ -22,21 +24,6 @@ struct gpq_gemv_multi {
 
 namespace {
 constexpr unsigned kGemvMultiMax = 16, kGemvMultiNP = GPQ_GEMV_MULTI_NP;
-
-struct MultiLayout { size_t rb, hat, acc, p, g, ws, total; };
-int multi_layout(gpq_ctx *c, const gpq_gemv_multi *ms, unsigned W, unsigned dimB, unsigned dimP, unsigned m, MultiLayout *l) {
-  const size_t nb = ms->baby.size(), big = (size_t)m * W * c->n * 8, slab = (size_t)m * ms->dim * c->n * 8;
-  l->rb = 2 * align64(nb * big);                       // the union's baby rotations, c0 | c1
-  l->hat = align64(2 * nb * slab);                     // ... decomposed and transformed over the largest dim
-  l->acc = kGemvMultiNP * align64(2 * slab);           // one giant step's sums of one plan group
-  l->p = 2 * align64(big);                             // ... of one plan, as words
-  l->g = 2 * align64(big);                             // one giant rotation
-  const size_t wn = nb ? gpq_he_rot_hoisted_workspace_bytes(c, W, dimB, dimP, (unsigned)nb, m) : 0, w1 = gpq_he_rot_hoisted_workspace_bytes(c, W, dimB, dimP, 1, m);
-  if ((nb && !wn) || !w1) return GPQ_ERR_INVALID;      // (the rotation plan's message is in gpq_last_error)
-  l->ws = align64(wn > w1 ? wn : w1);
-  l->total = l->rb + l->hat + l->acc + l->p + l->g + l->ws;
-  return GPQ_OK;
-}
 }  // namespace
 
 extern "C" unsigned gpq_gemv_multi_width(void) { return kGemvMultiNP; }
@@ -127,8 +114,7 @@ extern "C" int gpq_gemv_multi_create(gpq_ctx *c, gpq_gemv_multi **out, const gpq
 
 extern "C" size_t gpq_he_gemv_multi_workspace_bytes(gpq_ctx *c, const gpq_gemv_multi *ms, unsigned W, unsigned dimB, unsigned dimP, unsigned batch) {
   if (!c || !ms || !batch || !W) return 0;
-  MultiLayout l;
-  return multi_layout(c, ms, W, dimB, dimP, batch < c->set.chunk ? batch : c->set.chunk, &l) == GPQ_OK ? l.total : 0;
+  return gemv_call_workspace_bytes(c, ms->baby.size(), ms->dim, kGemvMultiNP, W, dimB, dimP, batch);
 }
 
 extern "C" int gpq_he_gemv_multi(gpq_ctx *c, uint64_t *const *out_c0, uint64_t *const *out_c1, const uint64_t *c0, const uint64_t *c1,
@@ -138,89 +124,17 @@ extern "C" int gpq_he_gemv_multi(gpq_ctx *c, uint64_t *const *out_c0, uint64_t *
   if (rc) return rc;
   if (!ms) return gpq_fail(GPQ_ERR_INVALID, "gpq_he_gemv_multi: null set");
   if (ms->ctx != c) return gpq_fail(GPQ_ERR_INVALID, "gpq_he_gemv_multi: the set belongs to another context");
-  const unsigned logql = ms->logql, n1 = ms->n1, count = ms->count;
-  if (!out_c0 || !out_c1 || !c0 || !c1 || !rk0 || !rk1 || !workspace || logDelta >= logql || W < (logql + 63) / 64 || W > 32)
-    return gpq_fail(GPQ_ERR_INVALID, "gpq_he_gemv_multi: bad arguments (W words must hold q = 2^%u, Delta below q)", logql);
-  const size_t n = c->n, bigpoly = (size_t)W * n, words = batch * bigpoly;
-  std::vector<const uint64_t *> slabs{c0, c1};                            // the inputs, then every output: no two may overlap
-  for (unsigned t = 0; t < count; ++t) {
-    if (!out_c0[t] || !out_c1[t]) return gpq_fail(GPQ_ERR_INVALID, "gpq_he_gemv_multi: output %u is NULL", t);
-    slabs.push_back(out_c0[t]); slabs.push_back(out_c1[t]);
-  }
-  for (size_t a = 2; a < slabs.size(); ++a)
-    for (size_t b = 0; b < a; ++b)
-      if (ranges_overlap(slabs[a], words, slabs[b], words))
-        return gpq_fail(GPQ_ERR_INVALID, "gpq_he_gemv_multi: the outputs alias each other or an input");
-  const unsigned nb = (unsigned)ms->baby.size();
-  std::vector<const uint64_t *> bk0(nb), bk1(nb);
-  for (unsigned r = 0; r < nb; ++r) {
-    bk0[r] = rk0[ms->baby[r]]; bk1[r] = rk1[ms->baby[r]];
-    if (!bk0[r] || !bk1[r]) return gpq_fail(GPQ_ERR_INVALID, "gpq_he_gemv_multi: key %u is NULL (a live baby rotation of the set)", ms->baby[r]);
-  }
-  for (const gpq_gemv_plan *p : ms->plans)
-    for (unsigned i = 0; i < p->n2; ++i)
-      if (p->nterms[i] && (!rk0[i * n1] || !rk1[i * n1])) return gpq_fail(GPQ_ERR_INVALID, "gpq_he_gemv_multi: key %u is NULL (a live giant rotation of the set)", i * n1);
-  hipStream_t s = (hipStream_t)stream;
-  const unsigned m = batch < c->set.chunk ? batch : c->set.chunk;
-  MultiLayout l;
-  if (multi_layout(c, ms, W, dimB, dimP, m, &l)) return gpq_fail(GPQ_ERR_INVALID, "gpq_he_gemv_multi: unsupported shape");
-  char *w = (char *)workspace;
-  uint64_t *RB0 = (uint64_t *)w, *RB1 = (uint64_t *)(w + l.rb / 2); w += l.rb;
-  uint64_t *hat = (uint64_t *)w; w += l.hat;
-  char *acc = w; w += l.acc;
-  uint64_t *P0 = (uint64_t *)w, *P1 = (uint64_t *)(w + l.p / 2); w += l.p;
-  uint64_t *G0 = (uint64_t *)w, *G1 = (uint64_t *)(w + l.g / 2); w += l.g;
-  void *ws = w;
-  const unsigned stride = 1 + kGemvMultiNP;
-  std::vector<unsigned char> first(count);
-  for (unsigned k0 = 0; k0 < batch; k0 += m) {
-    const unsigned polys = batch - k0 < m ? batch - k0 : m;
-    const size_t o = k0 * bigpoly, rslab = (size_t)polys * ms->dim * n;
-    for (unsigned t = 0; t < count; ++t)
-      if (ms->plans[t]->baby.empty()) {                                    // the zero matrix
-        HIP_TRY(hipMemsetAsync(out_c0[t] + o, 0, polys * bigpoly * 8, s));
-        HIP_TRY(hipMemsetAsync(out_c1[t] + o, 0, polys * bigpoly * 8, s));
-      }
-    if (!nb) continue;
-    uint64_t *hat0 = hat, *hat1 = hat + nb * rslab;
-    if ((rc = gpq_he_rot_hoisted(c, RB0, RB1, c0 + o, c1 + o, ms->baby.data(), bk0.data(), bk1.data(), nb, W, logql, dimB, dimP, polys, ws, stream))) return rc;   // src/he-algo.c:63-68
-    {
-      StageRange stage("gpq_he_gemv_multi: rns_decompose + forward transform of the baby rotations (once per group, for every plan)");
-      if ((rc = launch_decompose(c, hat0, RB0, W, 0, ms->dim, nb * polys, s))) return rc;
-      if ((rc = launch_decompose(c, hat1, RB1, W, 0, ms->dim, nb * polys, s))) return rc;
-      if ((rc = gpq_hoist_forward(c, hat, ms->dim, 2 * nb * polys, s))) return rc;
+  // one gemv_mac_multi launch for the NP plans from `first` on: the set's entries of (giant step, plan group), written for exactly these plans
+  auto inner_sums = [&](unsigned i, unsigned first, unsigned polys, const uint64_t *hat0, const uint64_t *hat1, uint64_t *const *acc) {
+    gpq_gemv_multi_arg arg[kGemvMultiNP];
+    for (unsigned t = 0; t < kGemvMultiNP; ++t) {
+      const gpq_gemv_plan *p = acc[t] ? ms->plans[first + t] : nullptr;
+      if (p) arg[t] = {p->d_hat, acc[t], acc[t] + (size_t)polys * p->dim * c->n, p->dim};
+      else arg[t] = {nullptr, nullptr, nullptr, 0};
     }
-    std::fill(first.begin(), first.end(), 1);
-    for (unsigned i = 0; i < ms->n2; ++i)
-      for (unsigned g = 0; g < ms->groups; ++g) {
-        const size_t at = (size_t)i * ms->groups + g;
-        if (!ms->nentries[at]) continue;                                   // no plan of the group has a live diagonal in this step
-        StageRange stage("gpq_he_gemv_multi: one giant step of one plan group (inner sums, then per plan the rotation)");
-        gpq_gemv_multi_arg arg[kGemvMultiNP];
-        for (unsigned t = 0; t < kGemvMultiNP; ++t) {
-          const unsigned pl = g * kGemvMultiNP + t;
-          const gpq_gemv_plan *p = pl < count ? ms->plans[pl] : nullptr;
-          uint64_t *a0 = (uint64_t *)(acc + t * (l.acc / kGemvMultiNP));
-          if (p && p->nterms[i]) arg[t] = {p->d_hat, a0, a0 + (size_t)polys * p->dim * n, p->dim};
-          else arg[t] = {nullptr, nullptr, nullptr, 0};
-        }
-        if ((rc = gpq_gemv_mac_multi(c, arg, hat0, hat1, ms->d_entries + (size_t)ms->first[at] * stride, ms->nentries[at], ms->dim, polys, s))) return rc;   // :70-78
-        for (unsigned t = 0; t < kGemvMultiNP; ++t) {
-          if (!arg[t].dim) continue;
-          const unsigned pl = g * kGemvMultiNP + t;
-          uint64_t *o0 = out_c0[pl] + o, *o1 = out_c1[pl] + o;
-          if ((rc = inner_finish(c, ms->plans[pl], P0, P1, arg[t].acc0, W, polys, stream))) return rc;
-          const unsigned shift = i * n1;
-          uint64_t *g0 = first[pl] ? o0 : G0, *g1 = first[pl] ? o1 : G1;                                                   // :80-84
-          if ((rc = gpq_he_rot_hoisted(c, g0, g1, P0, P1, &shift, rk0 + shift, rk1 + shift, 1, W, logql, dimB, dimP, polys, ws, stream))) return rc;
-          if (!first[pl] && ((rc = gpq_big_addsub(c, o0, o0, G0, W, polys, 0, stream)) || (rc = gpq_big_addsub(c, o1, o1, G1, W, polys, 0, stream)))) return rc;
-          first[pl] = 0;
-        }
-      }
-  }
-  for (unsigned t = 0; t < count; ++t) {
-    if ((rc = gpq_he_rs(c, out_c0[t], out_c1[t], W, 0, logql, batch, stream))) return rc;                                // the adds' mpi_smod
-    if (logDelta && (rc = gpq_he_rs(c, out_c0[t], out_c1[t], W, logDelta, logql - logDelta, batch, stream))) return rc;   // :87, src/he-rescale.c:33-54
-  }
-  return launched("gpq_he_gemv_multi");
+    const size_t at = (size_t)i * ms->groups + first / kGemvMultiNP;
+    return gpq_gemv_mac_multi(c, arg, hat0, hat1, ms->d_entries + (size_t)ms->first[at] * (1 + kGemvMultiNP), ms->nentries[at], ms->dim, polys, (hipStream_t)stream);
+  };
+  return gemv_call(c, GemvCall{"gpq_he_gemv_multi", ms->plans.data(), ms->count, &ms->baby, ms->dim, kGemvMultiNP}, inner_sums, out_c0, out_c1, c0, c1, rk0, rk1,
+                   W, logDelta, dimB, dimP, batch, workspace, stream);
 }

@@ -121,6 +121,30 @@ def test_different_live_sets_in_one_set(engine_ctx):
         _close(plans)
 
 
+def test_a_set_of_zero_matrices(engine_ctx):
+    """no plan has a live diagonal: the union of the baby rotations is empty, nothing is rotated or summed, every output is the planned call's"""
+    slots, k = 4, NP + 1
+    sh = MultiShape(engine_ctx, 10, 120, slots, 3)
+    c0, c1 = sh.ciphertexts()
+    plans = _plans(sh, k, zero=range(slots))
+    try:
+        assert all(p.exact and p.live == 0 for p in plans)
+        expect = [sh.planned(p, c0, c1) for p in plans]
+        try:
+            sh.g.set_chunk(2)                                # two launch groups, the last one odd
+            with sh.g.gemv_multi(plans) as ms:
+                assert ms.count == k and ms.baby == 0 and not any(ms.rotations())
+                got = []
+                cnt = counts(sh.g, lambda: got.append(sh.multi(ms, c0, c1, only=set())))
+                for t in range(k):
+                    same((got[0][0][t], got[0][1][t]), expect[t], "plan %d of %d" % (t, k))
+        finally:
+            sh.g.set_chunk(32)
+        assert cnt.get("gemv_mac_multi", 0) == 0 and cnt.get("keyswitch_rot_mid", 0) == 0, cnt
+    finally:
+        _close(plans)
+
+
 def test_different_dims_in_one_set(engine_ctx):
     """logn 10, q = 2^135, slots 64: eight 30-bit products need a fourth limb (tests/test_gemv_inner_gpu.py), 8-bit ones fit he_mulpt's three"""
     sh = MultiShape(engine_ctx, 10, 135, 64, 2, limbs=5)

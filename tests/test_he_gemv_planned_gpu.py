@@ -207,6 +207,23 @@ def test_zero_giant_steps_are_skipped(engine_ctx):
     assert cnt["gemv_mac"] == 2, cnt
 
 
+def test_zero_matrix_needs_no_key(engine_ctx):
+    """every diagonal zero: no rotation at all, the outputs are overwritten with what gpq_he_gemv computes from the same zero diagonals"""
+    slots = 4
+    sh = Shape(engine_ctx, 10, 120, slots, 3, zero_diags=range(slots))
+    c0, c1 = sh.ciphertexts()
+    expect = sh.baseline(c0, c1)
+    out0, out1 = torch.full_like(c0, 0x5A5A5A5A5A5A5A5A), torch.full_like(c1, -3)
+    try:
+        sh.g.set_chunk(2)                                    # two launch groups, the last one odd
+        with sh.plan() as plan:
+            assert plan.exact and plan.live == 0 and not any(plan.rotations())
+            sh.g.he_gemv_planned(out0, out1, c0, c1, plan, [None] * slots, [None] * slots, sh.W, LOGDELTA, sh.dimB, sh.dimP)
+            _same((out0, out1), expect)
+    finally:
+        sh.g.set_chunk(32)
+
+
 def test_launch_counts_of_the_product_stage(engine_ctx):
     logn, logq, slots, batch = 14, 438, 16, 2
     sh = Shape(engine_ctx, logn, logq, slots, batch)

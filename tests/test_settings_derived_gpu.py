@@ -1,7 +1,7 @@
 """The key-switching calls built on gpq_he_swk's pieces -- gpq_he_rot_hoisted, gpq_he_gemv, gpq_he_gemv_planned, gpq_gemv_inner,
 gpq_he_gemv_multi -- under every switch of tests/bridge_settings.py.  They choose the key switch's tables and the tail's route themselves
 (gpq_he_rot_hoisted: tail_prescale_mode, gpq_keyswitch_rotated, relin_tail with a rotated addend; nrot == 1: gpq_poly_rot + gpq_he_swk) and
-carve nested workspaces (planned_layout holds gpq_he_rot_hoisted_workspace_bytes), so a switch could reach them wrongly while
+carve nested workspaces (gemv_call_layout holds gpq_he_rot_hoisted_workspace_bytes), so a switch could reach them wrongly while
 gpq_he_mul / gpq_he_swk, which the other settings tests run, stay right.
 
 Three shapes, each the smallest that reaches a distinct route (dims = he_dims(logq, logq)):
