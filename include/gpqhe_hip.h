@@ -130,6 +130,39 @@ int gpq_device_local_cpus(int device, const char *sysfs_root, char *cpulist, siz
  * device, may call concurrently: the only state they share is the once-per-(kernel, device) LDS attribute flags, which are atomic.
  */
 
+/* ---- stream classes: what `void *stream` promises, function by function -------------------------------------------------------
+ * Every function below that takes a stream queues ALL its device work -- kernels, memsets, copies, the fork and join of a peer lane --
+ * on that stream: nothing goes to the null stream, which a non-blocking stream (gpq_stream_create's, torch's side streams) does not
+ * wait for.  Tables a call builds at first use are uploaded by host-synchronous copies BEFORE its first launch.  Beyond that there are
+ * four classes; tests/stream_contract.py holds the same table, tests/test_stream_contract_cover.py fails when a prototype with a
+ * `void *stream` is in none, and tests/test_stream_contract_gpu.py runs every call behind a delayed producer on a non-blocking side
+ * stream and, where the class allows it, inside a captured and replayed graph.
+ * CAPTURABLE: after ONE warm call of the same shape on the same context (first-use tables, scratch that grows with the batch, the
+ *   dynamic-LDS attribute of a kernel, the peer lane) the call makes no host synchronisation, no allocation and no host read-back, so
+ *   it may be captured into a graph and replayed; host arguments (rotation amounts, Galois elements, key pointer arrays, a seed, a
+ *   stream position) are read before the call returns and are part of the captured launches:
+ *     gpq_ntt gpq_invntt gpq_ntt_reference gpq_rns_mul gpq_rns_add gpq_poly_mul_rns gpq_mulpt_rns gpq_he_mul_tensor gpq_keyswitch
+ *     gpq_rns_decompose gpq_rns_decompose_limbs gpq_rns_reconstruct gpq_poly_mul gpq_he_rs gpq_he_rescale gpq_he_mul gpq_he_mul_rs
+ *     gpq_relin_tail gpq_relin_tail_overwriting gpq_big_transpose gpq_big_addsub gpq_big_add gpq_big_sub gpq_big_neg gpq_he_swk
+ *     gpq_he_mulpt gpq_poly_rot gpq_poly_conj gpq_he_mulpt_const gpq_he_addpt_const gpq_he_rot_hoisted gpq_he_gemv gpq_gemv_inner
+ *     gpq_he_gemv_planned gpq_he_gemv_multi gpq_he_ecd gpq_he_ecd_diagonals gpq_he_dcd gpq_he_dec gpq_sample_zo gpq_sample_error
+ *     gpq_sample_uniform gpq_small_to_big gpq_he_enc_pk gpq_he_enc_sk gpq_surf_bytes gpq_rng_device_bytes gpq_evk_pack
+ *     gpq_he_genswk_batch
+ * ORDERED: the device work is ordered on `stream` as above, but every call may wait for `stream` on the host or allocate, so it is for
+ *   eager use on any stream and never for a capture.  The general-modulus calls wait once per Barrett reduction (its constants are
+ *   copied from a host buffer of the call), the plan constructors allocate the plan, read their measurement back and refuse a
+ *   capturing stream with the error code for a bad argument:
+ *     gpq_rns_reconstruct_general gpq_poly_mul_general gpq_he_rs_general gpq_relin_tail_general gpq_he_mul_general
+ *     gpq_he_mulpt_general gpq_he_swk_general gpq_he_genswk gpq_gemv_plan_create gpq_gemv_plan_create_from_matrix
+ * REFUSES_IN_CAPTURE: allocates and fills its tables by host-synchronous copies and queues nothing on `stream`, which it takes only
+ *   to refuse a capturing one, before anything is allocated:
+ *     gpq_gemv_multi_create
+ * NOT_A_LAUNCH: a plain runtime operation on the stream, no kernel of a context and no scratch -- hipMemcpyAsync (gpq_upload,
+ *   gpq_download, gpq_copy), hipStreamSynchronize (gpq_stream_sync), an event recorded on one stream and awaited by the other
+ *   (gpq_stream_wait), hipStreamDestroy (gpq_stream_destroy), hipEventRecord (gpq_timer_start, gpq_timer_stop), and the copy-rate
+ *   yardstick's one copy kernel (gpq_probe_stream).
+ */
+
 /* ntt / invntt over every limb of every polynomial, in place.
  * Replaces the per-limb calls `ntt(a, rns)` / `invntt(a, rns)`, src/ntt.c:37,54.
  * Inputs are canonical residues in [0, p_d) (what rns_decompose and poly_rns_mul produce); gpq_invntt also takes the word p_d for a
