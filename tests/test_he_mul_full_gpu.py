@@ -8,6 +8,7 @@ import pytest
 
 from gpqhe_amd import big_to_ints, ints_to_big, to_device, to_host
 from oracle import bigint_ref as ref
+from tests.sparse_ints import sparse_mul as _sparse_mul
 
 pytestmark = pytest.mark.gpu
 
@@ -377,18 +378,6 @@ def test_he_mul_is_graph_capturable_after_the_first_call(engine_ctx):
     graph.replay()
     torch.cuda.synchronize()
     assert torch.equal(r0, o0) and torch.equal(r1, o1)
-
-
-def _sparse_mul(dense, terms, n):
-    out = [0] * n
-    for k, c in terms:
-        for i, v in enumerate(dense):
-            j = i + k
-            if j < n:
-                out[j] += c * v
-            else:
-                out[j - n] -= c * v
-    return out
 
 
 @pytest.mark.parametrize("logn,logq", [(13, 438), (16, 850)])

@@ -3,7 +3,13 @@ against the oracle, word for word: every butterfly class, the smallest two-pass 
 every fused middle (tensor, squaring, key switch in its pair and single forms, poly_mul, he_mulpt) under both cache policies,
 and the inputs that sit on the edges of the lazy ranges -- all-zero, all p - 1, and polynomials whose transform holds
 residues 0 (a lazy value may now be 0 where it was p; canonical outputs, and the reference's stored p, must not move).
-The integer model of the same code is tests/test_inject_ranges.py."""
+The integer model of the same code is tests/test_inject_ranges.py.
+
+The matrix: a launch of a transform kernel is one instantiation out of ring (5, 6, 7, 8 strided stages at logn 13 .. 16, nine low stages
+at 17) x butterfly class x cache policy, and the range a strided pass hands to the middle depends on the class and on how many stages
+ran.  So every ring 13 .. 17 has a case with one limb range of each class inside one transform, ring 15 -- which nothing else runs --
+also every uniform arrangement, all under both policies.  gpq_set_limb_classes clamps silently: each case first proves from the
+per-kernel profile that the classes it asked for are the classes that ran.  tests/test_ring_class_cover.py pins the table."""
 import numpy as np
 import pytest
 
@@ -16,8 +22,26 @@ pytestmark = pytest.mark.gpu
 BATCH = 3      # odd: the key switch runs a pair of polynomials and then the single-polynomial instantiation
 # (logn, limbs, (wide, split)): logn 13 is the smallest two-pass ring, three limbs of each class inside one transform
 # (gpq_set_limb_classes as tests/test_ntt_gpu.py uses it: the first `wide` limbs wide-split, up to `split` split, the rest 7-mad);
-# logn 17 (nine low stages) with two limbs, both through each class in turn
-CASES = [(13, 9, (3, 6)), (17, 2, (2, 2)), (17, 2, (0, 2)), (17, 2, (0, 0))]
+# logn 17 (nine low stages) with two limbs, both through each class in turn; then the smallest all-class cell of the other rings and of
+# 17 -- three limbs, one of each class -- and at ring 15 the uniform arrangements on the same three limbs (one range of three limbs)
+CASES = [(13, 9, (3, 6)), (17, 2, (2, 2)), (17, 2, (0, 2)), (17, 2, (0, 0)),
+         (14, 3, (1, 2)), (15, 3, (1, 2)), (16, 3, (1, 2)), (17, 3, (1, 2)), (15, 3, (0, 0)), (15, 3, (0, 3)), (15, 3, (3, 3))]
+NT_POLICIES = [0, 1]
+
+
+def class_ranges(dim, classes):
+    """Limbs per class (wide-split, split, 7-mad) of a transform over limbs 0 .. dim - 1 under gpq_set_limb_classes(*classes), when nothing
+    is clamped.  engine.hip, for_limb_ranges: e_wide = min(nwide, dim), e_split = min(nsplit, dim), and one call of f -- one ProfScope and
+    one launch in launch_strided / launch_contig -- per non-empty range [0, e_wide), [e_wide, e_split), [e_split, dim)."""
+    wide, split = classes
+    e_split = min(split, dim)
+    e_wide = min(wide, e_split)
+    return e_wide, e_split - e_wide, dim - e_split
+
+
+def launches(dim, classes):
+    return sum(1 for limbs in class_ranges(dim, classes) if limbs)
+
 
 _SHARED = {}
 
@@ -51,7 +75,45 @@ def _inputs(o, logn, dim):
     return _SHARED[logn, dim]
 
 
-@pytest.mark.parametrize("nt", [0, 1])          # both cache-policy instantiations of every kernel (the expectations are cached per ring)
+def assert_the_asked_classes_ran(g, slab, dim, classes):
+    """One gpq_ntt and one gpq_invntt of one launch group under the profile: each pass records one launch per class present.
+    Three launches on three ranges can only be one of each class.  One launch of a uniform arrangement is the asked class only next to
+    the mixed case of the same ring: a wide range clamped to 0 (or split tables for 0 limbs) would also launch once, and then (1, 2) on
+    a context built the same way launches twice; any other clamp splits the uniform range in two."""
+    want = launches(dim, classes)
+    dev = to_device(slab)
+    try:
+        g.profile(True)
+        g.profile_collect()
+        g.poly_ntt(dev, dim)
+        fwd = g.profile_collect()
+        g.poly_invntt(dev, dim)
+        inv = g.profile_collect()
+    finally:
+        g.profile(False)                             # (gpq_set_overlap lanes are not taken while it is on)
+    cnt = lambda prof, k: prof.get(k, (0, 0))[1]
+    for prof, names in ((fwd, ("strided_fwd", "contig_fwd")), (inv, ("contig_inv", "strided_inv"))):
+        for name in names:
+            assert cnt(prof, name) == want, "%s: %d launches, classes %s on %d limbs are %d (limbs per class %s): gpq_set_limb_classes clamped" % (
+                name, cnt(prof, name), classes, dim, want, class_ranges(dim, classes))
+
+
+@pytest.mark.parametrize("ran", [(0, 2), (1, 1), (0, 0)])
+def test_a_context_that_runs_fewer_classes_than_asked_fails_the_proof(ran):
+    """What a clamp would leave -- the wide range ended at limb 0, split tables for one limb only, neither -- is told from (1, 2)."""
+    logn, dim = 13, 3
+    g = gpqhe_amd.PolyContext(logn, dim)
+    try:
+        g.set_limb_classes(*ran)
+        slab = np.zeros(BATCH * dim << logn, dtype=np.uint64)
+        assert_the_asked_classes_ran(g, slab, dim, ran)
+        with pytest.raises(AssertionError, match="clamped"):
+            assert_the_asked_classes_ran(g, slab, dim, (1, 2))
+    finally:
+        g.close()
+
+
+@pytest.mark.parametrize("nt", NT_POLICIES)     # both cache-policy instantiations of every kernel (the expectations are cached per ring)
 @pytest.mark.parametrize("logn,dim,classes", CASES)
 def test_injected_butterflies_match_the_oracle(oracle_ctx, logn, dim, classes, nt):
     import torch
@@ -62,6 +124,7 @@ def test_injected_butterflies_match_the_oracle(oracle_ctx, logn, dim, classes, n
         assert g.p == o.p
         g.set_limb_classes(*classes)
         g.set_nt_policy(nt)
+        assert_the_asked_classes_ran(g, mix, dim, classes)
         per = dim * o.n
         for i, v in enumerate((edge, mix)):          # gpq_ntt, gpq_invntt
             dev = to_device(v)
