@@ -27,6 +27,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <optional>
 #include <set>
 #include <thread>
 #include <vector>
@@ -57,6 +58,7 @@ extern "C" void he_ecd(struct he_pt *pt, const _Complex double *m) __attribute__
 #include "shim_staging.hpp"
 #include "shim_keys.hpp"
 #include "shim_polys.hpp"
+#include "shim_call.hpp"
 
 namespace {
 
@@ -143,45 +145,23 @@ void poly_mul(poly_mpi_t *r, const poly_mpi_t *a, const poly_mpi_t *b, const uns
   const unsigned nbq = G.mpi_get_nbits(q);
   const poly_mpi_t *in[2] = {a, b};
   poly_mpi_t *out[1] = {r};
-  const bool pow2 = is_pow2(qw), same = a->coeffs == b->coeffs;
+  const bool pow2 = is_pow2(qw);
+  const int count = a->coeffs == b->coeffs ? 1 : 2;
   // one pass at W words per coefficient; with `kept`, from the resident copies of both operands (false: one of them has outgrown its copy)
   auto pass = [&](unsigned W, bool kept) -> bool {
     if (W > 32) die("poly_mul: coefficients wider than 2047 bits");
-    const size_t big = (size_t)W * n;
-    HostBuf s0(big * 8), s1(big * 8), t0s(big * 8);
-    DevBuf da(big * 8), db(big * 8), dr(big * 8), ws(gpq_poly_mul_general_workspace_bytes(c, dim, 1));
-    const DevBuf *dd[2] = {&da, &db}, *oo[1] = {&dr};
-    const HostBuf *ss[2] = {&s0, &s1}, *ts[1] = {&t0s};
-    Operands ops(same ? 1 : 2, in, dd, ss, n, W);
-    ops.prepare(kept);
-    auto device_work = [&]() {
-      const uint64_t *xa = ops.x[0], *xb = same ? xa : ops.x[1];
-      const int rc = pow2 ? gpq_poly_mul(c, dr.u64(), xa, xb, W, dim, nbq - 1, 1, ws.p, nullptr)
-                          : gpq_poly_mul_general(c, dr.u64(), xa, xb, W, dim, qw.data(), (unsigned)qw.size(), 1, ws.p, nullptr);
+    DevBuf ws(gpq_poly_mul_general_workspace_bytes(c, dim, 1));
+    StagedCall call(n, W, count, in, 1);
+    call.speculate = kept; call.report_misfits = true;
+    return call.run([&](const uint64_t *const x[], uint64_t *const o[]) {
+      const uint64_t *xa = x[0], *xb = count == 1 ? xa : x[1];
+      const int rc = pow2 ? gpq_poly_mul(c, o[0], xa, xb, W, dim, nbq - 1, 1, ws.p, nullptr)
+                          : gpq_poly_mul_general(c, o[0], xa, xb, W, dim, qw.data(), (unsigned)qw.size(), 1, ws.p, nullptr);
       if (rc != GPQ_OK) die("poly_mul failed");   // q = P*q_L in he_genswk (src/he-kem.c:95) takes the general path
-      download_issue(ts, oo, 1, n, W);
-    };
-    device_work();
-    if (ops.resident && ops.recheck()) {
-      if (ops.misfits) { (void)gpq_stream_sync(nullptr); return false; }   // the copies queued into / out of this pass's page-locked buffers must land before the buffers go back to the pool
-      device_work();
-    }
-    std::vector<uint64_t> oprints((size_t)ops.nt, 0);
-    download_convert(out, ts, 1, n, W, oprints.data());
-    remember_results(out, oo, 1, n, W, oprints);
-    return true;
+    }, out) == StagedCall::Done;
   };
-  bool done = false;
-  if (poly_cache_on(n)) {                                   // he_dec multiplies a chained ciphertext's c1 with the same secret key every time
-    const PolySlot *ka = resident_poly(a, n, 0), *kb = resident_poly(b, n, 0);
-    if (ka && kb && ka->trusted && kb->trusted && ka->W == kb->W && ka->W >= nbq / 64 + 1) done = pass(ka->W, true);
-  }
-  if (!done) {
-    unsigned bits = max_bits(a, n), bb = max_bits(b, n);
-    if (bb > bits) bits = bb;
-    if (nbq > bits) bits = nbq;
-    pass(bits / 64 + 1, false);
-  }
+  // (he_dec multiplies a chained ciphertext's c1 with the same secret key every time)
+  width_ladder(in, count, n, true, nbq / 64 + 1, nbq, 0, pass);
 }
 
 #include "shim_decrypt.hpp"
@@ -190,8 +170,7 @@ void poly_mul(poly_mpi_t *r, const poly_mpi_t *a, const poly_mpi_t *b, const uns
 // src/he-mult.c:88-156
 void he_mul(he_ct_t *ct, const he_ct_t *ct1, const he_ct_t *ct2, const he_evk_t *rlk) {
   SHIM_CALL();
-  need_gcrypt();
-  if (&hectx == nullptr || !hectx.q) die("`hectx` is not initialised (hectx_init first)");
+  need_hectx();
   if (ct1->l != ct2->l) die("he_mul: operands at different levels");   // assert at src/he-mult.c:90
   gpq_ctx *c = engine();
   const unsigned n = polyctx.n, l = ct1->l;
@@ -208,51 +187,29 @@ void he_mul(he_ct_t *ct, const he_ct_t *ct1, const he_ct_t *ct2, const he_evk_t 
   const unsigned dimP = hectx.dim;                                                             // hectx.P, src/precomp.c:401-404
   if (gpq_ctx_pbits(c, dimP) != G.mpi_get_nbits(hectx.P)) die("he_mul: hectx.P is not the product of the first hectx.dim primes");
   const unsigned W = logql / 64 + 1;
-  const size_t big = (size_t)W * n;
   const poly_mpi_t *in[4] = {&ct1->c0, &ct1->c1, &ct2->c0, &ct2->c1};
-  HostBuf s0(big * 8), s1(big * 8), s2(big * 8), s3(big * 8), t0s(big * 8), t1s(big * 8);
-  DevBuf d0(big * 8), d1(big * 8), d2(big * 8), d3(big * 8), o0(big * 8), o1(big * 8),
-      ws(pow2 ? gpq_he_mul_workspace_bytes(c, W, dimA, dimB, dimP, 1) : gpq_he_general_workspace_bytes(c, W, dimA, dimB, dimP, 1));
-  const DevBuf *dd[4] = {&d0, &d1, &d2, &d3}, *oo[2] = {&o0, &o1};
-  const HostBuf *ss[4] = {&s0, &s1, &s2, &s3}, *ts[2] = {&t0s, &t1s};   // results come back into rows of their own: ss may still be filling (recheck)
+  poly_mpi_t *out[2] = {&ct->c0, &ct->c1};
+  DevBuf ws(pow2 ? gpq_he_mul_workspace_bytes(c, W, dimA, dimB, dimP, 1) : gpq_he_general_workspace_bytes(c, W, dimA, dimB, dimP, 1));
   // he_mul(&ct, &ct, &ct, rlk), src/he-algo.c:151: one ciphertext on both sides -- convert and upload it once, square on the device
   const bool square = ct1->c0.coeffs == ct2->c0.coeffs && ct1->c1.coeffs == ct2->c1.coeffs;
+  StagedCall call(n, W, square ? 2 : 4, in, 2);
   const double t0 = wall_ms();
-  KeyPrint kp(rlk, dimB, n);
-  KeySlot *spec = resident_key(kp);                  // a resident copy: used at once, verified while the device works
-  Operands ops(square ? 2 : 4, in, dd, ss, n, W);
-  if (spec) ops.prepare(true); else ops.prepare(false, kp.parts, &kp.task);
-  uint64_t *k0, *k1;
-  if (spec) { k0 = (uint64_t *)spec->d0; k1 = (uint64_t *)spec->d1; } else key_on_device(kp, &k0, &k1);
+  CallKey key(rlk, dimB, n);                         // operands and key are checked against the caller's memory while the device works
+  key.ride(call);
+  call.prepare();
+  key.settle();
   if (!g_tick[0]) { (void)hipEventCreate(&g_tick[0]); (void)hipEventCreate(&g_tick[1]); }
   (void)hipEventRecord(g_tick[0], nullptr);
   const double t1 = wall_ms();
-  auto device_work = [&]() {
-    const uint64_t *const a0 = ops.x[0], *const a1 = ops.x[1], *const e0 = square ? a0 : ops.x[2], *const e1 = square ? a1 : ops.x[3];
-    const int rc = pow2 ? gpq_he_mul(c, o0.u64(), o1.u64(), a0, a1, e0, e1, k0, k1, W, logql, dimA, dimB, dimP, 1, ws.p, nullptr)
-                        : gpq_he_mul_general(c, o0.u64(), o1.u64(), a0, a1, e0, e1, k0, k1, W, qw.data(),
+  call.run([&](const uint64_t *const x[], uint64_t *const o[]) {
+    const uint64_t *const a0 = x[0], *const a1 = x[1], *const e0 = square ? a0 : x[2], *const e1 = square ? a1 : x[3];
+    const int rc = pow2 ? gpq_he_mul(c, o[0], o[1], a0, a1, e0, e1, key.k0, key.k1, W, logql, dimA, dimB, dimP, 1, ws.p, nullptr)
+                        : gpq_he_mul_general(c, o[0], o[1], a0, a1, e0, e1, key.k0, key.k1, W, qw.data(),
                                              (unsigned)qw.size(), dimA, dimB, dimP, 1, ws.p, nullptr);
     if (rc != GPQ_OK) die("he_mul failed");
     (void)hipEventRecord(g_tick[1], nullptr);
-    download_issue(ts, oo, 2, n, W);
-  };
-  device_work();
-  const double t2 = wall_ms();
-  bool again = false;
-  if (ops.resident) {                                      // operands and key are checked against the caller's memory while the device works
-    again = ops.recheck(kp.parts, &kp.task);
-    if (ops.misfits) die("coefficient does not fit the big slab");
-    if (!kp.matches(*spec)) { key_on_device(kp, &k0, &k1); again = true; }
-  } else if (spec && !key_still_valid(spec, kp)) {         // edited in place since the upload: the reference reads its key on every call
-    key_on_device(kp, &k0, &k1);
-    again = true;
-  }
-  if (again) device_work();
-  poly_mpi_t *out[2] = {&ct->c0, &ct->c1};
-  std::vector<uint64_t> oprints((size_t)2 * ops.nt, 0);
-  download_convert(out, ts, 2, n, W, oprints.data());
-  remember_results(out, oo, 2, n, W, oprints);
-  const double t3 = wall_ms();
+  }, out);
+  const double t2 = call.queued_ms, t3 = wall_ms();
   float dev_ms = 0;
   (void)hipEventElapsedTime(&dev_ms, g_tick[0], g_tick[1]);
   g_last_ms[0] = t1 - t0; g_last_ms[1] = dev_ms; g_last_ms[2] = t3 - t2; g_last_ms[3] = t3 - t0;
@@ -261,8 +218,7 @@ void he_mul(he_ct_t *ct, const he_ct_t *ct1, const he_ct_t *ct2, const he_evk_t 
 
 static void rescale_common(he_ct_t *ct, bool divide) {
   SHIM_CALL();
-  need_gcrypt();
-  if (&hectx == nullptr || !hectx.q) die("`hectx` is not initialised (hectx_init first)");
+  need_hectx();
   gpq_ctx *c = engine();
   const unsigned n = polyctx.n;
   if (ct->l == 0) die("he_rs / he_moddown: already at level 0");
@@ -275,11 +231,8 @@ static void rescale_common(he_ct_t *ct, bool divide) {
   const unsigned s = divide ? G.mpi_get_nbits(hectx.p) - 1 : 0;
   const poly_mpi_t *in[2] = {&ct->c0, &ct->c1};
   poly_mpi_t *out[2] = {&ct->c0, &ct->c1};
-  if (logql == 0) {
-    // q_0 = 1 (logq a multiple of logDelta, e.g. 850 = 17 x 50): mpi_smod (src/types.c:108-113) takes r = x mod 1 = 0, finds 0 >= floor(1/2)
-    // and subtracts q -- every coefficient of the reference's result is -1, whatever the ciphertext was.  No device work in that.
-    for (int k = 0; k < 2; ++k)
-      for (unsigned i = 0; i < n; ++i) { G.mpi_set_ui(out[k]->coeffs[i], 1); G.mpi_neg(out[k]->coeffs[i], out[k]->coeffs[i]); }
+  if (logql == 0) {                                          // q_0 = 1
+    fill_minus_one(out[0], n); fill_minus_one(out[1], n);
     ct->l = lnew;
     if (divide) { ct->nu /= hectx.Delta; ct->B = ct->B / hectx.Delta + hectx.bnd.Brs; }
     return;
@@ -288,43 +241,18 @@ static void rescale_common(he_ct_t *ct, bool divide) {
   // One pass at W words per coefficient; with `kept`, from the resident copies of both polynomials (returns false if one of them
   // turned out wider than its copy: the caller measures the integers and runs again)
   auto pass = [&](unsigned W, bool kept) -> bool {
-    const size_t big = (size_t)W * n;
-    HostBuf s0(big * 8), s1(big * 8), t0s(big * 8), t1s(big * 8);
-    DevBuf d0(big * 8), d1(big * 8), scratch(192 * 8);
-    const DevBuf *dd[2] = {&d0, &d1};
-    const HostBuf *ss[2] = {&s0, &s1}, *ts[2] = {&t0s, &t1s};
-    Operands ops(2, in, dd, ss, n, W);
-    ops.prepare(kept);
-    const unsigned Wdown = Wout < W ? Wout : W;
-    auto device_work = [&]() {
+    DevBuf scratch(192 * 8);
+    StagedCall call(n, W, 2, in, 2, true);
+    call.speculate = kept; call.report_misfits = true; call.Wdown = Wout < W ? Wout : W;
+    return call.run([&](const uint64_t *const x[], uint64_t *const o[]) {
       for (int i = 0; i < 2; ++i)                            // gpq_he_rs works in place: a resident copy is copied, not lent
-        if (ops.x[i] != dd[i]->u64() && hipMemcpyAsync(dd[i]->p, ops.x[i], big * 8, hipMemcpyDeviceToDevice, nullptr) != hipSuccess) die("device copy failed");
-      const int rc = pow2 ? gpq_he_rs(c, d0.u64(), d1.u64(), W, s, logql, 1, nullptr)                                  // :45-48 / :64-65
-                          : gpq_he_rs_general(c, d0.u64(), d1.u64(), W, divide ? dw[0] : 1ull, qw.data(), (unsigned)qw.size(), 1, scratch.p, nullptr);
+        if (x[i] != o[i] && hipMemcpyAsync(o[i], x[i], (size_t)W * n * 8, hipMemcpyDeviceToDevice, nullptr) != hipSuccess) die("device copy failed");
+      const int rc = pow2 ? gpq_he_rs(c, o[0], o[1], W, s, logql, 1, nullptr)                                          // :45-48 / :64-65
+                          : gpq_he_rs_general(c, o[0], o[1], W, divide ? dw[0] : 1ull, qw.data(), (unsigned)qw.size(), 1, scratch.p, nullptr);
       if (rc != GPQ_OK) die("he_rs failed");
-      download_issue(ts, dd, 2, n, Wdown);                   // the low Wdown words of every coefficient (word-major: the first rows)
-    };
-    device_work();
-    if (ops.resident && ops.recheck()) {
-      if (ops.misfits) { (void)gpq_stream_sync(nullptr); return false; }   // the copies queued into / out of this pass's page-locked buffers must land before the buffers go back to the pool
-      device_work();
-    }
-    std::vector<uint64_t> oprints((size_t)2 * ops.nt, 0);
-    download_convert(out, ts, 2, n, Wdown, oprints.data());
-    remember_results(out, dd, 2, n, Wdown, oprints);
-    return true;
+    }, out) == StagedCall::Done;
   };
-  bool done = false;
-  if (poly_cache_on(n)) {
-    const PolySlot *k0 = resident_poly(in[0], n, 0), *k1 = resident_poly(in[1], n, 0);
-    if (k0 && k1 && k0->trusted && k1->trusted && k0->W == k1->W && k0->W >= Wout) done = pass(k0->W, true);
-  }
-  if (!done) {
-    unsigned bits = max_bits(&ct->c0, n), b1 = max_bits(&ct->c1, n);
-    if (b1 > bits) bits = b1;
-    if (logql + 1 > bits) bits = logql + 1;
-    pass(bits / 64 + 1, false);
-  }
+  width_ladder(in, 2, n, true, Wout, logql + 1, 0, pass);
   ct->l = lnew;
   if (divide) { ct->nu /= hectx.Delta; ct->B = ct->B / hectx.Delta + hectx.bnd.Brs; }             // :37-38
 }
@@ -373,7 +301,7 @@ static bool const_pt_candidate(const poly_mpi_t *m, unsigned n, int64_t *a, int6
   return true;
 }
 // The rest of the scan -- is every other coefficient zero? -- cut into the conversion threads' ranges; a range stops at the first non-zero
-// coefficient anyone found.  The tasks ride with the conversions of the call (Operands::prepare / recheck take them as `side` tasks): when
+// coefficient anyone found.  The tasks ride with the conversions of the call (StagedCall's `side` tasks): when
 // every operand is resident the device already works on the candidate's closed form while the host scans, as it does for the operands.
 struct ConstScan {
   const poly_mpi_t *m;
@@ -406,47 +334,30 @@ static int mulpt_const(gpq_ctx *c, struct he_ct *dest, const struct he_ct *src, 
   static hipEvent_t counted = nullptr;
   if (!counted && hipEventCreateWithFlags(&counted, hipEventDisableTiming) != hipSuccess) die("hipEventCreate failed");
   const unsigned W = (logql + 1) / 64 + 1;
-  const size_t big = (size_t)W * n;
-  HostBuf s0(big * 8), s1(big * 8), t0s(big * 8), t1s(big * 8), count(8);
-  DevBuf d0(big * 8), d1(big * 8), o0(big * 8), o1(big * 8), bad(8);
-  const DevBuf *dd[2] = {&d0, &d1}, *oo[2] = {&o0, &o1};
-  const HostBuf *ss[2] = {&s0, &s1}, *ts[2] = {&t0s, &t1s};
+  HostBuf count(8);
+  DevBuf bad(8);
   const poly_mpi_t *in[2] = {&src->c0, &src->c1};
-  ConstScan scan(&pt->m, n);
-  const bool later = all_operands_resident(in, 2, n, W);
-  Operands ops(2, in, dd, ss, n, W);
-  if (later) ops.prepare(true); else ops.prepare(true, scan.parts, &scan.job);
-  // (on the ways out before download_convert: the copies queued into / out of this call's page-locked buffers land before the buffers return to the pool)
-  if (scan.dense.load()) { (void)gpq_stream_sync(nullptr); return -1; }
-  auto device_work = [&]() {
-    if (hipMemsetAsync(bad.p, 0, 4, nullptr) != hipSuccess) die("device memset failed");
-    if (gpq_he_mulpt_const(c, o0.u64(), o1.u64(), ops.x[0], ops.x[1], ca, cb, W, logql, dim, 0, 1, (unsigned *)bad.p, nullptr) != GPQ_OK) die("he_mulpt failed");
-    if (hipMemcpyAsync(count.p, bad.p, 4, hipMemcpyDeviceToHost, nullptr) != hipSuccess || hipEventRecord(counted, nullptr) != hipSuccess) die("download failed");
-    download_issue(ts, oo, 2, n, W);
-  };
-  device_work();
-  if (ops.resident) {
-    const bool again = ops.recheck(later ? scan.parts : 0, later ? &scan.job : nullptr);
-    if (scan.dense.load()) { (void)gpq_stream_sync(nullptr); return -1; }
-    if (again) {
-      if (ops.misfits) die("coefficient does not fit the big slab");
-      device_work();
-    }
-  }
-  if (hipEventSynchronize(counted) != hipSuccess) die("download failed");
-  if (*(volatile unsigned *)count.p) { (void)gpq_stream_sync(nullptr); return 0; }
   poly_mpi_t *out[2] = {&dest->c0, &dest->c1};
-  std::vector<uint64_t> oprints((size_t)2 * ops.nt, 0);
-  download_convert(out, ts, 2, n, W, oprints.data());
-  remember_results(out, oo, 2, n, W, oprints);
+  ConstScan scan(&pt->m, n);
+  StagedCall call(n, W, 2, in, 2);
+  call.side_parts = scan.parts; call.side = &scan.job; call.abort = &scan.dense;
+  call.side_later = all_operands_resident(in, 2, n, W);      // the scan rides with the check of the resident copies
+  const StagedCall::Verdict v = call.run([&](const uint64_t *const x[], uint64_t *const o[]) {
+    if (hipMemsetAsync(bad.p, 0, 4, nullptr) != hipSuccess) die("device memset failed");
+    if (gpq_he_mulpt_const(c, o[0], o[1], x[0], x[1], ca, cb, W, logql, dim, 0, 1, (unsigned *)bad.p, nullptr) != GPQ_OK) die("he_mulpt failed");
+    if (hipMemcpyAsync(count.p, bad.p, 4, hipMemcpyDeviceToHost, nullptr) != hipSuccess || hipEventRecord(counted, nullptr) != hipSuccess) die("download failed");
+  });
+  if (v == StagedCall::Aborted) return -1;
+  if (hipEventSynchronize(counted) != hipSuccess) die("download failed");
+  if (*(volatile unsigned *)count.p) return 0;
+  call.deliver(out);
   return 1;
 }
 
 // src/he-mult.c:159-196
 void he_mulpt(struct he_ct *dest, const struct he_ct *src, const struct he_pt *pt) {
   SHIM_CALL();
-  need_gcrypt();
-  if (&hectx == nullptr || !hectx.q) die("`hectx` is not initialised (hectx_init first)");
+  need_hectx();
   gpq_ctx *c = engine();
   const unsigned n = polyctx.n, l = src->l;
   const double nu = src->nu * pt->nu, B = src->B * pt->nu;                                      // :163-164
@@ -467,30 +378,15 @@ void he_mulpt(struct he_ct *dest, const struct he_ct *src, const struct he_pt *p
   unsigned bits = max_bits(&pt->m, n);
   if (logql + 1 > bits) bits = logql + 1;
   const unsigned W = bits / 64 + 1;
-  const size_t big = (size_t)W * n;
-  HostBuf s0(big * 8), s1(big * 8), s2(big * 8), t0s(big * 8), t1s(big * 8);
-  DevBuf d0(big * 8), d1(big * 8), dm(big * 8), o0(big * 8), o1(big * 8),
-      ws(gpq_he_mulpt_workspace_bytes(c, dim, 1) + gpq_poly_mul_general_workspace_bytes(c, dim, 1));
-  const DevBuf *dd[3] = {&d0, &d1, &dm}, *oo[2] = {&o0, &o1};
-  const HostBuf *ss[3] = {&s0, &s1, &s2}, *ts[2] = {&t0s, &t1s};
+  DevBuf ws(gpq_he_mulpt_workspace_bytes(c, dim, 1) + gpq_poly_mul_general_workspace_bytes(c, dim, 1));
   const poly_mpi_t *in[3] = {&src->c0, &src->c1, &pt->m};
-  Operands ops(3, in, dd, ss, n, W);
-  ops.prepare(true);
-  auto device_work = [&]() {
-    const int rc = pow2 ? gpq_he_mulpt(c, o0.u64(), o1.u64(), ops.x[0], ops.x[1], ops.x[2], W, logql, dim, 1, ws.p, nullptr)
-                        : gpq_he_mulpt_general(c, o0.u64(), o1.u64(), ops.x[0], ops.x[1], ops.x[2], W, qw.data(), (unsigned)qw.size(), dim, 1, ws.p, nullptr);
-    if (rc != GPQ_OK) die("he_mulpt failed");
-    download_issue(ts, oo, 2, n, W);
-  };
-  device_work();
-  if (ops.resident && ops.recheck()) {
-    if (ops.misfits) die("coefficient does not fit the big slab");
-    device_work();
-  }
   poly_mpi_t *out[2] = {&dest->c0, &dest->c1};
-  std::vector<uint64_t> oprints((size_t)2 * ops.nt, 0);
-  download_convert(out, ts, 2, n, W, oprints.data());
-  remember_results(out, oo, 2, n, W, oprints);
+  StagedCall call(n, W, 3, in, 2);
+  call.run([&](const uint64_t *const x[], uint64_t *const o[]) {
+    const int rc = pow2 ? gpq_he_mulpt(c, o[0], o[1], x[0], x[1], x[2], W, logql, dim, 1, ws.p, nullptr)
+                        : gpq_he_mulpt_general(c, o[0], o[1], x[0], x[1], x[2], W, qw.data(), (unsigned)qw.size(), dim, 1, ws.p, nullptr);
+    if (rc != GPQ_OK) die("he_mulpt failed");
+  }, out);
   dest->l = l; dest->nu = nu; dest->B = B;                                                      // :162-164
 }
 

@@ -11,8 +11,7 @@
 // no reduction -- 2n mpi_set on the host otherwise, and a copy the device knows nothing about)
 static void additive(he_ct_t *ct, const he_ct_t *a, const he_ct_t *b, const he_pt_t *pt, int kind) {
   SHIM_CALL();
-  need_gcrypt();
-  if (&hectx == nullptr || !hectx.q) die("`hectx` is not initialised (hectx_init first)");
+  need_hectx();
   if (kind < 2 && a->l != b->l) die("he_add / he_sub: operands at different levels");              // assert at src/he-add.c:35, :59
   gpq_ctx *c = engine();
   const unsigned n = polyctx.n, l = a->l;
@@ -23,9 +22,8 @@ static void additive(he_ct_t *ct, const he_ct_t *a, const he_ct_t *b, const he_p
   const bool pow2 = is_pow2(qw);
   const unsigned nbq = kind == 5 ? 2 : G.mpi_get_nbits(hectx.q[l]), logql = nbq - 1;
   poly_mpi_t *out[2] = {&ct->c0, &ct->c1};
-  if (logql == 0 && kind != 5) {                            // q_l = 1: mpi_smod leaves -1 everywhere (see he_rs)
-    for (int k = 0; k < 2; ++k)
-      for (unsigned i = 0; i < n; ++i) { G.mpi_set_ui(out[k]->coeffs[i], 1); G.mpi_neg(out[k]->coeffs[i], out[k]->coeffs[i]); }
+  if (logql == 0 && kind != 5) {                            // q_l = 1
+    fill_minus_one(out[0], n); fill_minus_one(out[1], n);
     ct->l = l; ct->nu = nu; ct->B = B;
     return;
   }
@@ -39,73 +37,44 @@ static void additive(he_ct_t *ct, const he_ct_t *a, const he_ct_t *b, const he_p
     auto pass = [&](unsigned W, bool kept) -> bool {
       if (W > 32) die("he_add: coefficients wider than 2047 bits");
       const size_t big = (size_t)W * n;
-      HostBuf s0(big * 8), s1(big * 8), s2(count > 2 ? big * 8 : 8), s3(count > 3 ? big * 8 : 8), t0s(big * 8), t1s(big * 8);
-      DevBuf d0(big * 8), d1(big * 8), d2(count > 2 ? big * 8 : 8), d3(count > 3 ? big * 8 : 8), o0(big * 8), o1(big * 8), scratch(192 * 8);
-      const DevBuf *dd[4] = {&d0, &d1, &d2, &d3}, *oo[2] = {&o0, &o1};
-      const HostBuf *ss[4] = {&s0, &s1, &s2, &s3}, *ts[2] = {&t0s, &t1s};
+      DevBuf scratch(192 * 8);
       ConstScan scan(cpt ? &pt->m : nullptr, n);
-      const bool later = cpt && kept && all_operands_resident(in, count, n, W);   // the scan rides with the check of the resident copies
-      Operands ops(count, in, dd, ss, n, W);
-      if (cpt && !later) ops.prepare(kept, scan.parts, &scan.job); else ops.prepare(kept);
-      // (on every way out before download_convert: the copies queued into / out of this pass's page-locked buffers land before the buffers return to the pool)
-      if (scan.dense.load()) { (void)gpq_stream_sync(nullptr); dense = true; return true; }
-      auto device_work = [&]() {
+      StagedCall call(n, W, count, in, 2);
+      call.speculate = kept; call.report_misfits = true; call.Wdown = Wout < W ? Wout : W;
+      if (cpt) {
+        call.side_parts = scan.parts; call.side = &scan.job; call.abort = &scan.dense;
+        call.side_later = kept && all_operands_resident(in, count, n, W);   // the scan rides with the check of the resident copies
+      }
+      const StagedCall::Verdict v = call.run([&](const uint64_t *const x[], uint64_t *const o[]) {
         int rc;
         if (kind == 5) {
-          if (hipMemcpyAsync(o0.p, ops.x[0], big * 8, hipMemcpyDeviceToDevice, nullptr) != hipSuccess ||
-              hipMemcpyAsync(o1.p, ops.x[1], big * 8, hipMemcpyDeviceToDevice, nullptr) != hipSuccess) die("device copy failed");
-          download_issue(ts, oo, 2, n, W);
+          if (hipMemcpyAsync(o[0], x[0], big * 8, hipMemcpyDeviceToDevice, nullptr) != hipSuccess ||
+              hipMemcpyAsync(o[1], x[1], big * 8, hipMemcpyDeviceToDevice, nullptr) != hipSuccess) die("device copy failed");
           return;
         }
         if (cpt) {                                            // the sum, c1's copy and both mpi_smod in one launch
-          if (gpq_he_addpt_const(c, o0.u64(), o1.u64(), ops.x[0], ops.x[1], ca, cb, kind & 1, W, logql, 1, nullptr) != GPQ_OK) die("he_addpt failed");
-          download_issue(ts, oo, 2, n, Wout < W ? Wout : W);
+          if (gpq_he_addpt_const(c, o[0], o[1], x[0], x[1], ca, cb, kind & 1, W, logql, 1, nullptr) != GPQ_OK) die("he_addpt failed");
           return;
         }
         if (kind == 4) {
-          rc = gpq_big_addsub(c, o0.u64(), ops.x[0], nullptr, W, 1, 2, nullptr);
-          if (rc == GPQ_OK) rc = gpq_big_addsub(c, o1.u64(), ops.x[1], nullptr, W, 1, 2, nullptr);
+          rc = gpq_big_addsub(c, o[0], x[0], nullptr, W, 1, 2, nullptr);
+          if (rc == GPQ_OK) rc = gpq_big_addsub(c, o[1], x[1], nullptr, W, 1, 2, nullptr);
         } else {
-          rc = gpq_big_addsub(c, o0.u64(), ops.x[0], ops.x[2], W, 1, kind & 1, nullptr);              // c0 (+/-) the other c0 or the plaintext
-          if (rc == GPQ_OK && kind < 2) rc = gpq_big_addsub(c, o1.u64(), ops.x[1], ops.x[3], W, 1, kind & 1, nullptr);
-          else if (rc == GPQ_OK && hipMemcpyAsync(o1.p, ops.x[1], big * 8, hipMemcpyDeviceToDevice, nullptr) != hipSuccess) die("device copy failed");   // c1 mod q, :92, :115
+          rc = gpq_big_addsub(c, o[0], x[0], x[2], W, 1, kind & 1, nullptr);                          // c0 (+/-) the other c0 or the plaintext
+          if (rc == GPQ_OK && kind < 2) rc = gpq_big_addsub(c, o[1], x[1], x[3], W, 1, kind & 1, nullptr);
+          else if (rc == GPQ_OK && hipMemcpyAsync(o[1], x[1], big * 8, hipMemcpyDeviceToDevice, nullptr) != hipSuccess) die("device copy failed");   // c1 mod q, :92, :115
         }
         if (rc == GPQ_OK)                                                                              // mpi_smod of both, :43-44 ...
-          rc = pow2 ? gpq_he_rs(c, o0.u64(), o1.u64(), W, 0, logql, 1, nullptr)
-                    : gpq_he_rs_general(c, o0.u64(), o1.u64(), W, 1ull, qw.data(), (unsigned)qw.size(), 1, scratch.p, nullptr);
+          rc = pow2 ? gpq_he_rs(c, o[0], o[1], W, 0, logql, 1, nullptr)
+                    : gpq_he_rs_general(c, o[0], o[1], W, 1ull, qw.data(), (unsigned)qw.size(), 1, scratch.p, nullptr);
         if (rc != GPQ_OK) die("he_add failed");
-        download_issue(ts, oo, 2, n, Wout < W ? Wout : W);
-      };
-      device_work();
-      if (ops.resident) {
-        const bool again = ops.recheck(later ? scan.parts : 0, later ? &scan.job : nullptr);
-        if (scan.dense.load()) { (void)gpq_stream_sync(nullptr); dense = true; return true; }
-        if (again) {
-          if (ops.misfits) { (void)gpq_stream_sync(nullptr); return false; }   // (as in mpi_shim.hip: queued copies land before the buffers return to the pool)
-          device_work();
-        }
-      }
-      const unsigned Wdown = Wout < W ? Wout : W;
-      std::vector<uint64_t> oprints((size_t)2 * ops.nt, 0);
-      download_convert(out, ts, 2, n, Wdown, oprints.data());
-      remember_results(out, oo, 2, n, Wdown, oprints);
-      return true;
+      }, out);
+      if (v == StagedCall::Aborted) dense = true;
+      return v != StagedCall::Misfit;
     };
-    bool done = false;
-    if ((pow2 || kind == 5) && poly_cache_on(n)) {            // wrapping sums are harmless below a power of two; any other q_l measures its operands first
-      unsigned W = 0;
-      bool all = true;
-      for (int i = 0; i < count && all; ++i) {
-        const PolySlot *k = resident_poly(in[i], n, 0);
-        if (!k || !k->trusted || (W && k->W != W)) all = false; else W = k->W;
-      }
-      if (all && (W >= Wout || kind == 5)) done = pass(W, true);
-    }
-    if (!done) {
-      unsigned bits = nbq;
-      for (int i = 0; i < count; ++i) { const unsigned bi = max_bits(in[i], n); if (bi > bits) bits = bi; }
-      pass((bits + 1) / 64 + 1, false);                       // one bit of headroom: the sum of two such integers still fits
-    }
+    // wrapping sums are harmless below a power of two; any other q_l measures its operands first.  One bit of headroom: the sum of two
+    // such integers still fits.  A copy keeps every word: any width of the resident copies serves it.
+    width_ladder(in, count, n, pow2 || kind == 5, kind == 5 ? 1 : Wout, nbq, 1, pass);
     return !dense;
   };
   int64_t ca = 0, cb = 0;
@@ -122,10 +91,9 @@ void he_neg(he_ct_t *ct) { additive(ct, ct, nullptr, nullptr, 4); }
 void he_copy_ct(he_ct_t *dest, const he_ct_t *src) { if (dest != src) additive(dest, src, nullptr, nullptr, 5); }      // src/he-mem.c:88-97
 
 // he_rot / he_conj, src/he-automorphism.c:87-115: permute both polynomials, then he_swk (:40-85) in place
-static void automorphism(he_ct_t *ct, const he_evk_t *key, bool conj, unsigned rot) {
+static void automorphism(he_ct_t *ct, const he_evk_t *evk, bool conj, unsigned rot) {
   SHIM_CALL();
-  need_gcrypt();
-  if (&hectx == nullptr || !hectx.q) die("`hectx` is not initialised (hectx_init first)");
+  need_hectx();
   gpq_ctx *c = engine();
   const unsigned n = polyctx.n, l = ct->l;
   const std::vector<uint64_t> qw = words_of(hectx.q[l], "he_rot/he_conj: q_l must be positive");
@@ -134,43 +102,23 @@ static void automorphism(he_ct_t *ct, const he_evk_t *key, bool conj, unsigned r
   const unsigned dimB = (nbq + nbPqL + polyctx.logn) / 59 + 1, dimP = hectx.dim;                // src/he-automorphism.c:52
   const unsigned W = logql / 64 + 1;
   const size_t big = (size_t)W * n;
-  HostBuf s0(big * 8), s1(big * 8), t0s(big * 8), t1s(big * 8);
-  DevBuf a0(big * 8), a1(big * 8), r0(big * 8), r1(big * 8), o0(big * 8), o1(big * 8),
-      ws(pow2 ? gpq_he_swk_workspace_bytes(c, W, dimB, dimP, 1) : gpq_he_general_workspace_bytes(c, W, 0, dimB, dimP, 1));
-  const DevBuf *dd[2] = {&a0, &a1}, *oo[2] = {&o0, &o1};
-  const HostBuf *ss[2] = {&s0, &s1}, *ts[2] = {&t0s, &t1s};
+  DevBuf r0(big * 8), r1(big * 8), ws(pow2 ? gpq_he_swk_workspace_bytes(c, W, dimB, dimP, 1) : gpq_he_general_workspace_bytes(c, W, 0, dimB, dimP, 1));
   const poly_mpi_t *in[2] = {&ct->c0, &ct->c1};
-  KeyPrint kp(key, dimB, n);
-  KeySlot *spec = resident_key(kp);
-  Operands ops(2, in, dd, ss, n, W);
-  if (spec) ops.prepare(true); else ops.prepare(false, kp.parts, &kp.task);
-  uint64_t *k0, *k1;
-  if (spec) { k0 = (uint64_t *)spec->d0; k1 = (uint64_t *)spec->d1; } else key_on_device(kp, &k0, &k1);
-  auto device_work = [&]() {
-    int rc = conj ? gpq_poly_conj(c, r0.u64(), ops.x[0], W, 1, nullptr) : gpq_poly_rot(c, r0.u64(), ops.x[0], W, rot, 1, nullptr);      // :95-96 / :108-109
-    if (rc == GPQ_OK) rc = conj ? gpq_poly_conj(c, r1.u64(), ops.x[1], W, 1, nullptr) : gpq_poly_rot(c, r1.u64(), ops.x[1], W, rot, 1, nullptr);
+  poly_mpi_t *out[2] = {&ct->c0, &ct->c1};
+  StagedCall call(n, W, 2, in, 2);
+  CallKey key(evk, dimB, n);
+  key.ride(call);
+  call.prepare();
+  key.settle();
+  call.run([&](const uint64_t *const x[], uint64_t *const o[]) {
+    int rc = conj ? gpq_poly_conj(c, r0.u64(), x[0], W, 1, nullptr) : gpq_poly_rot(c, r0.u64(), x[0], W, rot, 1, nullptr);              // :95-96 / :108-109
+    if (rc == GPQ_OK) rc = conj ? gpq_poly_conj(c, r1.u64(), x[1], W, 1, nullptr) : gpq_poly_rot(c, r1.u64(), x[1], W, rot, 1, nullptr);
     if (rc == GPQ_OK)                                                                                                                       // :97 / :110
-      rc = pow2 ? gpq_he_swk(c, o0.u64(), o1.u64(), r0.u64(), r1.u64(), k0, k1, W, logql, dimB, dimP, 1, ws.p, nullptr)
-                : gpq_he_swk_general(c, o0.u64(), o1.u64(), r0.u64(), r1.u64(), k0, k1, W, qw.data(), (unsigned)qw.size(), dimB, dimP, 1,
+      rc = pow2 ? gpq_he_swk(c, o[0], o[1], r0.u64(), r1.u64(), key.k0, key.k1, W, logql, dimB, dimP, 1, ws.p, nullptr)
+                : gpq_he_swk_general(c, o[0], o[1], r0.u64(), r1.u64(), key.k0, key.k1, W, qw.data(), (unsigned)qw.size(), dimB, dimP, 1,
                                      ws.p, nullptr);
     if (rc != GPQ_OK) die("he_rot/he_conj failed");
-    download_issue(ts, oo, 2, n, W);
-  };
-  device_work();
-  bool again = false;
-  if (ops.resident) {
-    again = ops.recheck(kp.parts, &kp.task);
-    if (ops.misfits) die("coefficient does not fit the big slab");
-    if (!kp.matches(*spec)) { key_on_device(kp, &k0, &k1); again = true; }
-  } else if (spec && !key_still_valid(spec, kp)) {
-    key_on_device(kp, &k0, &k1);
-    again = true;
-  }
-  if (again) device_work();
-  poly_mpi_t *out[2] = {&ct->c0, &ct->c1};
-  std::vector<uint64_t> oprints((size_t)2 * ops.nt, 0);
-  download_convert(out, ts, 2, n, W, oprints.data());
-  remember_results(out, oo, 2, n, W, oprints);
+  }, out);
 }
 void he_conj(he_ct_t *ct, const he_evk_t *ck) { automorphism(ct, ck, true, 0); }
 void he_rot(he_ct_t *ct, const int rot, const he_evk_t *rk) { automorphism(ct, &rk[rot], false, (unsigned)rot); }   // rk[rot], :110

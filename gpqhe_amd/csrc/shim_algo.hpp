@@ -107,8 +107,7 @@ static GemvPlanEntry *gemv_plan_on_device(gpq_ctx *c, GemvPlanKey &key, const Ge
 // kind 0: he_gemv (raw = the caller's slots x slots matrix), 1: he_sum, 2: he_idx (idx): what the plan cache keys on (shim_gemv_plans.hpp)
 static void gemv_impl(he_ct_t *ct_dest, const GemvMatrix &A, const he_ct_t *ct, const he_evk_t *rk, unsigned kind, unsigned idx, const gpq_zc *raw) {
   SHIM_CALL();
-  need_gcrypt();
-  if (&hectx == nullptr || !hectx.q) die("`hectx` is not initialised (hectx_init first)");
+  need_hectx();
   if (!he_ecd && !g_device_ecd) die("he_gemv: the host program provides no he_ecd (src/he-encode.c)");
   gpq_ctx *c = engine();
   const unsigned n = polyctx.n, l = ct->l, slots = hectx.slots;
@@ -194,9 +193,7 @@ static void gemv_impl(he_ct_t *ct_dest, const GemvMatrix &A, const he_ct_t *ct, 
     (void)gpq_gemv_plan_rotations(plan, needed.data());
     for (auto it = rots.begin(); it != rots.end();) it = needed[*it] ? std::next(it) : rots.erase(it);
   }
-  HostBuf s0(big * 8), s1(big * 8), t0s(big * 8), t1s(big * 8);
-  DevBuf a0(big * 8), a1(big * 8), o0(big * 8), o1(big * 8),
-         ws(plan ? gpq_he_gemv_planned_workspace_bytes(c, plan, W, dimB, dimP, 1) : gpq_he_gemv_workspace_bytes(c, W, slots, dimB, dimP, dimpt, 1));
+  DevBuf ws(plan ? gpq_he_gemv_planned_workspace_bytes(c, plan, W, dimB, dimP, 1) : gpq_he_gemv_workspace_bytes(c, W, slots, dimB, dimP, dimpt, 1));
   std::vector<const uint64_t *> k0(slots, nullptr), k1(slots, nullptr);
   for (unsigned r : rots) {                                        // at most g_key_slots keys: none of them is evicted by the next one
     KeyPrint kp(&rk[r], dimB, n);
@@ -205,27 +202,15 @@ static void gemv_impl(he_ct_t *ct_dest, const GemvMatrix &A, const he_ct_t *ct, 
     key_on_device(kp, &d0, &d1);
     k0[r] = d0; k1[r] = d1;
   }
-  const DevBuf *dd[2] = {&a0, &a1}, *oo[2] = {&o0, &o1};
-  const HostBuf *ss[2] = {&s0, &s1}, *ts[2] = {&t0s, &t1s};
   const poly_mpi_t *in[2] = {&ct->c0, &ct->c1};
-  Operands ops(2, in, dd, ss, n, W);
-  ops.prepare(true);
-  auto device_work = [&]() {
-    const int rc = plan ? gpq_he_gemv_planned(c, o0.u64(), o1.u64(), ops.x[0], ops.x[1], plan, k0.data(), k1.data(), W, logql - logql1, dimB, dimP, 1, ws.p, nullptr)
-                        : gpq_he_gemv(c, o0.u64(), o1.u64(), ops.x[0], ops.x[1], (const uint64_t *)dg->p, k0.data(), k1.data(), slots, W, logql, logql - logql1,
+  poly_mpi_t *out[2] = {&ct_dest->c0, &ct_dest->c1};
+  StagedCall call(n, W, 2, in, 2);
+  call.run([&](const uint64_t *const x[], uint64_t *const o[]) {
+    const int rc = plan ? gpq_he_gemv_planned(c, o[0], o[1], x[0], x[1], plan, k0.data(), k1.data(), W, logql - logql1, dimB, dimP, 1, ws.p, nullptr)
+                        : gpq_he_gemv(c, o[0], o[1], x[0], x[1], (const uint64_t *)dg->p, k0.data(), k1.data(), slots, W, logql, logql - logql1,
                                       dimB, dimP, dimpt, 1, ws.p, nullptr);
     if (rc != GPQ_OK) die("he_gemv failed");
-    download_issue(ts, oo, 2, n, W);
-  };
-  device_work();
-  if (ops.resident && ops.recheck()) {
-    if (ops.misfits) die("coefficient does not fit the big slab");
-    device_work();
-  }
-  poly_mpi_t *out[2] = {&ct_dest->c0, &ct_dest->c1};
-  std::vector<uint64_t> oprints((size_t)2 * ops.nt, 0);
-  download_convert(out, ts, 2, n, W, oprints.data());
-  remember_results(out, oo, 2, n, W, oprints);
+  }, out);
   ct_dest->l = l - 1;                                                                          // he_copy_ct + he_rs
   ct_dest->nu = onu / hectx.Delta;
   ct_dest->B = oB / hectx.Delta + hectx.bnd.Brs;

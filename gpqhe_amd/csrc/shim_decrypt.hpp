@@ -11,8 +11,7 @@
 } // extern "C"
 namespace {
 bool dec_body(struct he_pt *pt, _Complex double *z, const struct he_ct *ct, const poly_mpi_t *sk) {
-  need_gcrypt();
-  if (&hectx == nullptr || !hectx.q) die("`hectx` is not initialised (hectx_init first)");
+  need_hectx();
   gpq_ctx *c = engine();
   const unsigned n = polyctx.n, l = ct->l;
   const std::vector<uint64_t> qw = words_of(hectx.q[l], "he_dec: q_l must be positive");
@@ -33,69 +32,41 @@ bool dec_body(struct he_pt *pt, _Complex double *z, const struct he_ct *ct, cons
     dplan = g_dcd_plan.plan;
   } else {
     pt->nu = ct->nu;                                                                             // :108
-    if (logql == 0) {                                       // q_l = 1: mpi_smod leaves -1 everywhere (see he_rs)
-      for (unsigned i = 0; i < n; ++i) { G.mpi_set_ui(pt->m.coeffs[i], 1); G.mpi_neg(pt->m.coeffs[i], pt->m.coeffs[i]); }
-      return true;
-    }
+    if (logql == 0) { fill_minus_one(&pt->m, n); return true; }   // q_l = 1
   }
   const unsigned Wout = logql / 64 + 1;
   const size_t zbytes = (size_t)slots * 16;
   auto pass = [&](unsigned W, bool kept) -> bool {
     if (W > 32) die("he_dec: coefficients wider than 2047 bits");
     const size_t big = (size_t)W * n;
-    HostBuf s0(big * 8), s1(big * 8), s2(big * 8), t0s(big * 8);
-    DevBuf d0(big * 8), d1(big * 8), d2(big * 8), dr(big * 8), dz(big * 8), ws(gpq_poly_mul_general_workspace_bytes(c, dim, 1)), scratch(192 * 8);
-    DevBuf dzs(z ? zbytes : 8);
-    HostBuf hz(z ? zbytes : 8);
-    const DevBuf *dd[3] = {&d0, &d1, &d2}, *oo[1] = {&dr};
-    const HostBuf *ss[3] = {&s0, &s1, &s2}, *ts[1] = {&t0s};
-    Operands ops(3, in, dd, ss, n, W);
-    ops.prepare(kept);
-    const unsigned Wdown = Wout < W ? Wout : W;
-    auto device_work = [&]() {
-      int rc = pow2 ? gpq_poly_mul(c, dr.u64(), ops.x[0], ops.x[1], W, dim, logql, 1, ws.p, nullptr)                                   // :115
-                    : gpq_poly_mul_general(c, dr.u64(), ops.x[0], ops.x[1], W, dim, qw.data(), (unsigned)qw.size(), 1, ws.p, nullptr);
-      if (rc == GPQ_OK) rc = gpq_big_addsub(c, dr.u64(), dr.u64(), ops.x[2], W, 1, 0, nullptr);                                       // :117
+    DevBuf dz(big * 8), ws(gpq_poly_mul_general_workspace_bytes(c, dim, 1)), scratch(192 * 8);
+    std::unique_ptr<DevBuf> dm, dzs;                          // z: the plaintext stays in a slab of the call's own, the doubles come down
+    std::unique_ptr<HostBuf> hz;
+    if (z) { dm.reset(new DevBuf(big * 8)); dzs.reset(new DevBuf(zbytes)); hz.reset(new HostBuf(zbytes)); }
+    StagedCall call(n, W, 3, in, z ? 0 : 1);
+    call.speculate = kept; call.report_misfits = true; call.Wdown = Wout < W ? Wout : W;
+    const StagedCall::Verdict v = call.run([&](const uint64_t *const x[], uint64_t *const o[]) {
+      uint64_t *const dr = z ? dm->u64() : o[0];
+      int rc = pow2 ? gpq_poly_mul(c, dr, x[0], x[1], W, dim, logql, 1, ws.p, nullptr)                                                 // :115
+                    : gpq_poly_mul_general(c, dr, x[0], x[1], W, dim, qw.data(), (unsigned)qw.size(), 1, ws.p, nullptr);
+      if (rc == GPQ_OK) rc = gpq_big_addsub(c, dr, dr, x[2], W, 1, 0, nullptr);                                                       // :117
       if (rc == GPQ_OK && hipMemsetAsync(dz.p, 0, big * 8, nullptr) != hipSuccess) die("device memset failed");                       // the centring kernels take a pair
       if (rc == GPQ_OK)                                                                                                                // :118
-        rc = pow2 ? gpq_he_rs(c, dr.u64(), dz.u64(), W, 0, logql, 1, nullptr)
-                  : gpq_he_rs_general(c, dr.u64(), dz.u64(), W, 1ull, qw.data(), (unsigned)qw.size(), 1, scratch.p, nullptr);
+        rc = pow2 ? gpq_he_rs(c, dr, dz.u64(), W, 0, logql, 1, nullptr)
+                  : gpq_he_rs_general(c, dr, dz.u64(), W, 1ull, qw.data(), (unsigned)qw.size(), 1, scratch.p, nullptr);
       if (rc != GPQ_OK) die("he_dec failed");
-      if (!z) { download_issue(ts, oo, 1, n, Wdown); return; }
+      if (!z) return;
       // the centred plaintext (sign-extended over all W words) is decoded where it lies
-      if (gpq_he_dcd(c, dplan, (double *)dzs.p, dr.u64(), ct->nu, W, 1, nullptr) != GPQ_OK) die("he_dec_dcd: gpq_he_dcd failed");
-      if (gpq_download(hz.p, dzs.p, zbytes, nullptr) != GPQ_OK) die("download failed");
-    };
-    device_work();
-    if (ops.resident && ops.recheck()) {
-      if (ops.misfits) { (void)gpq_stream_sync(nullptr); return false; }   // the copies queued into / out of this pass's page-locked buffers must land before the buffers go back to the pool
-      device_work();
-    }
-    if (z) {
-      if (gpq_stream_sync(nullptr) != GPQ_OK) die("he_dec_dcd: the device work failed");
-      memcpy(z, hz.p, zbytes);
-      return true;
-    }
-    std::vector<uint64_t> oprints((size_t)ops.nt, 0);
-    download_convert(out, ts, 1, n, Wdown, oprints.data());
-    remember_results(out, oo, 1, n, Wdown, oprints);
+      if (gpq_he_dcd(c, dplan, (double *)dzs->p, dr, ct->nu, W, 1, nullptr) != GPQ_OK) die("he_dec_dcd: gpq_he_dcd failed");
+      if (gpq_download(hz->p, dzs->p, zbytes, nullptr) != GPQ_OK) die("download failed");
+    });
+    if (v != StagedCall::Done) return false;
+    if (!z) { call.deliver(out); return true; }
+    if (call.sync() != GPQ_OK) die("he_dec_dcd: the device work failed");
+    memcpy(z, hz->p, zbytes);
     return true;
   };
-  bool done = false;
-  if (pow2 && poly_cache_on(n)) {
-    unsigned W = 0;
-    bool all = true;
-    for (int i = 0; i < 3 && all; ++i) {
-      const PolySlot *k = resident_poly(in[i], n, 0);
-      if (!k || !k->trusted || (W && k->W != W)) all = false; else W = k->W;
-    }
-    if (all && W >= Wout) done = pass(W, true);
-  }
-  if (!done) {
-    unsigned bits = nbq;
-    for (int i = 0; i < 3; ++i) { const unsigned bi = max_bits(in[i], n); if (bi > bits) bits = bi; }
-    pass((bits + 1) / 64 + 1, false);
-  }
+  width_ladder(in, 3, n, pow2, Wout, nbq, 1, pass);
   return true;
 }
 }  // namespace

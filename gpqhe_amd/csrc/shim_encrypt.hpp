@@ -7,7 +7,7 @@
 // randombytes (weak) is called once per sampler call with the reference's byte counts -- n/4 (zo), n (error), n (nbits/8 + 1) (uniform) --
 // and gpq_sample_zo / gpq_sample_error / gpq_sample_uniform expand the bytes on the device; sample_sk stays the host's.  Power-of-two q_L
 // takes gpq_he_enc_pk / gpq_he_enc_sk; any other q_L the reference's sequence over the general entry points.  The key polynomials and the
-// plaintext are resident operands like he_dec's (Operands), the written ciphertext / public key is remembered (remember_results).
+// plaintext are resident operands like he_dec's, the written ciphertext / public key is remembered (one StagedCall, shim_call.hpp).
 // gpq_mpi_shim_set_device_rng(1) on top of the device samplers: the same byte counts in the same order are reserved from the default stream
 // of gpq_randombytes and generated in device memory by ONE gpq_randombytes_device per call; the samplers read slices of that buffer.
 } // extern "C"
@@ -112,59 +112,46 @@ void enc_body(int kind, poly_mpi_t *out0, poly_mpi_t *out1, const poly_mpi_t *ke
   auto pass = [&](unsigned W, bool kept, const DevBuf *da) -> bool {
     if (W > 32) die("he_enc: coefficients wider than 2047 bits");
     const size_t big = (size_t)W * n, slab = (size_t)dim * n * 8;
-    HostBuf s0(big * 8), s1(count > 1 ? big * 8 : 8), s2(count > 2 ? big * 8 : 8), t0s(big * 8), t1s(big * 8);
-    DevBuf d0(big * 8), d1(count > 1 ? big * 8 : 8), d2(count > 2 ? big * 8 : 8), o0(big * 8), o1(big * 8), k0(slab), k1(slab), tb(big * 8), scratch(192 * 8),
+    DevBuf k0(slab), k1(slab), tb(big * 8), scratch(192 * 8),
         ws(pow2 ? gpq_he_enc_workspace_bytes(c, dim, 1, kind == 0) : gpq_poly_mul_general_workspace_bytes(c, dim, 1));
-    const DevBuf *dd[3] = {&d0, &d1, &d2}, *oo[2] = {&o0, &o1};
-    const HostBuf *ss[3] = {&s0, &s1, &s2}, *ts[2] = {&t0s, &t1s};
-    Operands ops(count, in, dd, ss, n, W);
-    ops.prepare(kept);
+    StagedCall call(n, W, count, in, 2);
+    call.speculate = kept; call.report_misfits = true;
     auto ok = [](int rc) { if (rc != GPQ_OK) die("he_enc: the device work failed"); };
-    auto add_small = [&](const DevBuf &dst, const DevBuf &small) {                      // dst += small, through a big slab
+    auto add_small = [&](uint64_t *dst, const DevBuf &small) {                          // dst += small, through a big slab
       ok(gpq_small_to_big(c, tb.u64(), (const int8_t *)small.p, W, 1, nullptr));
-      ok(gpq_big_addsub(c, dst.u64(), dst.u64(), tb.u64(), W, 1, 0, nullptr));
+      ok(gpq_big_addsub(c, dst, dst, tb.u64(), W, 1, 0, nullptr));
     };
-    auto device_work = [&]() {
+    return call.run([&](const uint64_t *const x[], uint64_t *const o[]) {
       if (kind == 0) {
-        const uint64_t *p0 = ops.x[0], *p1 = ops.x[1], *mm = ops.x[2];
+        const uint64_t *p0 = x[0], *p1 = x[1], *mm = x[2];
         if (pow2) {
           ok(gpq_evk_pack(c, k0.u64(), p0, W, dim, 1, nullptr));
           ok(gpq_evk_pack(c, k1.u64(), p1, W, dim, 1, nullptr));
-          ok(gpq_he_enc_pk(c, o0.u64(), o1.u64(), mm, (const int8_t *)dv.p, (const int8_t *)de0.p, (const int8_t *)de1.p, k0.u64(), k1.u64(), W, logq, dim, 1, ws.p, nullptr));
+          ok(gpq_he_enc_pk(c, o[0], o[1], mm, (const int8_t *)dv.p, (const int8_t *)de0.p, (const int8_t *)de1.p, k0.u64(), k1.u64(), W, logq, dim, 1, ws.p, nullptr));
         } else {                                                                        // src/he-encrypt.c:58-66 call by call
           ok(gpq_small_to_big(c, tb.u64(), (const int8_t *)dv.p, W, 1, nullptr));
-          ok(gpq_poly_mul_general(c, o0.u64(), p0, tb.u64(), W, dim, qw.data(), (unsigned)qw.size(), 1, ws.p, nullptr));
-          ok(gpq_poly_mul_general(c, o1.u64(), p1, tb.u64(), W, dim, qw.data(), (unsigned)qw.size(), 1, ws.p, nullptr));
-          ok(gpq_big_addsub(c, o0.u64(), o0.u64(), mm, W, 1, 0, nullptr));
-          add_small(o0, de0);
-          add_small(o1, de1);
-          ok(gpq_he_rs_general(c, o0.u64(), o1.u64(), W, 1ull, qw.data(), (unsigned)qw.size(), 1, scratch.p, nullptr));
+          ok(gpq_poly_mul_general(c, o[0], p0, tb.u64(), W, dim, qw.data(), (unsigned)qw.size(), 1, ws.p, nullptr));
+          ok(gpq_poly_mul_general(c, o[1], p1, tb.u64(), W, dim, qw.data(), (unsigned)qw.size(), 1, ws.p, nullptr));
+          ok(gpq_big_addsub(c, o[0], o[0], mm, W, 1, 0, nullptr));
+          add_small(o[0], de0);
+          add_small(o[1], de1);
+          ok(gpq_he_rs_general(c, o[0], o[1], W, 1ull, qw.data(), (unsigned)qw.size(), 1, scratch.p, nullptr));
         }
       } else {
-        const uint64_t *s = ops.x[0], *mm = kind == 1 ? ops.x[1] : nullptr;
+        const uint64_t *s = x[0], *mm = kind == 1 ? x[1] : nullptr;
         if (pow2) {
           ok(gpq_evk_pack(c, k0.u64(), s, W, dim, 1, nullptr));
-          ok(gpq_he_enc_sk(c, o0.u64(), o1.u64(), mm, da->u64(), (const int8_t *)de0.p, k0.u64(), W, logq, dim, 1, ws.p, nullptr));
+          ok(gpq_he_enc_sk(c, o[0], o[1], mm, da->u64(), (const int8_t *)de0.p, k0.u64(), W, logq, dim, 1, ws.p, nullptr));
         } else {                                                                        // :91-97 / src/he-kem.c:59-64 call by call
-          ok(gpq_poly_mul_general(c, o0.u64(), da->u64(), s, W, dim, qw.data(), (unsigned)qw.size(), 1, ws.p, nullptr));
-          ok(gpq_big_addsub(c, o0.u64(), o0.u64(), nullptr, W, 1, 2, nullptr));
-          if (mm) ok(gpq_big_addsub(c, o0.u64(), o0.u64(), mm, W, 1, 0, nullptr));
-          add_small(o0, de0);
-          if (hipMemcpyAsync(o1.p, da->p, big * 8, hipMemcpyDeviceToDevice, nullptr) != hipSuccess) die("device copy failed");
-          ok(gpq_he_rs_general(c, o0.u64(), o1.u64(), W, 1ull, qw.data(), (unsigned)qw.size(), 1, scratch.p, nullptr));
+          ok(gpq_poly_mul_general(c, o[0], da->u64(), s, W, dim, qw.data(), (unsigned)qw.size(), 1, ws.p, nullptr));
+          ok(gpq_big_addsub(c, o[0], o[0], nullptr, W, 1, 2, nullptr));
+          if (mm) ok(gpq_big_addsub(c, o[0], o[0], mm, W, 1, 0, nullptr));
+          add_small(o[0], de0);
+          if (hipMemcpyAsync(o[1], da->p, big * 8, hipMemcpyDeviceToDevice, nullptr) != hipSuccess) die("device copy failed");
+          ok(gpq_he_rs_general(c, o[0], o[1], W, 1ull, qw.data(), (unsigned)qw.size(), 1, scratch.p, nullptr));
         }
       }
-      download_issue(ts, oo, 2, n, W);
-    };
-    device_work();
-    if (ops.resident && ops.recheck()) {
-      if (ops.misfits) { (void)gpq_stream_sync(nullptr); return false; }   // (as in mpi_shim.hip: queued copies land before the buffers return to the pool)
-      device_work();
-    }
-    std::vector<uint64_t> oprints((size_t)2 * ops.nt, 0);
-    download_convert(out, ts, 2, n, W, oprints.data());
-    remember_results(out, oo, 2, n, W, oprints);
-    return true;
+    }, out) == StagedCall::Done;
   };
   // the width: what holds q and every operand; the raw sample is made at that width once it is known
   auto run = [&](unsigned W, bool kept) -> bool {
@@ -178,16 +165,12 @@ void enc_body(int kind, poly_mpi_t *out0, poly_mpi_t *out1, const poly_mpi_t *ke
   const unsigned W = (bits + 1) / 64 + 1 > Wmin ? (bits + 1) / 64 + 1 : Wmin;
   if (!run(W, true)) die("he_enc: an operand changed width during the call");   // (operands with a trusted resident copy at this width are taken from it)
 }
-void enc_entry() {
-  need_gcrypt();
-  if (&hectx == nullptr || !hectx.q) die("`hectx` is not initialised (hectx_init first)");
-}
 }  // namespace
 extern "C" {
 
 void he_enc_pk(struct he_ct *ct, const struct he_pt *pt, const struct he_pk *pk) {
   SHIM_CALL();
-  enc_entry();
+  need_hectx();
   ct->l = hectx.L;                                                                       // src/he-encrypt.c:40-42
   ct->nu = pt->nu >= hectx.Delta ? pt->nu : hectx.Delta;
   ct->B = hectx.bnd.Bclean;
@@ -196,7 +179,7 @@ void he_enc_pk(struct he_ct *ct, const struct he_pt *pt, const struct he_pk *pk)
 
 void he_enc_sk(struct he_ct *ct, const struct he_pt *pt, const poly_mpi_t *sk) {
   SHIM_CALL();
-  enc_entry();
+  need_hectx();
   ct->l = hectx.L;                                                                       // :78-80
   ct->nu = pt->nu >= hectx.Delta ? pt->nu : hectx.Delta;
   ct->B = hectx.bnd.Bclean;
@@ -205,7 +188,7 @@ void he_enc_sk(struct he_ct *ct, const struct he_pt *pt, const poly_mpi_t *sk) {
 
 void he_keypair(he_pk_t *pk, poly_mpi_t *sk) {                                            // src/he-kem.c:43-71
   SHIM_CALL();
-  enc_entry();
+  need_hectx();
   if (!sample_sk) die("he_keypair: the host program does not provide sample_sk (src/sample.c)");
   printf("Generating sk and pk ... ");
   fflush(stdout);

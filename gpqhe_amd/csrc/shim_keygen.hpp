@@ -22,8 +22,7 @@ struct KeygenSecret {                                       // what every key of
 };
 
 void keygen_secret(KeygenSecret &k, const poly_mpi_t *sk) {
-  need_gcrypt();
-  if (&hectx == nullptr || !hectx.q) die("`hectx` is not initialised (hectx_init first)");
+  need_hectx();
   gpq_ctx *c = engine();
   const unsigned n = polyctx.n;
   if (!is_pow2(words_of(hectx.q[hectx.L], "he_gen*k: q_L must be positive"))) die("he_gen*k: q_L must be a power of two on this path");

@@ -9,7 +9,7 @@ namespace {
 // it is given on every call, src/he-mult.c:60-64: a key edited in place, in however few words, must multiply as edited).  A call at a
 // lower level reads fewer limbs of the same key (dimB shrinks with q_l, :51): the resident copy serves every prefix of itself, checked
 // over just the limbs in use -- one copy per key, not one per level.  For a key that is resident the fingerprint is computed by the host
-// threads WHILE the device works with the resident copy (they would wait for it otherwise: resident_key / key_still_valid; a mismatch
+// threads WHILE the device works with the resident copy (they would wait for it otherwise: resident_key, CallKey in shim_call.hpp; a mismatch
 // repeats the device work with the fresh key); for a new key, next to the ciphertext conversions.  gpq_mpi_shim_set_key_check(0) goes
 // back to ~1000 sampled words (of the exact length in use) for callers that never edit a key in place.
 struct KeySlot { const uint64_t *h0, *h1; unsigned limbs, n; bool full; std::vector<uint64_t> print; void *d0, *d1; size_t cap_words; uint64_t used; };
@@ -62,10 +62,6 @@ KeySlot *resident_key(const KeyPrint &kp) {
   for (KeySlot &k : g_keys)
     if (kp.covered_by(k)) { k.used = ++g_key_clock; return &k; }
   return nullptr;
-}
-bool key_still_valid(KeySlot *slot, KeyPrint &kp) {
-  if (kp.parts < 2) kp.task(0); else workers().run(kp.parts, kp.task);
-  return kp.matches(*slot);
 }
 
 void key_on_device(const KeyPrint &kp, uint64_t **d0, uint64_t **d1) {

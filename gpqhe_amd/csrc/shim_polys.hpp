@@ -1,4 +1,4 @@
-// shim_polys.hpp -- resident polynomials: the device keeps the slab of every polynomial it has read or written; Operands = the speculation protocol of one call.
+// shim_polys.hpp -- resident polynomials: the device keeps the slab of every polynomial it has read or written; Operands = the operands of one call under the speculation protocol (the call itself: StagedCall, shim_call.hpp).
 // Part of the MPI-typed surface: one translation unit (mpi_shim.hip includes these fragments in order); split by concern in round 4.
 #pragma once
 
@@ -72,7 +72,7 @@ void remember_poly(const poly_mpi_t *p, unsigned n, unsigned W, uint64_t print, 
 // The polynomial operands of one MPI-typed call.  prepare(): an operand with a trusted resident copy is taken from it (x[i] = the kept slab,
 // nothing converted yet); the others are converted and uploaded as ever (x[i] = the call's own buffers) and remembered.  After the device
 // work is queued, recheck() converts and fingerprints the caller's integers of the operands that were taken from their copies; those that
-// differ are uploaded from the rows just staged, x[i] moves to the call's own buffer, and the caller queues the device work again.
+// differ are uploaded from the rows just staged, x[i] moves to the call's own buffer, and the caller (StagedCall::run) queues the device work again.
 struct Operands {
   int count; unsigned n, W, nt; bool cache, resident = false; unsigned kept = 0 /* operands served from their resident copies */, misfits = 0;
   const poly_mpi_t *const *src; const DevBuf *const *dst; const HostBuf *const *stage;

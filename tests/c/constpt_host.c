@@ -139,6 +139,13 @@ static void counters(const char *step)
   last_taken = t; last_fell = f;
 }
 
+static void poly_stats(const char *when)
+{
+  uint64_t confirmed = 0, changed = 0;
+  gpq_mpi_shim_poly_stats(&confirmed, &changed);
+  printf("poly stats %s: resident %u confirmed %llu changed %llu\n", when, gpq_mpi_shim_resident_polys(), (unsigned long long)confirmed, (unsigned long long)changed);
+}
+
 /* one step on the twins: x with the constant path on, y with it off */
 #define STEP(name, onx, ony)                                         \
   do {                                                               \
@@ -189,6 +196,11 @@ static int run_check(unsigned logn, unsigned logq, int odd, int print)
   /* he_addpt / he_subpt */
   pt_const(&pt, 1l << 30, 0);
   STEP("he_addpt real", he_addpt(&x, &x, &pt), he_addpt(&y, &y, &pt));
+  /* one coefficient of c0 edited behind the library's back, the same on both twins: where x is resident the constant path starts from the
+   * kept copies, the recheck finds the edit and the one launch runs again (`poly stats` lines around that call) */
+  set_si(x.c0.coeffs[n / 3], -12345); set_si(y.c0.coeffs[n / 3], -12345);   /* centred at every level */
+  pt_const(&pt, (7l << 27) + 3, -5);
+  STEP("he_mulpt const after a host edit", poly_stats("before the edited call"); he_mulpt(&x, &x, &pt); poly_stats("after the edited call"), he_mulpt(&y, &y, &pt));
   pt_const(&pt, -77, (1l << 62) + 5);
   STEP("he_subpt complex", he_subpt(&x, &x, &pt), he_subpt(&y, &y, &pt));
   STEP("he_addpt complex", he_addpt(&dx, &x, &pt), he_addpt(&dy, &y, &pt); ct_set(&x, &dx); ct_set(&y, &dy));

@@ -1,7 +1,8 @@
 /* dcd_host.c -- gpq_shim_he_dec_dcd (include/gpqhe_hip_compat.h) with real libgcrypt MPIs: he_dec followed by he_dcd with the plaintext
  * staying on the device, against the shim's he_dec followed by the host program's own decoder.
  *
- *   dcd_host check <logn> <logq> <slots>      the doubles of both routes, bit for bit, twice (the second time everything is resident), and
+ *   dcd_host check <logn> <logq> <slots>      the doubles of both routes, bit for bit, twice (the second time everything is resident), a
+ *                                             third time after a host-side edit of c1 (`poly stats` lines around the device route), and
  *                                             he_dec alone afterwards still gives the same integers
  *   dcd_host fallback <logn> <logq> <slots>   q = 2^logq - 159, no power of two: the call returns 0 and leaves m untouched
  *   dcd_host time <logn> <logq> <slots> <iterations>
@@ -31,6 +32,7 @@ MPI gcry_mpi_set_ui(MPI w, unsigned long u);
 void gcry_mpi_lshift(MPI x, MPI a, unsigned int n);
 void gcry_mpi_sub(MPI w, MPI u, MPI v);
 void gcry_mpi_sub_ui(MPI w, MPI u, unsigned long v);
+void gcry_mpi_add_ui(MPI w, MPI u, unsigned long v);
 void gcry_mpi_neg(MPI w, MPI u);
 void gcry_mpi_mod(MPI r, MPI dividend, MPI divisor);
 void gcry_mpi_rshift(MPI x, MPI a, unsigned int n);
@@ -169,6 +171,13 @@ static int same_doubles(const _Complex double *a, const _Complex double *b, unsi
   return 0;
 }
 
+static void poly_stats(const char *when)
+{
+  uint64_t confirmed = 0, changed = 0;
+  gpq_mpi_shim_poly_stats(&confirmed, &changed);
+  printf("poly stats %s: resident %u confirmed %llu changed %llu\n", when, gpq_mpi_shim_resident_polys(), (unsigned long long)confirmed, (unsigned long long)changed);
+}
+
 static int check(unsigned slots)
 {
   struct he_pt pt, pt2;
@@ -182,6 +191,17 @@ static int check(unsigned slots)
     expect(rc == 1, round ? "again: gpq_shim_he_dec_dcd returns 1" : "gpq_shim_he_dec_dcd returns 1");
     bad |= same_doubles(zb, za, slots, round ? "again, everything resident: device decode against he_dec + host decode" : "device decode against he_dec + host decode");
   }
+  /* a third round with one coefficient of c1 edited behind the library's back.  The device route goes FIRST: it starts from the kept
+   * copies, its recheck finds the edit and the device work runs again (a polynomial found changed is not trusted by the call after) */
+  gcry_mpi_add_ui(ct.c1.coeffs[polyctx.n / 3], ct.c1.coeffs[polyctx.n / 3], 1);
+  memset(zb, 0x5a, slots * sizeof *zb);
+  poly_stats("before the edited call");
+  const int rc3 = gpq_shim_he_dec_dcd(zb, &ct, &sk);
+  poly_stats("after the edited call");
+  expect(rc3 == 1, "after a host edit: gpq_shim_he_dec_dcd returns 1");
+  he_dec(&pt, &ct, &sk);
+  decode(za, &pt);
+  bad |= same_doubles(zb, za, slots, "after a host edit: device decode against he_dec + host decode");
   expect(memcmp(&pt.nu, &ct.nu, 8) == 0, "he_dec copies nu");
   he_dec(&pt2, &ct, &sk);
   unsigned differ = 0, nonzero = 0;

@@ -1,7 +1,8 @@
 /* gemv_host.c -- he_gemv / he_sum / he_idx (src/he-algo.c:47-113) through the reference's signatures with real libgcrypt MPIs, against the
  * reference's loop spelled here over the library's per-call he_copy_ct / he_rot / he_mulpt / he_add / he_rs.
  *
- *   gemv_host check <logn> <logq> <slots> <odd>   every coefficient, l, and the bits of nu and B equal; odd = 1: q = 2^logq - 1 (the fallback)
+ *   gemv_host check <logn> <logq> <slots> <odd>   every coefficient, l, and the bits of nu and B equal; odd = 1: q = 2^logq - 1 (the fallback);
+ *                                                 he_gemv also after a host-side edit of its operand (`poly stats` lines around that call)
  *   gemv_host gemvtime <logn> <logq> <slots>      wall time of he_gemv against the loop (conversions and copies included)
  *   gemv_host ref <path> <logn> <logq> <slots>    the same MPIs through the reference built into oracle/_ref/ (dlopen) and through this library;
  *                                                 `refonly <path> ..`: the reference alone; `ref - <ecd file> ..`: this library alone (see refmode)
@@ -27,6 +28,7 @@ void gcry_mpi_release(MPI a);
 MPI gcry_mpi_set_ui(MPI w, unsigned long u);
 void gcry_mpi_lshift(MPI x, MPI a, unsigned int n);
 void gcry_mpi_sub_ui(MPI w, MPI u, unsigned long v);
+void gcry_mpi_add_ui(MPI w, MPI u, unsigned long v);
 void gcry_mpi_sub(MPI w, MPI u, MPI v);
 void gcry_mpi_neg(MPI w, MPI u);
 void gcry_mpi_mod(MPI r, MPI dividend, MPI divisor);
@@ -136,6 +138,13 @@ static int same(const he_ct_t *a, const he_ct_t *b, const char *what)
 static he_evk_t *rk, rlk, ck;
 static he_ct_t ct;
 
+static void poly_stats(const char *when)
+{
+  uint64_t confirmed = 0, changed = 0;
+  gpq_mpi_shim_poly_stats(&confirmed, &changed);
+  printf("poly stats %s: resident %u confirmed %llu changed %llu\n", when, gpq_mpi_shim_resident_polys(), (unsigned long long)confirmed, (unsigned long long)changed);
+}
+
 static void setup(unsigned logn, unsigned logq, unsigned slots, int odd)
 {
   MPI q = gcry_mpi_new(0);
@@ -197,6 +206,16 @@ static int check(unsigned slots)
   he_gemv(&got, A, &ct, rk);
   ref_gemv(&want, A, &ct, rk);
   bad |= same(&got, &want, "he_gemv");
+  /* one coefficient of c0 edited behind the library's back: where ct is resident the call starts from the kept copy, the recheck finds
+   * the edit and the device work runs a second time on the integers as they are now */
+  he_ct_t got2;
+  ct_alloc(&got2);
+  gcry_mpi_add_ui(ct.c0.coeffs[polyctx.n / 3], ct.c0.coeffs[polyctx.n / 3], 1);
+  poly_stats("before the edited call");
+  he_gemv(&got2, A, &ct, rk);
+  poly_stats("after the edited call");
+  ref_gemv(&want, A, &ct, rk);
+  bad |= same(&got2, &want, "he_gemv after a host edit");
   for (unsigned i = 0; i < slots; i++) S[i] = 1;
   he_sum(&got, &ct, rk);
   ref_gemv(&want, S, &ct, rk);

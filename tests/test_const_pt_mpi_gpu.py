@@ -10,6 +10,7 @@ import pytest
 
 from oracle import bigint_ref as ref
 from tests import const_pt_cases as cp
+from tests.poly_stats import edited_call_movement
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -27,7 +28,7 @@ def host(tmp_path_factory):
 
 # step -> (calls that took the constant path, he_mulpt calls among them that fell back)
 STEPS = [("he_mulpt real", 1, 0), ("he_rs real", 0, 0), ("he_mulpt negative", 1, 0), ("he_rs negative", 0, 0), ("he_mulpt complex", 1, 0),
-         ("he_rs complex", 0, 0), ("he_addpt real", 1, 0), ("he_subpt complex", 1, 0), ("he_addpt complex", 1, 0), ("he_mulpt dense", 0, 0),
+         ("he_rs complex", 0, 0), ("he_addpt real", 1, 0), ("he_mulpt const after a host edit", 1, 0), ("he_subpt complex", 1, 0), ("he_addpt complex", 1, 0), ("he_mulpt dense", 0, 0),
          ("he_addpt dense", 0, 0), ("he_mulpt nearly sparse", 0, 0), ("he_subpt nearly sparse", 0, 0), ("he_mulpt nearly sparse at the end", 0, 0),
          ("he_addpt wide constant", 0, 0), ("he_mulpt non-centred", 1, 1), ("he_mulpt centred again", 1, 0)]
 
@@ -54,6 +55,11 @@ def test_switch_on_and_off_agree_and_the_counters_tell(host, oracle_ctx, logn, l
         assert "ok " + name in lines, name
         assert got[name] == (taken, fell), (name, got[name])
     assert "ok he_mulpt complex leaves its source" in lines
+    resident, confirmed, changed = edited_call_movement(lines)
+    assert (resident > 0) == (logn >= 12), [x for x in lines if x.startswith("poly stats")]
+    if resident:
+        # as printed by the build before the staged-call driver: c0 (edited) found changed, c1 confirmed
+        assert (confirmed, changed) == (1, 1), [x for x in lines if x.startswith("poly stats")]
     if logn != 8:
         return
     # the first product, integer by integer, against the restated reference with the plaintext as a dense polynomial
