@@ -111,6 +111,15 @@ SIGNATURES = {
     "gpq_he_mulpt_const_fits": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_uint, C.c_uint]),
     "gpq_he_mulpt_const": (C.c_int, [vp] * 5 + [C.c_int64, C.c_int64] + [C.c_uint] * 5 + [vp, vp]),
     "gpq_he_addpt_const": (C.c_int, [vp] * 5 + [C.c_int64, C.c_int64, C.c_int] + [C.c_uint] * 3 + [vp]),
+    # include/gpqhe_hip_algo.h
+    "gpq_he_lin_const": (C.c_int, [vp, vp, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int), C.c_uint, C.c_int64, C.c_int64] + [C.c_uint] * 3 + [vp]),
+    "gpq_he_algo_depth": (C.c_int, [C.c_int, C.c_uint]),
+    "gpq_he_algo_workspace_bytes": (C.c_size_t, [vp, C.c_int] + [C.c_uint] * 6),
+    "gpq_he_inv": (C.c_int, [vp] * 7 + [C.c_uint] * 6 + [vp, vp]),
+    "gpq_he_sqrt": (C.c_int, [vp] * 7 + [C.c_uint] * 6 + [vp, vp]),
+    "gpq_he_sigmoid": (C.c_int, [vp] * 7 + [C.c_uint] * 5 + [vp, vp]),
+    "gpq_he_log": (C.c_int, [vp] * 7 + [C.c_uint] * 5 + [vp, vp]),
+    "gpq_he_exp": (C.c_int, [vp] * 6 + [C.c_uint, vp, vp] + [C.c_uint] * 6 + [vp, vp]),
     "gpq_poly_rot": (C.c_int, [vp, vp, vp, C.c_uint, C.c_uint, C.c_uint, vp]),
     "gpq_poly_conj": (C.c_int, [vp, vp, vp, C.c_uint, C.c_uint, vp]),
     "gpq_he_general_workspace_bytes": (C.c_size_t, [vp, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_uint]),
@@ -236,6 +245,8 @@ EXPORTED_ONLY = ["montgomery_reduce", "barrett_reduce",
                  # MPI-typed surface: driven from C with real libgcrypt MPIs (tests/c/mpi_host.c)
                  "rns_decompose", "rns_reconstruct", "poly_rns2mpi", "poly_mul", "he_mul", "he_rs", "he_rescale", "he_moddown", "he_mulpt", "he_add", "he_sub", "he_addpt", "he_subpt", "he_neg", "he_copy_ct", "he_dec", "he_enc_pk", "he_enc_sk", "he_keypair", "he_conj", "he_rot", "he_genrlk", "he_genck", "he_genrk",
                  "he_gemv", "he_sum", "he_idx",
+                 # the evaluators of src/he-algo.c:131-458 on the reference's types (tests/c/algo_host.c)
+                 "gpq_shim_he_inv", "gpq_shim_he_sqrt", "gpq_shim_he_sigmoid", "gpq_shim_he_log", "gpq_shim_he_exp",
                  ]
 # libgpqhe_hip_ctx.so (ctx_compat.hip): context construction / storage names for hosts that are not GPQHE; driven from C
 CTX_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libgpqhe_hip_ctx.so")

@@ -8,6 +8,7 @@
 #include "bridge_stream.hpp"
 #include "genswk_kernels.hpp"
 #include "constpt_kernels.hpp"
+#include "algo_kernels.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -899,3 +900,4 @@ extern "C" int gpq_he_genswk(gpq_ctx *c, uint64_t *evk0, uint64_t *evk1, const u
 }
 
 #include "bridge_genswk.hpp"   // gpq_he_genswk_batch: `count` keys per call through the CRT split of P 2^k (genswk_crt_tail)
+#include "bridge_algo.hpp"     // the evaluators of src/he-algo.c:131-458: gpq_he_lin_const, gpq_he_inv / _sqrt / _sigmoid / _log / _exp

@@ -430,7 +430,7 @@ static const char *const kKernelNames[GPQ_K_COUNT] = {"strided_fwd", "strided_in
                                                       "bridge_relin_tail_direct", "bridge_crt_decompose", "bridge_tail_stream",
                                                       "keyswitch_rot_mid", "automorphism_gather", "gemv_mac", "he_ecd_lds", "he_dcd_lds",
                                                       "sample_bytes", "enc_small_tail", "genswk_crt_tail", "surf_stream", "gemv_mac_multi",
-                                                      "he_mulpt_const", "he_addpt_const"};
+                                                      "he_mulpt_const", "he_addpt_const", "he_lin_const"};
 
 int check_shape(const gpq_ctx *c, unsigned dim, unsigned batch, const char *who) {
   if (!c) return gpq_fail(GPQ_ERR_INVALID, "%s: null context", who);

@@ -100,7 +100,9 @@ enum { GPQ_K_STRIDED_FWD = 0, GPQ_K_STRIDED_INV, GPQ_K_CONTIG_FWD, GPQ_K_CONTIG_
        // gpq_he_gemv_multi: one giant step's inner sums for several plans on the same ciphertexts (gemv_mac_multi)
        GPQ_K_GEMV_MAC_MULTI,
        // constant plaintexts (constpt_kernels.hpp): he_mulpt [+ he_rs] and he_addpt / he_subpt by a + b x^(n/2) as one pass over the big slabs
-       GPQ_K_MULPT_CONST, GPQ_K_ADDPT_CONST, GPQ_K_COUNT };
+       GPQ_K_MULPT_CONST, GPQ_K_ADDPT_CONST,
+       // the additive glue of the evaluators (algo_kernels.hpp): up to three signed terms, a constant plaintext and one mpi_smod in one pass
+       GPQ_K_LIN_CONST, GPQ_K_COUNT };
 
 // Constant matrix of the matrix-core CRT fast path for one basis and result width WL (bridge_mfma.hpp)
 struct gpq_recon_mfma {

@@ -46,6 +46,7 @@ extern "C" void randombytes(uint8_t *x, size_t xlen) __attribute__((weak));
 extern "C" void he_ecd(struct he_pt *pt, const _Complex double *m) __attribute__((weak));
 
 #include "mpi_convert.hpp"
+#include "algo_seq.hpp"         // the evaluators' sequences and their host bookkeeping (shim_evaluators.hpp)
 
 // Every copy, kernel and event of the MPI-typed calls goes to the legacy null stream (stream argument nullptr), from the calling thread and
 // from the conversion threads alike: that ONE stream is what orders a range's upload before the transposes and kernels that read it, and a
@@ -393,6 +394,7 @@ void he_mulpt(struct he_ct *dest, const struct he_ct *src, const struct he_pt *p
 #include "shim_additive.hpp"
 #include "shim_keygen.hpp"
 #include "shim_algo.hpp"
+#include "shim_evaluators.hpp"
 
 }  // extern "C"
 

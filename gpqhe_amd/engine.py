@@ -362,6 +362,51 @@ class PolyContext:
         _native.check(self.lib.gpq_he_addpt_const(self.h, self._ptr(out_c0), self._ptr(out_c1), self._ptr(c0), self._ptr(c1), a, b, 1 if sub else 0, W, logql,
                                                   batch, self._stream()), "gpq_he_addpt_const")
 
+    # --- the evaluators of src/he-algo.c:131-458 (include/gpqhe_hip_algo.h) ---
+    ALGO_KINDS = {"inv": 0, "sqrt": 1, "sigmoid": 2, "log": 3, "exp": 4}
+
+    def he_lin_const(self, out_c0, out_c1, terms, W, logql, a=0, b=0):
+        """out = smod(sum of sign * (x_c0, x_c1) over the one to three `terms` (x_c0, x_c1, sign) + (a + b x^(n/2)), 2^logql): the collapsed
+        chain of he_neg / he_add / he_sub / he_addpt / he_subpt / he_moddown / he_copy_ct, one launch; out may be one of the terms."""
+        K = len(terms)
+        batch = terms[0][0].numel() // (W * self.n)
+        x0 = (C.c_void_p * 3)(*[self._ptr(t[0]).value for t in terms])
+        x1 = (C.c_void_p * 3)(*[self._ptr(t[1]).value for t in terms])
+        sg = (C.c_int * 3)(*[int(t[2]) for t in terms])
+        _native.check(self.lib.gpq_he_lin_const(self.h, self._ptr(out_c0), self._ptr(out_c1), x0, x1, sg, K, a, b, W, logql, batch, self._stream()),
+                      "gpq_he_lin_const")
+
+    def he_algo_depth(self, kind, iter=0):
+        return int(self.lib.gpq_he_algo_depth(self.ALGO_KINDS[kind], iter))
+
+    def he_algo_workspace_bytes(self, kind, W, logqL, logql, logDelta, iter, batch):
+        """bytes of an evaluator call's workspace; 0 when the call would be refused"""
+        return int(self.lib.gpq_he_algo_workspace_bytes(self.h, self.ALGO_KINDS[kind], W, logqL, logql, logDelta, iter, batch))
+
+    def he_algo_call(self, kind, out_c0, out_c1, c0, c1, rlk0, rlk1, W, logqL, logql, logDelta, iter, workspace, m=None, dimpt=0):
+        """the return code of gpq_he_<kind> on a caller-owned workspace (tests look at refusals and at the workspace's end)"""
+        batch = c0.numel() // (W * self.n)
+        head = [self.h, self._ptr(out_c0), self._ptr(out_c1), self._ptr(c0), self._ptr(c1)]
+        keys = [self._ptr(rlk0), self._ptr(rlk1)]
+        tail = [batch, self._ptr(workspace), self._stream()]
+        if kind == "exp":
+            return self.lib.gpq_he_exp(*head, self._ptr(m), dimpt, *keys, W, logqL, logql, logDelta, iter, *tail)
+        if kind in ("inv", "sqrt"):
+            return getattr(self.lib, "gpq_he_" + kind)(*head, *keys, W, logqL, logql, logDelta, iter, *tail)
+        return getattr(self.lib, "gpq_he_" + kind)(*head, *keys, W, logqL, logql, logDelta, *tail)
+
+    def he_algo(self, kind, out_c0, out_c1, c0, c1, rlk0, rlk1, W, logqL, logql, logDelta, iter=0, m=None, dimpt=0):
+        """he_inv / he_sqrt / he_sigmoid / he_log / he_exp (kind) of the batch as one call; q_l = 2^logql is the input's modulus, the output's
+        is 2^(logql - depth logDelta).  he_exp: m = he_ecd of the constant vector a / 2^iter (one big slab), dimpt = he_mulpt's limbs."""
+        torch = _torch()
+        batch = c0.numel() // (W * self.n)
+        nbytes = self.he_algo_workspace_bytes(kind, W, logqL, logql, logDelta, iter, batch)
+        if not nbytes:
+            raise _native.GpqError("gpq_he_algo_workspace_bytes: " + self.lib.gpq_last_error().decode())
+        ws = torch.empty(nbytes // 8, dtype=torch.int64, device=self._dev)
+        _native.check(self.he_algo_call(kind, out_c0, out_c1, c0, c1, rlk0, rlk1, W, logqL, logql, logDelta, iter, ws, m, dimpt), "gpq_he_" + kind)
+        return ws
+
     def he_genswk(self, evk0, evk1, p1, sk, e, sp, W, dimP, logqL, dimevk):
         """src/he-kem.c:74-118 from host-sampled p1 / e and the hidden polynomial sp; q_L = 2^logqL."""
         torch = _torch()

@@ -240,6 +240,20 @@ void gpq_mpi_shim_set_device_ecd(int on);
  * the doubles are those of the reference's he_dec + he_dcd on that table, bit for bit.  Returns 1 when done; 0 -- and m untouched -- when q_l
  * is no power of two or there is no ring table: the caller then runs he_dec + he_dcd.  Any slot count up to polyctx.n / 2. */
 int gpq_shim_he_dec_dcd(_Complex double *m, const struct he_ct *ct, const poly_mpi_t *sk);
+/* he_inv, he_sqrt, he_sigmoid, he_log, he_exp (src/he-algo.c:131-458) as ONE staged call each around the evaluators of gpqhe_hip_algo.h: the
+ * source is found resident or uploaded once, the key comes through the key cache, one evaluator call runs the reference's whole sequence on
+ * the device, the result comes down once and is remembered; dst->l / nu / B are the reference's, replayed call for call on the host.  Names of
+ * their own for the reason above: a library-side `he_inv` would shadow GPQHE's.  A GPQHE build forwards under its GPQHE_HIP guard:
+ *     void he_inv(he_ct_t *d, const he_ct_t *s, const he_evk_t *rlk, const unsigned int iter) { if (gpq_shim_he_inv(d, s, rlk, iter)) return; ...its loop... }
+ * Each returns 1 when done and 0 -- dst untouched, the caller runs the reference's loop as before -- when a modulus on the way or Delta is no
+ * power of two, the depth does not fit the source's level (or would end at q = 1), a constant does not pass gpq_he_mulpt_const_fits, a
+ * coefficient of the source is not centred mod q_l (counted on the device), or, for he_exp, the host program provides no he_ecd (its one
+ * plaintext is encoded by the host's own, as he_gemv's diagonals are).  dst may be src. */
+int gpq_shim_he_inv(he_ct_t *dst, const he_ct_t *src, const he_evk_t *rlk, unsigned iter);
+int gpq_shim_he_sqrt(he_ct_t *dst, const he_ct_t *src, const he_evk_t *rlk, unsigned iter);
+int gpq_shim_he_sigmoid(he_ct_t *dst, const he_ct_t *src, const he_evk_t *rlk);
+int gpq_shim_he_log(he_ct_t *dst, const he_ct_t *src, const he_evk_t *rlk);
+int gpq_shim_he_exp(he_ct_t *dst, _Complex double a, const he_ct_t *src, const he_evk_t *rlk, unsigned iter);
 /* How a resident key is recognised: by the caller's two pointers and a fingerprint of EVERY word, limb by limb (full != 0, the
  * default: a key edited in place multiplies as edited, like the reference, which reads its key on every call), computed by the
  * conversion threads while the device works; a call at a lower level, which reads fewer limbs of the same key (src/he-mult.c:51),
