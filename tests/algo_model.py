@@ -17,6 +17,27 @@ from oracle import bigint_ref as br
 
 KINDS = ("inv", "sqrt", "sigmoid", "log", "exp")
 
+# The slab shapes the evaluators are pinned at away from (logn 7, q_L = 2^200, Delta = 2^30, the top level, W = 4):
+# cell -> (logn, logqL, logDelta, levels below the top the input sits at, W, batch, [(kind, iter)]).  tests/test_algo_model.py runs the collapse at every
+# one without a device, tests/test_he_algo_shapes_gpu.py the library.
+SLAB_SHAPES = {
+    "A": (7, 200, 30, 2, 4, 2, [("inv", 2), ("sqrt", 2), ("sigmoid", 0), ("log", 0), ("exp", 0)]),   # logql != logqL in every operation; ends at 2^20
+    "B": (7, 200, 20, 2, 4, 2, [("inv", 3), ("sqrt", 3), ("exp", 2)]),                               # a third iteration; another scale
+    "C": (7, 300, 59, 0, 5, 2, [("inv", 1), ("sqrt", 1), ("sigmoid", 0), ("log", 0), ("exp", 0)]),   # constants next to INT64_MAX; depth 4 ends at 2^64
+    "D": (7, 200, 4, 40, 1, 2, [("log", 0), ("inv", 2), ("sigmoid", 0)]),                            # W = 1; constants that round to 0
+    "E1": (7, 438, 30, 0, 7, 2, [("sigmoid", 0), ("inv", 2)]),                                       # 8/16/24 limbs, fewer with every level
+    "E2": (7, 438, 30, 8, 4, 2, [("log", 0), ("exp", 1)]),                                           # P sized for q_L far above q_l = 2^198
+    "F": (7, 850, 30, 0, 14, 2, [("inv", 1)]),                                                       # a 16-word P
+    "G": (13, 200, 30, 1, 4, 3, [("sqrt", 1), ("log", 0)]),                                          # a two-pass ring below the top
+}
+
+
+def primes_for(logn, logq):
+    """an upper bound of dimevk (src/precomp.c:407) for q_L = 2^logq that needs no prime: the chain's primes have at most 60 bits, so P has at
+    most 60 per limb.  A probe context of this many primes (at least the 12 every other test probes with) answers gpq_he_dims for the shape."""
+    dimP = (logq + 1 + logn) // 59 + 1
+    return max(12, ((logq + 1) + (60 * dimP + logq + 1) + logn) // 59 + 1)
+
 
 def depth(kind, iter=0):
     return {"inv": iter + 1, "sqrt": 2 * iter, "sigmoid": 4, "log": 4, "exp": 4 + iter}[kind]
@@ -279,6 +300,7 @@ class LazyOps(BigintOps):
     def __init__(self, *args, **kw):
         BigintOps.__init__(self, *args, **kw)
         self.most_terms = 0
+        self.sums = 0                                       # sums that were materialised: each is at most one gpq_he_lin_const of an evaluator
 
     def _lin(self, ct):
         return ct.c if isinstance(ct.c, Lin) else Lin([(1, ct.c)], 0)
@@ -287,6 +309,7 @@ class LazyOps(BigintOps):
         if isinstance(ct.c, Lin):
             lin, q, n = ct.c, self.q(ct.l), self.n
             self.most_terms = max(self.most_terms, len(lin.terms))
+            self.sums += 1
             c0 = [br.mpi_smod(sum(s * c[0][i] for s, c in lin.terms) + (lin.a if i == 0 else 0), q) for i in range(n)]
             c1 = [br.mpi_smod(sum(s * c[1][i] for s, c in lin.terms), q) for i in range(n)]
             ct.c = (c0, c1)

@@ -3,6 +3,8 @@
  * symbols (he_mul, he_rs, he_mulpt, he_addpt, ...) in the same program.
  *
  *   algo_host check <logn> <logq> <all>   q = 2^logq, Delta = 2^30; all = 0: he_inv and he_sqrt with one iteration, 1: all five
+ *   algo_host check_at <logn> <logq> <logDelta> <down> <all>   the same with Delta = 2^logDelta on a source brought `down` levels below the top
+ *                                         by this program's own he_moddown (centred mod q_l, l < L), and he_sigmoid once more in place
  *   algo_host refuse <logn> <logq>        the 0 returns: a depth that does not fit, a source that is not centred
  *   algo_host odd <logn> <logq>           ... and q = 2^logq - 1: no modulus on the way is a power of two
  *   algo_host time <logn> <logq> <logDelta> <rounds>   he_inv's call sequence over the per-call symbols against ONE gpq_shim_he_inv, wall time
@@ -295,16 +297,21 @@ static void loop(int kind, he_ct_t *dst, const he_ct_t *src, unsigned iter)
   }
 }
 
-static int run_check(unsigned logn, unsigned logq, int all)
+static int run_check(unsigned logn, unsigned logq, unsigned logdelta, unsigned down, int all)
 {
   he_ct_t ct, x, y, keep;
+  LOGDELTA = logdelta;
   setup(logn, logq, 0, &ct);
+  if (down >= hectx.L) { printf("FAIL %u levels down from L = %u\n", down, hectx.L); return 1; }
+  for (unsigned d = 0; d < down; d++) he_moddown(&ct);          /* l < L: Bmult[l], q_l and the limb counts are no longer the top's */
+  printf("source at l %u of L %u\n", ct.l, hectx.L);
   ct_alloc(&x); ct_alloc(&y); ct_alloc(&keep);
   int bad = 0;
   he_copy_ct(&keep, &ct);                                     /* a first call on ct: where polynomials are kept resident, ct is from here on */
   he_mul(&x, &ct, &ct, &rlk);                                 /* ... and a first product: the key is on the device (a call with a key that is not takes no operand from its copy) */
   for (int kind = 0; kind < (all ? 5 : 2); kind++) {
-    const unsigned iter = kind == 2 || kind == 3 ? 0 : 1;
+    unsigned iter = kind == 2 || kind == 3 ? 0 : 1;
+    if (kind == 4 && (ct.l < 5 || gcry_mpi_get_nbits(hectx.q[ct.l - 5]) < 2)) iter = 0;   /* he_exp takes 4 + iter levels, and q = 1 is no level */
     char what[64];
     stats(NAMES[kind], "before");
     const unsigned e0 = ecd_calls;
@@ -321,6 +328,11 @@ static int run_check(unsigned logn, unsigned logq, int all)
       if (gpq_shim_he_inv(&x, &x, &rlk, 2) != 1) { printf("FAIL he_inv in place did not run\n"); bad = 1; continue; }
       loop_inv(&y, &ct, 2);
       bad |= same(&x, &y, "he_inv in place, two iterations");
+    }
+    if (kind == 2 && down) {                                  /* in place once more, below the top */
+      ct_set(&x, &ct);
+      if (gpq_shim_he_sigmoid(&x, &x, &rlk) != 1) { printf("FAIL he_sigmoid in place did not run\n"); bad = 1; continue; }
+      bad |= same(&x, &y, "he_sigmoid in place");
     }
   }
   return bad;
@@ -413,9 +425,10 @@ static int run_time(unsigned logn, unsigned logq, unsigned logdelta, int rounds)
 int main(int argc, char **argv)
 {
   if (argc >= 6 && !strcmp(argv[1], "time")) return run_time(atoi(argv[2]), atoi(argv[3]), atoi(argv[4]), atoi(argv[5]));
-  if (argc >= 5 && !strcmp(argv[1], "check")) return run_check(atoi(argv[2]), atoi(argv[3]), atoi(argv[4]));
+  if (argc >= 5 && !strcmp(argv[1], "check")) return run_check(atoi(argv[2]), atoi(argv[3]), 30, 0, atoi(argv[4]));
+  if (argc >= 7 && !strcmp(argv[1], "check_at")) return run_check(atoi(argv[2]), atoi(argv[3]), atoi(argv[4]), atoi(argv[5]), atoi(argv[6]));
   if (argc >= 4 && !strcmp(argv[1], "refuse")) return run_refuse(atoi(argv[2]), atoi(argv[3]));
   if (argc >= 4 && !strcmp(argv[1], "odd")) return run_odd(atoi(argv[2]), atoi(argv[3]));
-  fprintf(stderr, "usage: algo_host check <logn> <logq> <all> | refuse <logn> <logq> | odd <logn> <logq> | time <logn> <logq> <logDelta> <rounds>\n");
+  fprintf(stderr, "usage: algo_host check <logn> <logq> <all> | check_at <logn> <logq> <logDelta> <down> <all> | refuse <logn> <logq> | odd <logn> <logq> | time <logn> <logq> <logDelta> <rounds>\n");
   return 2;
 }

@@ -54,6 +54,26 @@ def test_one_call_equals_the_loop_over_the_per_call_symbols(host, logn, logq, al
     assert "ok he_inv in place, two iterations" in lines
 
 
+# below the top level and at another scale: q_l, the limb counts, W and Bmult[l] (a different value per level) are no longer the top's.
+# (8, 120, Delta 2^20, l = 5 of 6: q_0 = 1, so he_exp runs without an iteration and ends at q_1 = 2^20; 13, 200, Delta 2^30, l = 4 of 6: he_exp
+# without an iteration ends at q_0 = 2^20)
+@pytest.mark.parametrize("logn,logq,logdelta,down", [(8, 120, 20, 1), (13, 200, 30, 2)])
+def test_one_call_equals_the_loop_below_the_top_level(host, logn, logq, logdelta, down):
+    lines = _run([host, "check_at", str(logn), str(logq), str(logdelta), str(down), "1"])
+    L = logq // logdelta
+    assert "source at l %d of L %d" % (L - down, L) in lines
+    for name in NAMES:
+        assert "ok " + name in lines and "ok %s leaves its source" % name in lines, name
+        assert "%s returned 1, he_ecd calls %d" % (name, 1 if name == "he_exp" else 0) in lines
+        before, after = _stats(lines, name, "before"), _stats(lines, name, "after")
+        if logn >= 12:
+            assert after[1] - before[1] == 2 and after[2] == before[2], (name, before, after)
+            assert after[0] >= before[0] >= 2, (name, before, after)
+        else:
+            assert before[0] == after[0] == 0
+    assert "ok he_inv in place, two iterations" in lines and "ok he_sigmoid in place" in lines
+
+
 def test_the_zero_returns_leave_dst_untouched(host):
     lines = _run([host, "refuse", "8", "120"])
     for name in ("he_inv", "he_sqrt", "he_exp"):
