@@ -120,6 +120,12 @@ SIGNATURES = {
     "gpq_he_sigmoid": (C.c_int, [vp] * 7 + [C.c_uint] * 5 + [vp, vp]),
     "gpq_he_log": (C.c_int, [vp] * 7 + [C.c_uint] * 5 + [vp, vp]),
     "gpq_he_exp": (C.c_int, [vp] * 6 + [C.c_uint, vp, vp] + [C.c_uint] * 6 + [vp, vp]),
+    "gpq_he_lin_pt": (C.c_int, [vp, vp, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int), C.c_uint, vp, C.c_int, C.c_int64, C.c_int64] + [C.c_uint] * 3 + [vp]),
+    "gpq_he_cmp_rounds": (C.c_int, [C.c_uint]),
+    "gpq_he_cmp_depth": (C.c_int, [C.c_uint, C.c_uint]),
+    "gpq_he_cmp_workspace_bytes": (C.c_size_t, [vp, C.c_int] + [C.c_uint] * 7),
+    "gpq_he_cmp": (C.c_int, [vp] * 9 + [C.c_uint] * 7 + [vp, vp]),
+    "gpq_he_cmppt": (C.c_int, [vp] * 8 + [C.c_uint] * 7 + [vp, vp]),
     "gpq_poly_rot": (C.c_int, [vp, vp, vp, C.c_uint, C.c_uint, C.c_uint, vp]),
     "gpq_poly_conj": (C.c_int, [vp, vp, vp, C.c_uint, C.c_uint, vp]),
     "gpq_he_general_workspace_bytes": (C.c_size_t, [vp, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_uint]),
@@ -247,6 +253,8 @@ EXPORTED_ONLY = ["montgomery_reduce", "barrett_reduce",
                  "he_gemv", "he_sum", "he_idx",
                  # the evaluators of src/he-algo.c:131-458 on the reference's types (tests/c/algo_host.c)
                  "gpq_shim_he_inv", "gpq_shim_he_sqrt", "gpq_shim_he_sigmoid", "gpq_shim_he_log", "gpq_shim_he_exp",
+                 # he_cmp / he_cmppt (:460-548) likewise (tests/c/cmp_host.c)
+                 "gpq_shim_he_cmp", "gpq_shim_he_cmppt",
                  ]
 # libgpqhe_hip_ctx.so (ctx_compat.hip): context construction / storage names for hosts that are not GPQHE; driven from C
 CTX_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libgpqhe_hip_ctx.so")

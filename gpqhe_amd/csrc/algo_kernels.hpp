@@ -8,6 +8,9 @@
 // Big slabs are word-major (word j of coefficient i at j n + i): one lane per coefficient, so every word plane a wavefront touches is one contiguous
 // run of 8-byte words, and one carry chain over the words.  A lane reads word j of every term before it writes word j of its own coefficient and
 // touches no other coefficient, so out may be any of the inputs in the same position.  No workspace, no LDS.
+// PT (gpq_he_lin_pt): he_addpt / he_subpt by ONE dense plaintext m (src/he-add.c:80-123) is one more addend of c0's chain,
+//   out.c0 = smod(.. + msign m + (a + b x^h), 2^logql),
+// m a W-word big slab of one polynomial shared by the whole batch and read by the c0 half of the grid only.
 #pragma once
 #include "constpt_kernels.hpp"   // centre_word
 namespace gpq {
@@ -18,10 +21,12 @@ struct LinConstArgs {
   int64_t a, b;
   unsigned neg;                   // bit k: s_k = -1
   unsigned W, logn, logql;
+  const uint64_t *m;              // PT: the plaintext, [W][n], no batch stride
+  unsigned mneg;                  // PT: 1 where msign = -1
 };
 
 // Grid y = 2 ciphertext + (0: c0, 1: c1).  -x = ~x + 1 on the words of x: the ones of the negated terms enter as the carry into word 0.
-template <unsigned K>
+template <unsigned K, bool PT = false>
 __global__ __launch_bounds__(256) void he_lin_const(LinConstArgs a) {
   const unsigned n = 1u << a.logn, i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
@@ -38,12 +43,20 @@ __global__ __launch_bounds__(256) void he_lin_const(LinConstArgs a) {
   const int64_t t = c1 ? 0 : i == 0 ? a.a : i == (n >> 1) ? a.b : 0;
   const uint64_t t0 = (uint64_t)t, text = (uint64_t)(t >> 63);
   uint64_t carry = __popc(a.neg & ((1u << K) - 1u)), qsign = 0;           // at most K + 1 afterwards: K + 1 addends and a carry of at most K
+  const bool pt = PT && !c1;                                              // (uniform over the block)
+  const uint64_t *m = PT ? a.m + i : nullptr, mflip = PT ? 0 - (uint64_t)a.mneg : 0;
+  if (pt) carry += a.mneg;                                                // PT: one addend and one unit of carry more, K + 2
   for (unsigned j = 0; j < a.W; ++j) {
     const uint64_t y = j ? text : t0;
     uint64_t acc = carry + y, c = acc < y;
 #pragma unroll
     for (unsigned k = 0; k < K; ++k) {
       const uint64_t x = in[k][(size_t)j << a.logn] ^ flip[k];
+      acc += x;
+      c += acc < x;
+    }
+    if (pt) {
+      const uint64_t x = m[(size_t)j << a.logn] ^ mflip;
       acc += x;
       c += acc < x;
     }

@@ -1,10 +1,12 @@
-// algo_seq.hpp -- the evaluators of src/he-algo.c:131-458 (he_inv, he_sqrt, he_sigmoid, he_log, he_exp), each written ONCE as a sequence over four
-// operations on numbered ciphertext slots (slot 0 = the input, the others the reference's named temporaries):
+// algo_seq.hpp -- the evaluators of src/he-algo.c:131-548 (he_inv, he_sqrt, he_sigmoid, he_log, he_exp, he_cmp, he_cmppt), each written ONCE as a
+// sequence over four operations on numbered ciphertext slots (slot 0 = the input, he_cmp's slot 1 = its second input, the others the reference's
+// named temporaries):
 //   mul(d, x, y)      he_mul(&d, &x, &y, rlk); he_rs(&d)                                  src/he-mult.c:88-156, src/he-rescale.c:33-54
 //   mulc(d, x, re)    he_const_pt(&pt, re); he_mulpt(&d, &x, &pt); he_rs(&d)              src/he-encode.c:119-125, src/he-mult.c:159-196
 //   mulpt(d, x)       he_mulpt(&d, &x, &pt) by the call's one dense plaintext; he_rs(&d)  (he_exp, :448-450)
 //   lin(d, terms, ..) a chain of he_copy_ct / he_neg / he_add / he_addpt / he_subpt / he_moddown collapsed into one sum and one mpi_smod at
-//                     the level the chain ends at (algo_kernels.hpp has the argument); terms may sit at higher levels: their he_moddown rides
+//                     the level the chain ends at (algo_kernels.hpp has the argument); terms may sit at higher levels: their he_moddown rides;
+//                     he_cmppt's he_addpt by the call's one dense plaintext is a term of it (msign)
 // plus alias(d, x) -- he_copy_ct of a value that is not written afterwards: a name, no work -- and ret(d), the function's result.
 // Two implementations run the same text.  Book (here) is the host's: it replays l, nu and B call for call as the reference -- and mpi_shim.hip /
 // shim_additive.hpp per call today -- compute them, knows every level's logql, limb counts and constants, and refuses what cannot run before
@@ -58,6 +60,8 @@ struct Book {
   unsigned nops = 0;                                   // operations that write a slot, so far
   int last_dst = -1, result = -1;
   bool last_mul_reads_input = false, uses_m = false;
+  bool two = false;                                    // slot 1 is a second input ciphertext (he_cmp), centred mod 2^logql as slot 0
+  double pt_nu = 0.0;                                  // nu of lin's dense plaintext (he_cmppt's pt->nu); a slab call passes Delta
   size_t ws = 0;
   // what the last operation decided, for the launch behind it
   unsigned dimP = 0, dimA = 0, dimB = 0, dim = 0;
@@ -73,7 +77,10 @@ struct Book {
     if (s < 1 || s > 63) { fail("logDelta outside 1..63"); return; }
     if (logql0 < 1 || logql0 > logqL) { fail("1 <= logql <= logqL"); return; }
     Delta = (double)(1ull << s);
+    pt_nu = Delta;
   }
+  void second_input(double nu, double B) { two = true; v[1] = Val{true, 0, nu, B}; }
+  bool is_input(int slot) const { return slot == 0 || (two && slot == 1); }
   bool fail(const char *w) { if (!err) { err = GPQ_ERR_INVALID; why = w; } return false; }
   unsigned logql(unsigned lv) const { return logql0 - lv * s; }
   unsigned lv(int slot) const { return v[slot].lv; }
@@ -103,8 +110,24 @@ struct Book {
     const double nu1 = d == x ? nu : v[x].nu, nu2 = d == y ? nu : v[y].nu;
     const double B = nu1 * v[y].B + nu2 * v[x].B + v[x].B * v[y].B + (Bmult ? Bmult[l0 - level] : 0.0);
     rescaled(d, level, nu, B);
-    wrote(d, x == 0 || y == 0);
+    wrote(d, is_input(x) || is_input(y));
     return true;
+  }
+  // x = x^2 and y = y^2, two independent squarings at one level (he_cmp_core's an^2 and bn^2): the bookkeeping of the two he_mul + he_rs in the
+  // reference's order; on the device ONE product over 2 batch ciphertexts, so the products' workspace is sized for that
+  bool sq2(int x, int y) {
+    if (err) return false;
+    if (batch > 16383) return fail("he_cmp: a round squares 2 batch ciphertexts at once: batch <= 16383");
+    const bool was = sizing;
+    sizing = false;
+    const bool ok = mul(x, x, x) && mul(y, y, y);
+    sizing = was;
+    if (ok && sizing) {
+      const size_t b = gpq_he_mul_workspace_bytes(c, W, dimA, dimB, dimP, 2 * batch);     // (dims: the level both were at)
+      if (!b) return fail("gpq_he_mul_workspace_bytes refuses the shape");
+      if (b > ws) ws = b;
+    }
+    return ok;
   }
   bool mulc(int d, int x, double re) {
     if (err) return false;
@@ -135,8 +158,9 @@ struct Book {
     return true;
   }
   // d = sum of sign * term [+ csign * he_const_pt(re)] at level lv_out; nu: the running maximum of he_add / he_addpt (src/he-add.c:37, :84), B: the
-  // running sum of he_add (:38), both in the order of the terms; he_neg, he_moddown and he_copy_ct leave them alone
-  bool lin(int d, const Term *t, unsigned K, unsigned lv_out, bool has_c = false, double re = 0.0, int csign = 1) {
+  // running sum of he_add (:38), both in the order of the terms; he_neg, he_moddown and he_copy_ct leave them alone.  msign != 0: he_addpt (+1) /
+  // he_subpt (-1) of the call's one dense plaintext after the terms: nu the larger of the sum's and pt->nu, B the sum's (:84-85)
+  bool lin(int d, const Term *t, unsigned K, unsigned lv_out, bool has_c = false, double re = 0.0, int csign = 1, int msign = 0) {
     if (err) return false;
     if (K < 1 || K > 3) return fail("he_add: one to three terms");
     double nu = 0, B = 0;
@@ -147,6 +171,7 @@ struct Book {
       B = k ? B + x.B : x.B;
     }
     if (!reachable(lv_out)) return false;
+    if (msign) nu = nu >= pt_nu ? nu : pt_nu;
     ca = 0;
     if (has_c) {
       if (!constant(re)) return false;
@@ -172,18 +197,22 @@ struct Book {
 };
 
 // ---- the sequences --------------------------------------------------------------------------------------------------------------------------
-template <class O> void seq_inv(O &o, unsigned iter) {                   // src/he-algo.c:131-164
-  enum { CT, TMP, AN, BN };
-  const Term neg[1] = {{CT, -1}};
-  o.lin(AN, neg, 1, 1, true, 2);                                         // :145-148  tmp = -ct; an = tmp + two; he_moddown(&an)
-  o.lin(BN, neg, 1, 0, true, 1);                                         // :149      bn = tmp + one
+// he_inv's slots by name, and what it inverts: the sum of K <= 2 terms at one level (the caller's he_add in front of a nested he_inv rides in
+// the two opening sums).  The default is the function on its own: the input, and the reference's three temporaries.
+struct InvSlots { int TMP, AN, BN; Term src[2]; unsigned K; };
+template <class O> void seq_inv(O &o, unsigned iter, const InvSlots &n = InvSlots{1, 2, 3, {{0, 1}, {0, 1}}, 1}, bool nested = false) {   // src/he-algo.c:131-164
+  const int TMP = n.TMP, AN = n.AN, BN = n.BN;
+  const Term neg[2] = {{n.src[0].slot, -n.src[0].sign}, {n.src[1].slot, -n.src[1].sign}};
+  const unsigned lv = o.lv(n.src[0].slot);
+  o.lin(AN, neg, n.K, lv + 1, true, 2);                                  // :145-148  tmp = -ct; an = tmp + two; he_moddown(&an)
+  o.lin(BN, neg, n.K, lv, true, 1);                                      // :149      bn = tmp + one
   for (unsigned i = 0; i < iter; ++i) {
     o.mul(BN, BN, BN);                                                   // :151-152
     const Term b[1] = {{BN, 1}};
     o.lin(TMP, b, 1, o.lv(BN), true, 1);                                 // :153
     o.mul(AN, AN, TMP);                                                  // :154-155
   }
-  o.ret(AN);                                                             // :157
+  if (!nested) o.ret(AN);                                                // :157 (nested: the caller reads AN)
 }
 
 template <class O> void seq_sqrt(O &o, unsigned iter) {                  // :166-206
@@ -278,6 +307,49 @@ template <class O> void seq_exp(O &o, unsigned iter) {                   // :364
   o.lin(RES, sum, 3, o.lv(CT4567));                                      // :389, :399-400, :421
   for (unsigned i = 0; i < iter; ++i) o.mul(RES, RES, RES);              // :452-455
   o.ret(RES);
+}
+
+// he_cmp (with_pt = false: slot 1 is the second ciphertext) and he_cmppt (the call's dense plaintext), src/he-algo.c:460-548.  Eight slots.
+// The two he_inv are seq_inv's text on three slots of their own; he_cmp_core's bn = 1 - an (:485-486, :499-500) is written where the next
+// round reads it, so the last one -- it feeds nothing -- is never computed (as he_sqrt's).
+template <class O> void seq_cmp(O &o, unsigned iter, unsigned t, bool with_pt) {
+  enum { CT, CT2, INV, AN, BN, ITMP, IAN, IBN };                         // (AN = CMP_AN, BN = CMP_BN)
+  const Term sum[2] = {{CT, 1}, {CT2, 1}}, an[1] = {{AN, 1}}, nan[1] = {{AN, -1}};
+  const InvSlots first{ITMP, IAN, IBN, {{INV, 1}, {INV, 1}}, 1}, round{ITMP, IAN, IBN, {{AN, 1}, {BN, 1}}, 2};
+  if (with_pt) o.lin(INV, sum, 1, 0, false, 0.0, 1, 1);                  // :543  he_addpt(&an, ct, pt)
+  else o.lin(INV, sum, 2, 0);                                            // :525  he_add(&an, ct1, ct2)   (:466 inv = an)
+  o.mulc(INV, INV, 0.5);                                                 // :473-474  l-1
+  seq_inv(o, iter, first, true);                                         // :475      l-2-iter, in IAN
+  o.mulc(AN, CT, 0.5);                                                   // :477-478  l-1
+  o.lin(AN, an, 1, o.lv(AN) + iter + 1);                                 // :479-480  iter + 1 he_moddown
+  o.mul(AN, AN, IAN);                                                    // :482-483  l-3-iter
+  for (unsigned r = 0; r < t; ++r) {
+    o.lin(BN, nan, 1, o.lv(AN), true, 1);                                // :485-486 / :499-500  bn = -(an - one)
+    o.sq2(AN, BN);                                                       // :489-492  an = an^2, bn = bn^2: independent and at one level, ONE product
+    seq_inv(o, iter, round, true);                                       // :493-494  he_add(&inv, an, &bn) rides in he_inv's two sums
+    o.lin(AN, an, 1, o.lv(AN) + iter + 1);                               // :495-496
+    o.mul(AN, AN, IAN);                                                  // :497-498
+  }
+  o.ret(AN);                                                             // :527 / :545
+}
+enum { CMP_SINGLES = 4, CMP_AN = 3, CMP_BN = 4 };                        // INV and he_inv's three; an and bn (sq2) live side by side
+// bridge_algo.hpp's allocator names the singles, their spare and the four halves of the two double buffers in one table of SLOTS entries
+static_assert(CMP_SINGLES + 1 + 4 <= SLOTS, "he_cmp's buffers do not fit the evaluators' buffer table");
+
+// (3 + iter)(1 + t), the levels he_cmp / he_cmppt consume; -1 beyond 4096 (64 words of 64 bits hold no more levels)
+inline int cmp_depth(unsigned iter, unsigned t) {
+  if (iter > 4096 || t > 4096) return -1;
+  const uint64_t d = (uint64_t)(3 + iter) * (1 + t);
+  return d > 4096 ? -1 : (int)d;
+}
+
+template <class O> bool run_cmp(O &o, unsigned iter, unsigned t, bool with_pt) {
+  if (o.err) return false;
+  const int d = cmp_depth(iter, t);
+  if (d < 0) return o.fail("a level would fall below logql = 1");
+  if (!o.reachable((unsigned)d)) return false;          // before any loop over iter or t
+  seq_cmp(o, iter, t, with_pt);
+  return o.err == GPQ_OK;
 }
 
 // false: refused (o.err, o.why)

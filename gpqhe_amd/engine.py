@@ -407,6 +407,53 @@ class PolyContext:
         _native.check(self.he_algo_call(kind, out_c0, out_c1, c0, c1, rlk0, rlk1, W, logqL, logql, logDelta, iter, ws, m, dimpt), "gpq_he_" + kind)
         return ws
 
+    def he_lin_pt(self, out_c0, out_c1, terms, m, W, logql, msign=1, a=0, b=0):
+        """he_lin_const plus msign * m in c0: he_addpt / he_subpt by ONE dense plaintext m (a big slab of one polynomial, shared by the batch)"""
+        K = len(terms)
+        batch = terms[0][0].numel() // (W * self.n)
+        x0 = (C.c_void_p * 3)(*[self._ptr(t[0]).value for t in terms])
+        x1 = (C.c_void_p * 3)(*[self._ptr(t[1]).value for t in terms])
+        sg = (C.c_int * 3)(*[int(t[2]) for t in terms])
+        _native.check(self.lib.gpq_he_lin_pt(self.h, self._ptr(out_c0), self._ptr(out_c1), x0, x1, sg, K, self._ptr(m), msign, a, b, W, logql, batch,
+                                             self._stream()), "gpq_he_lin_pt")
+
+    # --- he_cmp / he_cmppt (src/he-algo.c:460-548) ---
+    @staticmethod
+    def he_cmp_rounds(alpha):
+        """he_cmp's t for alpha in 1..52, -1 otherwise.  Host only."""
+        return int(_native.load().gpq_he_cmp_rounds(alpha))
+
+    @staticmethod
+    def he_cmp_depth(iter, t):
+        """(3 + iter)(1 + t), or -1.  Host only."""
+        return int(_native.load().gpq_he_cmp_depth(iter, t))
+
+    def he_cmp_workspace_bytes(self, with_pt, W, logqL, logql, logDelta, iter, t, batch):
+        """bytes of a gpq_he_cmp (with_pt false) / gpq_he_cmppt call's workspace; 0 when the call would be refused"""
+        return int(self.lib.gpq_he_cmp_workspace_bytes(self.h, 1 if with_pt else 0, W, logqL, logql, logDelta, iter, t, batch))
+
+    def he_cmp_call(self, out_c0, out_c1, a_c0, a_c1, other, rlk0, rlk1, W, logqL, logql, logDelta, iter, t, workspace):
+        """the return code of gpq_he_cmp (other = (b_c0, b_c1)) or gpq_he_cmppt (other = the plaintext slab m) on a caller-owned workspace"""
+        batch = a_c0.numel() // (W * self.n)
+        head = [self.h, self._ptr(out_c0), self._ptr(out_c1), self._ptr(a_c0), self._ptr(a_c1)]
+        tail = [self._ptr(rlk0), self._ptr(rlk1), W, logqL, logql, logDelta, iter, t, batch, self._ptr(workspace), self._stream()]
+        if isinstance(other, (tuple, list)):
+            return self.lib.gpq_he_cmp(*head, self._ptr(other[0]), self._ptr(other[1]), *tail)
+        return self.lib.gpq_he_cmppt(*head, self._ptr(other), *tail)
+
+    def he_cmp(self, out_c0, out_c1, a_c0, a_c1, other, rlk0, rlk1, W, logqL, logql, logDelta, iter, t):
+        """he_cmp(a, other = (b_c0, b_c1)) or he_cmppt(a, other = m) of the batch as one call; t from he_cmp_rounds(alpha)"""
+        torch = _torch()
+        batch = a_c0.numel() // (W * self.n)
+        with_pt = not isinstance(other, (tuple, list))
+        nbytes = self.he_cmp_workspace_bytes(with_pt, W, logqL, logql, logDelta, iter, t, batch)
+        if not nbytes:
+            raise _native.GpqError("gpq_he_cmp_workspace_bytes: " + self.lib.gpq_last_error().decode())
+        ws = torch.empty(nbytes // 8, dtype=torch.int64, device=self._dev)
+        _native.check(self.he_cmp_call(out_c0, out_c1, a_c0, a_c1, other, rlk0, rlk1, W, logqL, logql, logDelta, iter, t, ws),
+                      "gpq_he_cmppt" if with_pt else "gpq_he_cmp")
+        return ws
+
     def he_genswk(self, evk0, evk1, p1, sk, e, sp, W, dimP, logqL, dimevk):
         """src/he-kem.c:74-118 from host-sampled p1 / e and the hidden polynomial sp; q_L = 2^logqL."""
         torch = _torch()

@@ -1,5 +1,5 @@
-/* gpqhe_hip_algo.h -- the evaluators of src/he-algo.c:131-458 (he_inv, he_sqrt, he_sigmoid, he_log, he_exp) as single device calls on big slabs,
- * and the one kernel they add to the library, gpq_he_lin_const.  Companion of gpqhe_hip.h (contexts, slab layout, error codes, every call the
+/* gpqhe_hip_algo.h -- the evaluators of src/he-algo.c:131-548 (he_inv, he_sqrt, he_sigmoid, he_log, he_exp, he_cmp, he_cmppt) as single device
+ * calls on big slabs, and the one kernel they add to the library, gpq_he_lin_const (with a dense plaintext term: gpq_he_lin_pt).  Companion of gpqhe_hip.h (contexts, slab layout, error codes, every call the
  * evaluators are made of); DESIGN.md section 6, "Evaluators".
  *
  * Stream class (gpqhe_hip.h, "stream classes"): every function below that takes a `void *stream` is CAPTURABLE -- all its device work is queued
@@ -70,6 +70,43 @@ int gpq_he_log(gpq_ctx *ctx, uint64_t *out_c0, uint64_t *out_c1, const uint64_t 
 int gpq_he_exp(gpq_ctx *ctx, uint64_t *out_c0, uint64_t *out_c1, const uint64_t *c0, const uint64_t *c1, const uint64_t *m, unsigned dimpt,
                const uint64_t *rlk0, const uint64_t *rlk1, unsigned W, unsigned logqL, unsigned logql, unsigned logDelta, unsigned iter,
                unsigned batch, void *workspace, void *stream);
+
+/* gpq_he_lin_const plus ONE dense plaintext: he_addpt (msign = +1) / he_subpt (msign = -1) by any plaintext (src/he-add.c:80-123) as one more
+ * addend of the same launch.
+ *   out.c0 = smod(s_0 x_0.c0 + .. + s_(K-1) x_(K-1).c0 + msign m + (a + b x^h), 2^logql)          out.c1 as gpq_he_lin_const's
+ * m: a W-word two's-complement big slab of ONE polynomial, shared by the whole batch (no batch stride), as gpq_he_exp takes its plaintext.
+ * Everything else, the refusals included, is gpq_he_lin_const's; also refused: m NULL, msign not +-1, m overlapping an output.  CAPTURABLE. */
+int gpq_he_lin_pt(gpq_ctx *ctx, uint64_t *out_c0, uint64_t *out_c1, const uint64_t *const x_c0[3], const uint64_t *const x_c1[3],
+                  const int sign[3], unsigned K, const uint64_t *m, int msign, int64_t a, int64_t b, unsigned W, unsigned logql, unsigned batch,
+                  void *stream);
+
+/* he_cmp and he_cmppt (src/he-algo.c:460-548) as single calls.
+ * The reference derives its round count from alpha: t = (unsigned)log2(alpha / log2(1 + pow(2, -(int)alpha))) (:519-520).  gpq_he_cmp_rounds
+ * evaluates that C double expression for 1 <= alpha <= 52 and returns -1 otherwise (alpha = 0 takes log2(0), alpha >= 53 divides by
+ * log2(1.0) = 0: the reference converts an infinity to unsigned, which is undefined).  he_cmppt's own expression (:537) negates an UNSIGNED
+ * alpha and is undefined for every alpha, so both calls below take t, and a caller of he_cmppt says which t it means.  Host only. */
+int gpq_he_cmp_rounds(unsigned alpha);
+/* (3 + iter)(1 + t), the levels both consume; -1 where that overflows or exceeds 4096.  Host only. */
+int gpq_he_cmp_depth(unsigned iter, unsigned t);
+/* Bytes of the workspace of gpq_he_cmp (with_pt = 0) / gpq_he_cmppt (1): four temporaries and a spare as big slabs of `batch` ciphertexts, two
+ * slabs of 2 batch ciphertexts (an and bn side by side: the two squarings of a round are ONE gpq_he_mul_rs over 2 batch ciphertexts, out of one
+ * into the other), plus the largest gpq_he_mul_workspace_bytes of the levels, at 2 batch where there is a round.  0 when the call would be
+ * refused (gpq_last_error says why). */
+size_t gpq_he_cmp_workspace_bytes(gpq_ctx *ctx, int with_pt, unsigned W, unsigned logqL, unsigned logql, unsigned logDelta, unsigned iter,
+                                  unsigned t, unsigned batch);
+/* out = he_cmp(a, b) / he_cmppt(ct, m) of `batch` ciphertexts, the contract of the five evaluators above: the reference's sequence call for
+ * call with every additive chain in one gpq_he_lin_const / gpq_he_lin_pt, the nested he_inv included (its text, run once more on other
+ * temporaries); he_cmp_core's last bn = 1 - an feeds nothing and is not computed.  Inputs centred mod 2^logql and never written; the output is
+ * centred mod 2^(logql - gpq_he_cmp_depth(iter, t) logDelta).  out_c0 / out_c1 may be a_c0 / a_c1 (c0 / c1) and overlap nothing else.
+ * m: ONE plaintext big slab (W words) shared by the batch, any integers: it enters through one mpi_smod at the input's level.
+ * Refusals as above, decided before anything is launched; also batch > 16383 where t > 0.  `workspace`: gpq_he_cmp_workspace_bytes.
+ * CAPTURABLE. */
+int gpq_he_cmp(gpq_ctx *ctx, uint64_t *out_c0, uint64_t *out_c1, const uint64_t *a_c0, const uint64_t *a_c1, const uint64_t *b_c0,
+               const uint64_t *b_c1, const uint64_t *rlk0, const uint64_t *rlk1, unsigned W, unsigned logqL, unsigned logql, unsigned logDelta,
+               unsigned iter, unsigned t, unsigned batch, void *workspace, void *stream);
+int gpq_he_cmppt(gpq_ctx *ctx, uint64_t *out_c0, uint64_t *out_c1, const uint64_t *c0, const uint64_t *c1, const uint64_t *m,
+                 const uint64_t *rlk0, const uint64_t *rlk1, unsigned W, unsigned logqL, unsigned logql, unsigned logDelta, unsigned iter,
+                 unsigned t, unsigned batch, void *workspace, void *stream);
 
 #ifdef __cplusplus
 }

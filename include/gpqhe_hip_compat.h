@@ -254,6 +254,18 @@ int gpq_shim_he_sqrt(he_ct_t *dst, const he_ct_t *src, const he_evk_t *rlk, unsi
 int gpq_shim_he_sigmoid(he_ct_t *dst, const he_ct_t *src, const he_evk_t *rlk);
 int gpq_shim_he_log(he_ct_t *dst, const he_ct_t *src, const he_evk_t *rlk);
 int gpq_shim_he_exp(he_ct_t *dst, _Complex double a, const he_ct_t *src, const he_evk_t *rlk, unsigned iter);
+/* he_cmp and he_cmppt (src/he-algo.c:460-548) the same way, around gpq_he_cmp / gpq_he_cmppt: ONE staged call, both sources found resident or
+ * uploaded once (he_cmp(&d, &ct, &ct, ..): once), one counting pass per source, one download; dst->l / nu / B replayed over the text the device
+ * runs.  dst may be ct1 or ct2.  0, dst untouched, in every case above, and also when ct1->l != ct2->l (the reference asserts), alpha is
+ * outside 1..52 (gpq_he_cmp_rounds: the reference's t = log2(alpha / log2(1 + 2^-alpha)) is defined there only) or the depth
+ * (3 + iter)(1 + t) does not fit.
+ * gpq_shim_he_cmppt takes t, NOT alpha: the reference computes pow(2, -alpha) with alpha unsigned (:537), so its c is inf and its t the
+ * conversion of -inf to unsigned -- undefined behaviour, which the library does not guess.  A GPQHE build forwards after computing its t:
+ *     void he_cmppt(he_ct_t *d, const he_ct_t *s, const he_pt_t *pt, const he_evk_t *rlk, const unsigned int iter, const unsigned int alpha)
+ *     { ...its t...; if (gpq_shim_he_cmppt(d, s, pt, rlk, iter, t)) return; ...its loop... }
+ * The plaintext is any he_pt_t: converted and uploaded as he_exp's, the slabs widened to its bits; 0 beyond 32 words.  pt->nu enters nu. */
+int gpq_shim_he_cmp(he_ct_t *dst, const he_ct_t *ct1, const he_ct_t *ct2, const he_evk_t *rlk, unsigned iter, unsigned alpha);
+int gpq_shim_he_cmppt(he_ct_t *dst, const he_ct_t *ct, const he_pt_t *pt, const he_evk_t *rlk, unsigned iter, unsigned t);
 /* How a resident key is recognised: by the caller's two pointers and a fingerprint of EVERY word, limb by limb (full != 0, the
  * default: a key edited in place multiplies as edited, like the reference, which reads its key on every call), computed by the
  * conversion threads while the device works; a call at a lower level, which reads fewer limbs of the same key (src/he-mult.c:51),
